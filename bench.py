@@ -5,7 +5,7 @@ A "step" = one complete two-phase simplex solve of dense-LP(2048,2048,seed) (BAS
 tableau 2049 x 2049 fp64, 3923 pivots for seed 42) by the HIP path, starting from a pristine
 copy of the tableau that is already resident in HBM.  value = pivots executed / wall time.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--size 2048] [--workload replicas|sharded]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--size 2048] [--workload replicas|sharded] [--dump-outputs DIR]
   N > 1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
          one process per GPU; every rank solves its own LP (seed 42 + rank) -- independent
          sub-problems shard with no data-path collective (weak scaling); torch.distributed
@@ -21,6 +21,11 @@ copy of the tableau that is already resident in HBM.  value = pivots executed / 
          children are separate processes with a time limit, so that nothing that goes wrong there -- RCCL init, graph
          capture, memory, a hang -- can change this run's return code or headline: it becomes "sharded_c5": {"error": ...}
          (--no-sharded-c5 skips it).
+
+  --dump-outputs DIR: after the timed steps, what the last timed step computed -- the tableau it left, both permutations
+         and [status, objective cell, pivots] -- as DIR/<name>.npy in float64 (rank<r>_<name>.npy when N > 1), at most
+         64 MB in all: beyond that a fixed, seeded sample of the tableau's rows (tableau_rows = their global indices).
+         The inputs depend only on the arguments, so two builds can be compared output for output.
 
 Extra objects on the JSON line (N == 1 / rank 0 only):
   roofline      the dominant (only) kernel of the timed region.  At 2049^2 the tableau fits on chip
@@ -115,6 +120,33 @@ def measured_exchange_floor(native, ctx, nb, T, J, epochs=4000):
     return out
 
 
+DUMP_BYTES = 64 * 10**6  # --dump-outputs: at most this much in all, files with their headers (shared by the ranks)
+NPY_HEADER_BYTES = 1024  # room kept per file for its .npy header (np.save writes 128 bytes for these arrays)
+
+
+def dump_outputs(path, rank, world, tableau, row_ids, status, result, pivots, pos, var):
+    """--dump-outputs: the rows of the tableau the last timed step left (row_ids: their global indices), both permutations
+    and the solve's scalars, as float64 .npy files.  Beyond this rank's share of DUMP_BYTES a fixed, seeded sample of the
+    rows is written, the objective row always among them."""
+    from yalps_amd import _native
+    os.makedirs(path, exist_ok=True)
+    arrays = {"position_of_variable": pos, "variable_at_position": var,
+              "summary": [_native.STATUS.index(status), result, pivots]}  # [status code (_native.STATUS), objective cell, pivots]
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    n, w = tableau.shape
+    room = DUMP_BYTES // world - NPY_HEADER_BYTES * (len(arrays) + 2) - sum(a.nbytes for a in arrays.values())
+    keep = room // (8 * w + 8)  # (a row of the tableau and its entry in tableau_rows)
+    if keep < n:
+        pick = np.sort(np.random.default_rng(20261015).choice(np.arange(1, n), keep - 1, replace=False))
+        pick = np.concatenate([[0], pick])
+        tableau, row_ids = tableau[pick], row_ids[pick]
+    arrays["tableau"] = np.asarray(tableau, dtype=np.float64)
+    arrays["tableau_rows"] = np.asarray(row_ids, dtype=np.float64)
+    prefix = "rank%d_" % rank if world > 1 else ""
+    for name, a in arrays.items():
+        np.save(os.path.join(path, prefix + name + ".npy"), a)
+
+
 def cpu_baseline(M, N, seed, budget_pivots, threads=1):
     """Oracle (kind "port") on a bounded sample: the first `budget_pivots` pivots of the same LP
     (all of them by default: 3923 pivots of the 2049x2049 tableau take ~7-10 s on one core).
@@ -138,7 +170,7 @@ def cpu_baseline(M, N, seed, budget_pivots, threads=1):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--size", type=int, default=2048, help="M = N of dense-LP(M,N,seed)")
     ap.add_argument("--cpu-pivots", type=float, default=float("inf"),
@@ -157,7 +189,11 @@ def main():
     ap.add_argument("--no-sharded-c5", action="store_true", help="N > 1, default workload: skip the row-sharded config-5 measurement")
     ap.add_argument("--sharded-c5-size", type=int, default=16384, help="M = N of the row-sharded LP measured beside the replicas when N > 1")
     ap.add_argument("--sharded-c5-timeout", type=float, default=420.0, help="seconds the children of that measurement get")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float64, at most 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     rank = int(os.environ.get("RANK", "0"))
@@ -220,6 +256,10 @@ def main():
     assert status == "optimal", status
     if seed == 42 and args.size == 2048:  # known answer of the reference
         assert (npiv, result) == (3923, -1022.09813705), (npiv, result)
+    if args.dump_outputs:  # (work still holds the last timed step's result: nothing has run on it since)
+        m_out, pos_out, var_out = work.download()
+        dump_outputs(args.dump_outputs, rank, world, m_out.reshape(h, w), np.arange(h), status, result, npiv, pos_out, var_out)
+        del m_out
 
     tot = torch.tensor([dt, float(pivots)], dtype=torch.float64, device="cpu" if rehearsal else "cuda")
     if dist is not None:
@@ -313,10 +353,15 @@ def main():
                 "kernel": info["streaming"], "avg_us": us_apply, "achieved_GBps": bpp / (us_apply * 1e-6) / 1e9,
                 "note": "the general (HBM-streaming) kernel in APPLY mode, fixed pivot, back-to-back launches"}
             if args.cpu_pivots > 0:
-                out["cpu_baseline"] = cpu_baseline(M, N, seed, args.cpu_pivots)
+                # (a CPU figure that cannot be taken is reported on the line; the GPU measurement above stands)
                 threads = min(args.cpu_threads, os.cpu_count() or 1)
-                if threads > 1:
-                    out["cpu_baseline_all_cores"] = cpu_baseline(M, N, seed, args.cpu_pivots, threads)
+                for key, n in (("cpu_baseline", 1), ("cpu_baseline_all_cores", threads)):
+                    if key == "cpu_baseline" or threads > 1:
+                        try:
+                            out[key] = cpu_baseline(M, N, seed, args.cpu_pivots, n)
+                        except Exception as e:  # noqa: BLE001
+                            out[key] = {"value": None, "unit": "pivots/s", "error": "%s: %s" % (type(e).__name__, e)}
+                            print("bench.py: %s not taken: %s" % (key, out[key]["error"]), file=sys.stderr)
     work.close()
     pristine.close()
     ctx.close()
@@ -388,7 +433,7 @@ def bench_sharded(args, torch, dist, rank, local_rank, world):
     local = np.concatenate([_native.dense_lp_rows(M, N, 42, 0, 1), _native.dense_lp_rows(M, N, 42, bounds[rank], bounds[rank + 1])])
     rehearsal = world > torch.cuda.device_count()  # (ranks share GPU 0: RCCL refuses; the host transport over gloo instead)
 
-    def run(pivots):
+    def run(pivots, dump=False):
         ops = sharded.HipShardOps(local, w, bounds, rank, h, ident, ident.copy(), device=local_rank, private_stream=True)
         comm = sharded.native_comm(ops.ctx, rank, world, transport="host" if rehearsal else "rccl")
         if dist is not None:
@@ -402,12 +447,17 @@ def bench_sharded(args, torch, dist, rank, local_rank, world):
         dt = time.perf_counter() - t0
         info = comm.info()
         info["kernel"] = ops.tab.info()["streaming"]
+        if dump:  # this rank's rows: the objective row and global rows bounds[rank] .. bounds[rank + 1]
+            lm, pos, var = ops.download()
+            rows = np.concatenate([[0], np.arange(bounds[rank], bounds[rank + 1])])
+            dump_outputs(args.dump_outputs, rank, world, lm.reshape(-1, w), rows, status, result, npiv, pos, var)
+            del lm
         comm.close()
         ops.close()
         return dt, npiv, status, gpu_ms, info
 
     run(args.pivots_per_step * max(args.warmup, 1))
-    dt, npiv, status, gpu_ms, info = run(args.pivots_per_step * args.steps)
+    dt, npiv, status, gpu_ms, info = run(args.pivots_per_step * args.steps, dump=bool(args.dump_outputs))
     verdict = verify_sharded(args, torch, dist, sharded, local, w, h, M, N, bounds, ident, rank, local_rank, world, rehearsal) if args.verify_pivots > 0 else None
     t = torch.tensor([dt], dtype=torch.float64, device="cpu" if rehearsal else "cuda")
     if dist is not None:
