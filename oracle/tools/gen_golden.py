@@ -7,7 +7,9 @@ TEST-FIXTURE TOOLING, build container only (needs /root/reference and node).
   2. a small driver (written below, our code) feeds the reference's
      tableauModel()+simplex() with (a) every tests/cases/*.json model of the
      reference's own test-suite, (b) dense-LP(M,N,seed) tableaux (SURVEY.md
-     section 8d) and (c) sparse mixed-sign tableaux with near-1e-16 entries,
+     section 8d), (c) sparse mixed-sign tableaux with near-1e-16 entries and
+     (d) the edge tableaux of tests/_edges.py (ties, infinite ratios, signed
+     zeros, the flush band, exact thresholds, extreme exponents),
      and records for each run: status, result, the pivot sequence, the final
      permutations, the final RHS column and SHA-256 digests of the initial and
      final Float64Array bytes;
@@ -24,6 +26,8 @@ import os
 import shutil
 import subprocess
 import sys
+import tempfile
+import time
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(os.path.dirname(HERE))
@@ -121,6 +125,17 @@ if (mode === "cases") {
     const [pos, vr] = identityPerms(w + h)
     run({ kind: "mixed", id: id++, M, N, seed }, { matrix: Float64Array.from(init), width: w, height: h, positionOfVariable: pos, variableAtPosition: vr }, opts, true)
   }
+} else if (mode === "edges") {
+  // tableaux of tests/_edges.py, written by gen_golden.py as raw float64 files: argv[3] lists them (JSON)
+  for (const spec of JSON.parse(fs.readFileSync(process.argv[3], "utf-8"))) {
+    const buf = fs.readFileSync(spec.file)
+    const matrix = new Float64Array(buf.buffer.slice(buf.byteOffset, buf.byteOffset + buf.length))
+    const w = spec.N + 1, h = spec.M + 1
+    const [pos, vr] = identityPerms(w + h)
+    const opts = { precision: spec.precision, maxPivots: spec.maxPivots, checkCycles: spec.checkCycles }
+    run({ kind: "edges", family: spec.family, M: spec.M, N: spec.N, seed: spec.seed, layout: spec.layout },
+        { matrix, width: w, height: h, positionOfVariable: pos, variableAtPosition: vr }, opts, w * h <= 20000)
+  }
 }
 """
 
@@ -131,10 +146,46 @@ def run_driver(erased, mode, *args):
     return [json.loads(line) for line in out.splitlines() if line.startswith("{")]
 
 
+def edge_specs(tmp):
+    """Writes every tableau of tests/_edges.py to a raw float64 file under `tmp` (outside the repository) and returns the
+    list the driver's "edges" mode reads."""
+    sys.path.insert(0, REPO)
+    from tests import _edges as E
+    specs = []
+    for i, (family, M, N, seed) in enumerate(E.specs()):
+        layout = E.default_layout(M, N)
+        m = E.make(family, M, N, seed, layout)
+        path = os.path.join(tmp, "edge_%04d.f64" % i)
+        m.tofile(path)
+        o = E.options(family, M, N, seed)
+        specs.append(dict(file=path, family=family, M=M, N=N, seed=seed, layout=[list(layout[0]), list(layout[1])],
+                          precision=o["precision"], maxPivots=o["max_pivots"], checkCycles=o["check_cycles"]))
+    with open(os.path.join(tmp, "edges.json"), "w") as f:
+        json.dump(specs, f)
+    return os.path.join(tmp, "edges.json")
+
+
+def compact(rec):
+    """Edge records of large tableaux: the permutations as the entries that differ from the identity, and col0 of more
+    than 1024 rows as its SHA-256 (final_sha256 covers it as well)."""
+    import base64
+    import hashlib
+    import numpy as np
+    for key in ("pos", "var"):
+        p = np.frombuffer(base64.b64decode(rec[key]), np.int32)
+        idx = np.flatnonzero(p != np.arange(p.size)).astype(np.int32)
+        rec[key] = {"n": int(p.size), "idx": base64.b64encode(idx.tobytes()).decode(),
+                    "val": base64.b64encode(p[idx].tobytes()).decode()}
+    if rec["height"] > 1024:
+        rec["col0_sha256"] = hashlib.sha256(base64.b64decode(rec.pop("col0"))).hexdigest()
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--max-dense", type=int, default=2048)
     ap.add_argument("--erased-dir", default="/tmp/yalps_erased")
+    ap.add_argument("--only", nargs="*", default=("cases", "mixed", "dense", "edges"))
     args = ap.parse_args()
 
     erased = erase(args.erased_dir)
@@ -143,15 +194,22 @@ def main():
     golden = os.path.join(REPO, "tests", "golden")
     os.makedirs(os.path.join(golden, "cases"), exist_ok=True)
 
-    for mode, extra in (("cases", ()), ("mixed", ()), ("dense", (args.max_dense,))):
-        recs = run_driver(erased, mode, *extra)
+    tmp = tempfile.mkdtemp(prefix="yalps_edges_")
+    for mode, extra in (("cases", ()), ("mixed", ()), ("dense", (args.max_dense,)), ("edges", ())):
+        if mode not in args.only:
+            continue
+        t0 = time.time()
+        recs = run_driver(erased, mode, *(extra if mode != "edges" else (edge_specs(tmp),)))
+        if mode == "edges":
+            recs = [compact(r) for r in recs]
         path = os.path.join(golden, f"simplex_{mode}.json.gz")
         with gzip.GzipFile(path, "wb", mtime=0) as gz:
             gz.write(json.dumps({"generator": "oracle/tools/gen_golden.py", "reference": "Ivordir/YALPS src/simplex.ts "
                                  "(type-erased, node %s)" % subprocess.run(["node", "--version"], capture_output=True,
                                                                            text=True).stdout.strip(),
                                  "records": recs}).encode())
-        print(f"{mode}: {len(recs)} records -> {path} ({os.path.getsize(path)} bytes)")
+        print(f"{mode}: {len(recs)} records -> {path} ({os.path.getsize(path)} bytes, {time.time() - t0:.0f} s)")
+    shutil.rmtree(tmp)
 
     # the reference test-suite's own data files (model + expected), as data
     src = "/root/reference/tests/cases"

@@ -4,12 +4,35 @@ simplex() as oracle/simplex_oracle.c -- src/simplex.ts:5-39 (pivot), :66-103 (ph
 full sizes (16385 x 16385: 2.1 GB) can be checked bit for bit in seconds.  numpy never fuses a
 multiply with a subtract, so `a - c * p` rounds twice exactly like V8 and like the kernels.
 It is pinned itself: tests/test_oracle_golden.py runs it over the golden records of the reference.
-No checkCycles (the full-size workloads do not use it)."""
+No checkCycles (the full-size workloads do not use it).
+
+`rules` names deliberate deviations from the reference (MUTANTS): tests/test_edge_records.py shows that the edge records
+of tests/_edges.py tell each of them from the reference.  The default, no deviation, is the reference."""
 import math
 
 import numpy as np
 
 STATUS = ("optimal", "infeasible", "unbounded", "cycled")
+MUTANTS = {  # one comparison site of src/simplex.ts each
+    "obj_ge": "reduced cost >= precision is eligible (:74 is `>`)",
+    "tie_col2": "the last of equal largest reduced costs enters (:75 keeps the first)",
+    "value_ge": "pivot entry >= precision is eligible (:86 is `<= precision: continue`)",
+    "tie_row2": "the last of equal smallest ratios leaves (:89 keeps the first)",
+    "inf_row2": "+inf phase-2 ratios are candidates (:89 never takes +inf)",
+    "break_lt": "the early break takes ratio < precision (:92 is `<=`)",
+    "no_early_break": "phase 2 takes the minimum ratio even after a ratio <= precision (:92)",
+    "rhs_le": "rhs <= -precision starts phase 1 (:115 is `<`)",
+    "tie_row1": "the last of equal most negative right-hand sides leaves (:116 keeps the first)",
+    "coef_le": "phase-1 coefficient <= -precision is eligible (:126 is `<`)",
+    "tie_col1": "the last of equal largest phase-1 ratios enters (:127 keeps the first)",
+    "ninf_col1": "-inf phase-1 ratios are candidates (:127 never takes -inf)",
+    "flush_ge_row": "pivot-row entries with |x| >= 1e-16 are kept (:17 is `>`)",
+    "flush_ge_coef": "rows with |coef| >= 1e-16 are updated (:31 is `>`)",
+    "keep_neg_zero": "flushed pivot-row entries keep their sign (-0.0) instead of becoming +0.0 (:20)",
+    "keep_col": "column col is always in the non-zero list (:17-23)",
+    "patch_kept_only": "1 / q is written only when q itself is outside the flush band (:25)",
+    "ftz": "subnormal results of the pivot are flushed to zero (a GPU's denormal flushing)",
+}
 
 
 def _js_round(x):
@@ -20,11 +43,11 @@ def _js_round(x):
 
 
 def round_to_precision(num, precision):  # src/util.ts:1-4
-    rounding = _js_round(1.0 / precision)
+    rounding = _js_round(1.0 / precision if precision != 0 else math.inf)  # (JS: 1 / 0 = Infinity, the result NaN)
     return _js_round((num + 2.220446049250313e-16) * rounding) / rounding
 
 
-def pivot(M, pos, var, row, col, block=1024):
+def pivot(M, pos, var, row, col, block=1024, rules=frozenset()):
     """src/simplex.ts:5-39 on the 2-D view M (h, w), in place."""
     h, w = M.shape
     q = M[row, col]
@@ -32,31 +55,45 @@ def pivot(M, pos, var, row, col, block=1024):
     var[w + row], var[col] = entering, leaving
     pos[leaving], pos[entering] = col, w + row
     prow = M[row]
-    nz = np.abs(prow) > 1e-16  # :14-23 nonZeroColumns
-    prow[:] = np.where(nz, prow / q, 0.0)
-    prow[col] = 1.0 / q  # :25
+    nz = (np.abs(prow) >= 1e-16) if "flush_ge_row" in rules else (np.abs(prow) > 1e-16)  # :14-23 nonZeroColumns
+    if "keep_col" in rules:
+        nz[col] = True
+    with np.errstate(all="ignore"):
+        prow[:] = np.where(nz, prow / q, np.copysign(0.0, prow) if "keep_neg_zero" in rules else 0.0)
+    if "patch_kept_only" not in rules or abs(q) > 1e-16:
+        prow[col] = 1.0 / q  # :25
     all_nz = bool(nz.all())
     nzi = None if all_nz else np.flatnonzero(nz)
     for r0 in range(0, h, block):  # :27-38
         blk = M[r0:r0 + block]
         coef = blk[:, col].copy()
-        act = np.abs(coef) > 1e-16
+        act = (np.abs(coef) >= 1e-16) if "flush_ge_coef" in rules else (np.abs(coef) > 1e-16)
         if r0 <= row < r0 + block:
             act[row - r0] = False
         if not act.any():
             continue
         ai = np.flatnonzero(act)
-        if all_nz:
-            blk[ai] = blk[ai] - coef[ai, None] * prow[None, :]
-        else:
-            sub = blk[np.ix_(ai, nzi)]
-            blk[np.ix_(ai, nzi)] = sub - coef[ai, None] * prow[None, nzi]
-        blk[ai, col] = -coef[ai] / q  # :36
+        with np.errstate(all="ignore"):
+            if all_nz:
+                blk[ai] = blk[ai] - coef[ai, None] * prow[None, :]
+            else:
+                sub = blk[np.ix_(ai, nzi)]
+                blk[np.ix_(ai, nzi)] = sub - coef[ai, None] * prow[None, nzi]
+            blk[ai, col] = -coef[ai] / q  # :36
+    if "ftz" in rules:
+        M[np.abs(M) < np.finfo(np.float64).tiny] *= 0.0
 
 
-def simplex(matrix, width, height, pos, var, precision=1e-8, max_pivots=8192.0):
+def _first(mask, last=False):
+    idx = np.flatnonzero(mask)
+    return int(idx[-1] if last else idx[0])
+
+
+def simplex(matrix, width, height, pos, var, precision=1e-8, max_pivots=8192.0, rules=frozenset()):
     """Returns (status, result, n_pivots); matrix (flat, row-major) and the permutations are
     updated in place like the reference does."""
+    assert set(rules) <= set(MUTANTS), rules
+    on = set(rules).__contains__
     M = matrix.reshape(height, width)
     npiv = 0
     it = 0.0
@@ -66,34 +103,39 @@ def simplex(matrix, width, height, pos, var, precision=1e-8, max_pivots=8192.0):
             return "cycled", math.nan, npiv
         if phase == 1:
             rhs = M[1:, 0]
-            if rhs.size == 0 or not (rhs.min() < -precision):  # :111-120
+            if rhs.size == 0 or not (rhs.min() <= -precision if on("rhs_le") else rhs.min() < -precision):  # :111-120
                 phase, it = 2, 0.0
                 continue
-            row = int(np.argmin(rhs)) + 1  # first minimum
+            row = _first(rhs == rhs.min(), on("tie_row1")) + 1  # first minimum
             coef = M[row, 1:]
-            elig = np.flatnonzero(coef < -precision)  # :123-134
-            ratio = -M[0, 1:][elig] / coef[elig]
-            ok = ratio > -math.inf
+            elig = np.flatnonzero(coef <= -precision if on("coef_le") else coef < -precision)  # :123-134
+            with np.errstate(all="ignore"):
+                ratio = -M[0, 1:][elig] / coef[elig]
+            ok = np.ones(ratio.shape, bool) if on("ninf_col1") else ratio > -math.inf
             if not ok.any():
                 return "infeasible", math.nan, npiv
             best = ratio[ok].max()
-            col = int(elig[ok][np.argmax(ratio[ok] == best)]) + 1  # first maximum
+            col = int(elig[ok][_first(ratio[ok] == best, on("tie_col1"))]) + 1  # first maximum
         else:
             obj = M[0, 1:]
-            elig = np.flatnonzero(obj > precision)  # :71-79
+            elig = np.flatnonzero(obj >= precision if on("obj_ge") else obj > precision)  # :71-79
             if elig.size == 0:
-                return "optimal", round_to_precision(float(M[0, 0]), precision), npiv
-            col = int(elig[np.argmax(obj[elig])]) + 1
+                with np.errstate(all="ignore"):
+                    return "optimal", round_to_precision(float(M[0, 0]), precision), npiv
+            col = int(elig[_first(obj[elig] == obj[elig].max(), on("tie_col2"))]) + 1
             value = M[1:, col]
-            rows = np.flatnonzero(value > precision)  # :83-95
+            rows = np.flatnonzero(value >= precision if on("value_ge") else value > precision)  # :83-95
             with np.errstate(all="ignore"):
                 ratio = M[1:, 0][rows] / value[rows]
-            ok = ratio < math.inf
+            ok = np.ones(ratio.shape, bool) if on("inf_row2") else ratio < math.inf
             rows, ratio = rows[ok], ratio[ok]
             if rows.size == 0:
                 return "unbounded", float(col), npiv
-            early = np.flatnonzero(ratio <= precision)  # the `break` at :93
-            row = int(rows[early[0]] if early.size else rows[np.argmin(ratio)]) + 1
-        pivot(M, pos, var, row, col)
+            early = np.flatnonzero(ratio < precision if on("break_lt") else ratio <= precision)  # the `break` at :93
+            if on("no_early_break") or not early.size:
+                row = int(rows[_first(ratio == ratio.min(), on("tie_row2"))]) + 1
+            else:
+                row = int(rows[early[0]]) + 1
+        pivot(M, pos, var, row, col, rules=rules)
         it += 1.0
         npiv += 1

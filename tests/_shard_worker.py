@@ -7,7 +7,8 @@ objective row and of every rank's block of rows (full-size runs: the tableau is 
 tests/test_hip_parity.py's sweep cases (one row "-a x <= -b", exact zeros) instead of the seed's parity.
 `c5:<variant>`: the input of tests/_c5.py (BASELINE config 5); rank 0 saves SHA-256 digests per block of 512 rows with
 their global row numbers, every rank's copy of the objective row, column 0 and the basis.
-`npy:<file>[:check]`: the (M+1) x (N+1) tableau in <file> instead of a generated one; `:check` = options.checkCycles."""
+`npy:<file>[:check][:precision=<x>]`: the (M+1) x (N+1) tableau in <file> instead of a generated one; `:check` =
+options.checkCycles, `:precision=<x>` = options.precision (default 1e-8)."""
 import os
 import sys
 
@@ -36,9 +37,11 @@ def main():
     w, h = N + 1, M + 1
     c5 = sys.argv[7][3:] if len(sys.argv) > 7 and sys.argv[7].startswith("c5:") else None
     npy = sys.argv[7][4:] if len(sys.argv) > 7 and sys.argv[7].startswith("npy:") else None
-    check_cycles = bool(npy) and npy.endswith(":check")
+    flags = npy.split(":")[1:] if npy else []
+    check_cycles = "check" in flags
+    precision = float(next((f.split("=", 1)[1] for f in flags if f.startswith("precision=")), 1e-8))
     if npy:
-        m = np.load(npy[:-6] if check_cycles else npy).astype(np.float64).reshape(-1)
+        m = np.load(npy.split(":")[0]).astype(np.float64).reshape(-1)
         assert m.size == w * h
     elif c5:
         from tests import _c5
@@ -74,16 +77,17 @@ def main():
     if kind in ("hip-native", "hip-rccl"):  # (hip-rccl: one rank per GPU -- RCCL refuses ranks that share a device)
         transport = "host" if kind == "hip-native" else "rccl"
         ncomm = sharded.native_comm(ops.ctx, rank, world, transport=transport)
-        status, result, pivots = sharded.sharded_simplex_native(ops, ncomm, max_pivots=max_pivots, check_every=8 if kind == "hip-native" else 64,
-                                                                check_cycles=check_cycles)
+        status, result, pivots = sharded.sharded_simplex_native(ops, ncomm, precision=precision, max_pivots=max_pivots,
+                                                                check_every=8 if kind == "hip-native" else 64, check_cycles=check_cycles)
         assert ncomm.info()["transport"] == transport and int(ncomm.info()["collectives"]) >= pivots
         ncomm.close()
     else:
         comm = sharded.TorchComm()
-        status, result, pivots = sharded.sharded_simplex(ops, comm, max_pivots=max_pivots, check_every=8 if max_pivots > 8 else 1,
-                                                         check_cycles=check_cycles)
+        status, result, pivots = sharded.sharded_simplex(ops, comm, precision=precision, max_pivots=max_pivots,
+                                                         check_every=8 if max_pivots > 8 else 1, check_cycles=check_cycles)
     lap("solve done: %s, %d pivots" % (status, pivots))
     kernel = kind if kind.startswith("numpy") else ops.tab.info()["streaming"]
+    shard_sweep = "" if kind.startswith("numpy") else ops.tab.info().get("shard_sweep", "")  # (dshard: "inline" / "launch")
     lm, pos, var = ops.download()
     lap("downloaded")
     if c5:
@@ -124,7 +128,8 @@ def main():
             if r == 0:
                 full[0] = pm[0]
             full[lo:hi] = pm[1:]
-        np.savez(out, matrix=full.reshape(-1), pos=pos, var=var, status=status, result=result, pivots=pivots, kernel=kernel)
+        np.savez(out, matrix=full.reshape(-1), pos=pos, var=var, status=status, result=result, pivots=pivots, kernel=kernel,
+                 shard_sweep=shard_sweep)
     ops.close()
     dist.barrier()
     dist.destroy_process_group()
