@@ -10,8 +10,12 @@ gen_golden.py runs the erased modules once to emit tests/golden/*.json.gz.
 
 Every edit is a literal, asserted replacement, so a changed reference fails
 loudly instead of silently producing different code.  No behaviour is changed:
-the only non-type edits are `??` -> explicit null checks (node 12 has no `??`)
-and one appended trace hook in pivot() that records (row, col).
+the only non-type edits are `??` -> explicit null checks (node 12 has no `??`),
+one appended trace hook in pivot() that records (row, col), the npm `heap` import
+of branchAndCut.ts pointed at a stand-in module the caller writes (./heap.mjs), and
+trace hooks in branchAndCut() and solve() that only read: the popped node, the
+node's tableau before and after simplex(), the loop's final state, the root solve
+and the tableau handed to solution().  A hook is called only where the caller set it.
 """
 import os
 import re
@@ -93,16 +97,72 @@ UTIL_EDITS = [
 ]
 
 
+# hooks: globalThis.__yalps_bnc = { pop(relaxedEval, cuts), node(tableau, status, result) (node(tableau) before simplex),
+# exit(kind, state) } and globalThis.__yalps_solve = { root(status, result), solution(tabmod, status, result) }
+_HOOK = "globalThis.__yalps_bnc"
+BRANCH_AND_CUT_EDITS = [
+    ('import { Options, SolutionStatus } from "./types.js"\n', ""),
+    ('import { index, Tableau, TableauModel } from "./tableau.js"', 'import { index } from "./tableau.mjs"'),
+    ('import { simplex } from "./simplex.js"', 'import { simplex } from "./simplex.mjs"'),
+    ('import Heap from "heap"', 'import Heap from "./heap.mjs"'),
+    ("const buffer = (matrixLength: number, posVarLength: number): Buffer => ({",
+     "const buffer = (matrixLength, posVarLength) => ({"),
+    ("  tableau: Tableau,\n  { matrix, positionOfVariable, variableAtPosition }: Buffer,\n  cuts: readonly Cut[],\n): Tableau => {",
+     "  tableau,\n  { matrix, positionOfVariable, variableAtPosition },\n  cuts,\n) => {"),
+    ("  tableau: Tableau,\n  intVars: readonly number[],\n): [variable: number, value: number, frac: number] => {",
+     "  tableau,\n  intVars,\n) => {"),
+    ("export const branchAndCut = <VarKey, ConKey>(\n  tabmod: TableauModel<VarKey, ConKey>,\n  initResult: number,\n"
+     "  options: Required<Options>,\n): [TableauModel<VarKey, ConKey>, SolutionStatus, number] => {",
+     "export const branchAndCut = (\n  tabmod,\n  initResult,\n  options,\n) => {"),
+    ("  if (initFrac <= precision) return [tabmod, \"optimal\", initResult]",
+     "  if (initFrac <= precision) { if (%s) %s.exit(\"integral\", {}); return [tabmod, \"optimal\", initResult] }" % (_HOOK, _HOOK)),
+    ("new Heap<Branch>((x, y) => x[0] - y[0])", "new Heap((x, y) => x[0] - y[0])"),
+    ("    const [relaxedEval, cuts] = branches.pop()!\n    if (relaxedEval > bestEval) break",
+     "    const [relaxedEval, cuts] = branches.pop()\n    if (%s) %s.pop(relaxedEval, cuts)\n"
+     "    if (relaxedEval > bestEval) { if (%s) %s.exit(\"break\", { iter }); break }" % (_HOOK, _HOOK, _HOOK, _HOOK)),
+    ("    const [status, result] = simplex(currentTableau, options)\n",
+     "    if (%s) %s.node(currentTableau)\n    const [status, result] = simplex(currentTableau, options)\n"
+     "    if (%s) %s.node(currentTableau, status, result)\n" % (_HOOK, _HOOK, _HOOK, _HOOK)),
+    ("const cutsUpper: Cut[] = []", "const cutsUpper = []"),
+    ("const cutsLower: Cut[] = []", "const cutsLower = []"),
+    ("  // Did the solver \"timeout\"?\n",
+     "  if (%s) %s.exit(\"loop\", { iter, empty: branches.empty(), bestEval, optimalThreshold, timedout })\n" % (_HOOK, _HOOK)),
+]
+
+YALPS_EDITS = [
+    ('import { Model, Options, SolutionStatus, Solution } from "./types.js"\n', ""),
+    ('import { index, tableauModel, TableauModel } from "./tableau.js"', 'import { index, tableauModel } from "./tableau.mjs"'),
+    ('from "./util.js"', 'from "./util.mjs"'),
+    ('from "./simplex.js"', 'from "./simplex.mjs"'),
+    ('from "./branchAndCut.js"', 'from "./branchAndCut.mjs"'),
+    ("const solution = <VarKey, ConKey>(\n  { tableau, sign, variables: vars }: TableauModel<VarKey, ConKey>,\n"
+     "  status: SolutionStatus,\n  result: number,\n  { precision, includeZeroVariables }: Required<Options>,\n"
+     "): Solution<VarKey> => {\n",
+     "const solution = (\n  { tableau, sign, variables: vars },\n  status,\n  result,\n  { precision, includeZeroVariables },\n) => {\n"
+     "  if (globalThis.__yalps_solve) globalThis.__yalps_solve.solution(tableau, status, result)\n"),
+    ("const variables: [VarKey, number][] = []", "const variables = []"),
+    ("const defaultOptionValues: Required<Options> = {", "const defaultOptionValues = {"),
+    ("export const defaultOptions: Required<Options> = {", "export const defaultOptions = {"),
+    ("export const solve = <VarKey = string, ConKey = string>(\n  model: Model<VarKey, ConKey>,\n  options?: Options,\n"
+     "): Solution<VarKey> => {", "export const solve = (\n  model,\n  options,\n) => {"),
+    ("  const [status, result] = simplex(tabmod.tableau, opt)\n",
+     "  const [status, result] = simplex(tabmod.tableau, opt)\n"
+     "  if (globalThis.__yalps_solve) globalThis.__yalps_solve.root(tabmod, status, result)\n"),
+]
+
+
 def erase(out_dir="/tmp/yalps_erased"):
     os.makedirs(out_dir, exist_ok=True)
-    jobs = [("simplex.ts", SIMPLEX_EDITS), ("tableau.ts", TABLEAU_EDITS), ("util.ts", UTIL_EDITS)]
+    jobs = [("simplex.ts", SIMPLEX_EDITS), ("tableau.ts", TABLEAU_EDITS), ("util.ts", UTIL_EDITS),
+            ("branchAndCut.ts", BRANCH_AND_CUT_EDITS), ("YALPS.ts", YALPS_EDITS)]
     for fname, edits in jobs:
         with open(os.path.join(REF_SRC, fname)) as f:
             text = f.read()
         text = _drop_type_decls(_apply(text, edits, fname))
         code = re.sub(r"export \{[^}]*\}", "", text)  # `export { a as b }` is plain JS
         code = re.sub(r"//[^\n]*", "", code)
-        leftover = re.findall(r":\s*(?:number|Tableau|string)\b|\bas\s+\w+|<\w+(?:,\s*\w+)*>\(", code)
+        leftover = re.findall(r":\s*(?:number|Tableau|string|Buffer|Cut|Options|Model)\b|\bas\s+\w+|<\w+(?:,\s*\w+)*>\(|\)!",
+                              code)
         if leftover:
             raise SystemExit(f"erase_types: type syntax left in {fname}: {leftover[:5]}")
         with open(os.path.join(out_dir, fname.replace(".ts", ".mjs")), "w") as f:

@@ -10,6 +10,9 @@ TEST-FIXTURE TOOLING, build container only (needs /root/reference and node).
      section 8d), (c) sparse mixed-sign tableaux with near-1e-16 entries and
      (d) the edge tableaux of tests/_edges.py (ties, infinite ratios, signed
      zeros, the flush band, exact thresholds, extreme exponents),
+     (e) `--only milp`: the MILP models of tests/_milps.py through the
+     reference's solve() (YALPS.ts, branchAndCut.ts on the heap stand-in
+     below), recording every popped node, the exit and the Solution,
      and records for each run: status, result, the pivot sequence, the final
      permutations, the final RHS column and SHA-256 digests of the initial and
      final Float64Array bytes;
@@ -37,6 +40,7 @@ from erase_types import erase  # noqa: E402
 DRIVER = r"""
 import { simplex } from "./simplex.mjs"
 import { tableauModel } from "./tableau.mjs"
+import { solve } from "./YALPS.mjs"
 import * as fs from "fs"
 import * as crypto from "crypto"
 
@@ -125,6 +129,61 @@ if (mode === "cases") {
     const [pos, vr] = identityPerms(w + h)
     run({ kind: "mixed", id: id++, M, N, seed }, { matrix: Float64Array.from(init), width: w, height: h, positionOfVariable: pos, variableAtPosition: vr }, opts, true)
   }
+} else if (mode === "milp") {
+  // models of tests/_milps.py (argv[3] lists them, JSON) through the reference's solve(): the root, every popped node of
+  // branchAndCut, the loop's exit, the tableau solution() reads and the Solution itself
+  const hexd = (x) => { const b = Buffer.alloc(8); b.writeDoubleBE(x, 0); return b.toString("hex") }
+  const sha2 = (a, b) => crypto.createHash("sha256").update(Buffer.from(a.buffer, a.byteOffset, a.byteLength))
+    .update(Buffer.from(b.buffer, b.byteOffset, b.byteLength)).digest("hex")
+  const col0Of = (t) => { const c = new Float64Array(t.height); for (let r = 0; r < t.height; r++) c[r] = t.matrix[r * t.width]; return c }
+  const marshal = (sol) => ({ status: sol.status, result: hexd(sol.result), variables: sol.variables.map(([k, v]) => [k, hexd(v)]) })
+  for (const spec of JSON.parse(fs.readFileSync(process.argv[3], "utf-8"))) {
+    const rec = { kind: "milp", family: spec.family, seed: spec.seed, variant: spec.variant, options: spec.options }
+    const tm = tableauModel(spec.model)
+    rec.width = tm.tableau.width; rec.height = tm.tableau.height; rec.init_sha256 = sha(tm.tableau.matrix)
+    rec.sign = tm.sign; rec.integers = tm.integers
+    const nodes = []
+    let popped = null
+    rec.exit = "root"
+    globalThis.__yalps_bnc = {
+      pop: (ev, cuts) => { popped = { eval: hexd(ev), cuts: cuts.map(([s, v, x]) => [s, v, hexd(x)]) } },
+      node: (t, status, result) => {
+        if (status === undefined) { popped.init_sha256 = sha(t.matrix); globalThis.__yalps_trace = []; return }
+        Object.assign(popped, { status, result: hexd(result), n_pivots: globalThis.__yalps_trace.length / 2,
+                                final_sha256: sha(t.matrix), perm_sha256: sha2(t.positionOfVariable, t.variableAtPosition) })
+        nodes.push(popped)
+      },
+      exit: (kind, st) => {
+        if (kind === "break") { rec.exit = "break"; rec.break_eval = popped.eval; return }
+        if (kind === "integral") { rec.exit = "integral"; return }
+        if (rec.exit === "break") return
+        const o = Object.assign({ maxIterations: 32768 }, spec.options)
+        rec.exit = !(st.iter < o.maxIterations) ? "iterations" : st.empty ? "exhausted"
+          : !(st.bestEval >= st.optimalThreshold) ? "threshold" : "timeout"
+      },
+    }
+    globalThis.__yalps_solve = {
+      root: (tabmod, status, result) => {
+        rec.root = { status, result: hexd(result), n_pivots: globalThis.__yalps_trace.length / 2, final_sha256: sha(tabmod.tableau.matrix) }
+      },
+      solution: (t, status, result) => {
+        rec.best = { status, result: hexd(result), height: t.height, col0_sha256: sha(col0Of(t)),
+                     perm_sha256: sha2(t.positionOfVariable.subarray(0, t.width + t.height), t.variableAtPosition.subarray(0, t.width + t.height)) }
+      },
+    }
+    globalThis.__yalps_trace = []
+    const t0 = Date.now()
+    const sol = solve(spec.model, spec.options)
+    rec.wall_ms = Date.now() - t0
+    globalThis.__yalps_bnc = undefined; globalThis.__yalps_solve = undefined; globalThis.__yalps_trace = undefined
+    rec.nodes = nodes; rec.iterations = nodes.length
+    rec.solution = marshal(sol)
+    if (spec.zero_flip) {
+      const flipped = !(spec.options.includeZeroVariables === true)
+      rec.solution_flip = marshal(solve(spec.model, Object.assign({}, spec.options, { includeZeroVariables: flipped })))
+    }
+    console.log(JSON.stringify(rec))
+  }
 } else if (mode === "edges") {
   // tableaux of tests/_edges.py, written by gen_golden.py as raw float64 files: argv[3] lists them (JSON)
   for (const spec of JSON.parse(fs.readFileSync(process.argv[3], "utf-8"))) {
@@ -136,6 +195,62 @@ if (mode === "cases") {
     run({ kind: "edges", family: spec.family, M: spec.M, N: spec.N, seed: spec.seed, layout: spec.layout },
         { matrix, width: w, height: h, positionOfVariable: pos, variableAtPosition: vr }, opts, w * h <= 20000)
   }
+}
+"""
+
+# The one assumption left in the MILP records: npm `heap` 0.2.7 (the reference's queue, package.json) is not vendored,
+# so branchAndCut.ts runs on this stand-in.  heap 0.2.7 is a port of CPython's heapq: push / pop / empty below
+# are heapq's heappush / heappop with its _siftdown / _siftup, comparing by the reference's comparator `x[0] - y[0] < 0`.
+# tests/test_milp_records.py runs it under node against heapq on push / pop sequences full of ties.
+HEAP_MJS = r"""
+export default class Heap {
+  constructor(cmp) { this.cmp = cmp; this.nodes = [] }
+  empty() { return this.nodes.length === 0 }
+  push(x) { this.nodes.push(x); this._siftdown(0, this.nodes.length - 1) }
+  pop() {
+    const last = this.nodes.pop()
+    if (this.nodes.length === 0) return last
+    const ret = this.nodes[0]
+    this.nodes[0] = last
+    this._siftup(0)
+    return ret
+  }
+  _siftdown(startpos, pos) {
+    const newitem = this.nodes[pos]
+    while (pos > startpos) {
+      const parentpos = (pos - 1) >> 1
+      const parent = this.nodes[parentpos]
+      if (this.cmp(newitem, parent) < 0) { this.nodes[pos] = parent; pos = parentpos; continue }
+      break
+    }
+    this.nodes[pos] = newitem
+  }
+  _siftup(pos) {
+    const endpos = this.nodes.length, startpos = pos, newitem = this.nodes[pos]
+    let childpos = 2 * pos + 1
+    while (childpos < endpos) {
+      const rightpos = childpos + 1
+      if (rightpos < endpos && !(this.cmp(this.nodes[childpos], this.nodes[rightpos]) < 0)) childpos = rightpos
+      this.nodes[pos] = this.nodes[childpos]
+      pos = childpos
+      childpos = 2 * pos + 1
+    }
+    this.nodes[pos] = newitem
+    this._siftdown(startpos, pos)
+  }
+}
+"""
+
+# the stand-in on its own (argv[2]: a JSON list of operation lists, a number = push [number, id], null = pop): prints, per
+# list, the ids popped in order, the heap drained at the end
+HEAP_DRIVER = r"""
+import Heap from "./heap.mjs"
+import * as fs from "fs"
+for (const ops of JSON.parse(fs.readFileSync(process.argv[2], "utf-8"))) {
+  const h = new Heap((x, y) => x[0] - y[0]), out = []
+  ops.forEach((op, id) => { if (op === null) { if (!h.empty()) out.push(h.pop()[1]) } else h.push([op, id]) })
+  while (!h.empty()) out.push(h.pop()[1])
+  console.log(JSON.stringify(out))
 }
 """
 
@@ -165,6 +280,20 @@ def edge_specs(tmp):
     return os.path.join(tmp, "edges.json")
 
 
+def milp_specs(tmp):
+    """The models of tests/_milps.py with their options, as the driver's "milp" mode reads them."""
+    sys.path.insert(0, REPO)
+    from tests import _milps as ML
+    specs = []
+    for family, seed, variant in ML.specs():
+        model, options = ML.make(family, seed, variant)
+        specs.append(dict(family=family, seed=seed, variant=variant, model=model, options=options,
+                          zero_flip=ML.zero_flip(family, seed, variant)))
+    with open(os.path.join(tmp, "milp.json"), "w") as f:
+        json.dump(specs, f)
+    return os.path.join(tmp, "milp.json")
+
+
 def compact(rec):
     """Edge records of large tableaux: the permutations as the entries that differ from the identity, and col0 of more
     than 1024 rows as its SHA-256 (final_sha256 covers it as well)."""
@@ -185,28 +314,32 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--max-dense", type=int, default=2048)
     ap.add_argument("--erased-dir", default="/tmp/yalps_erased")
-    ap.add_argument("--only", nargs="*", default=("cases", "mixed", "dense", "edges"))
+    ap.add_argument("--only", nargs="*", default=("cases", "mixed", "dense", "edges", "milp"))
     args = ap.parse_args()
 
     erased = erase(args.erased_dir)
     with open(os.path.join(erased, "golden_driver.mjs"), "w") as f:
         f.write(DRIVER)
+    with open(os.path.join(erased, "heap.mjs"), "w") as f:
+        f.write(HEAP_MJS)
     golden = os.path.join(REPO, "tests", "golden")
     os.makedirs(os.path.join(golden, "cases"), exist_ok=True)
 
     tmp = tempfile.mkdtemp(prefix="yalps_edges_")
-    for mode, extra in (("cases", ()), ("mixed", ()), ("dense", (args.max_dense,)), ("edges", ())):
+    for mode, extra in (("cases", ()), ("mixed", ()), ("dense", (args.max_dense,)), ("edges", ()), ("milp", ())):
         if mode not in args.only:
             continue
         t0 = time.time()
-        recs = run_driver(erased, mode, *(extra if mode != "edges" else (edge_specs(tmp),)))
+        specs = {"edges": edge_specs, "milp": milp_specs}.get(mode)
+        recs = run_driver(erased, mode, *(extra if specs is None else (specs(tmp),)))
         if mode == "edges":
             recs = [compact(r) for r in recs]
         path = os.path.join(golden, f"simplex_{mode}.json.gz")
+        src = "YALPS.ts, branchAndCut.ts on the heap stand-in of gen_golden.py" if mode == "milp" else "simplex.ts"
+        node = subprocess.run(["node", "--version"], capture_output=True, text=True).stdout.strip()
         with gzip.GzipFile(path, "wb", mtime=0) as gz:
-            gz.write(json.dumps({"generator": "oracle/tools/gen_golden.py", "reference": "Ivordir/YALPS src/simplex.ts "
-                                 "(type-erased, node %s)" % subprocess.run(["node", "--version"], capture_output=True,
-                                                                           text=True).stdout.strip(),
+            gz.write(json.dumps({"generator": "oracle/tools/gen_golden.py",
+                                 "reference": "Ivordir/YALPS src/%s (type-erased, node %s)" % (src, node),
                                  "records": recs}).encode())
         print(f"{mode}: {len(recs)} records -> {path} ({os.path.getsize(path)} bytes, {time.time() - t0:.0f} s)")
     shutil.rmtree(tmp)

@@ -29,6 +29,11 @@ def _js_round(x):
     return f + 1.0 if x - f >= 0.5 else float(f)
 
 
+def _js_ceil(x):
+    """Math.ceil: -0 for a value in (-1, 0), like std::ceil in milp_host.inc (math.ceil returns the integer 0)."""
+    return float(np.ceil(x))
+
+
 def apply_cuts(tableau, buf, cuts):
     """:22-61  new tableau = root tableau + one row per cut (sign, variable, value)."""
     matrix, pos, var = buf
@@ -86,7 +91,7 @@ def branch_and_cut(simplex, tabmod, init_result, options):
         return tabmod, "optimal", init_result
 
     branches = []
-    heapq.heappush(branches, _Branch(init_result, [(-1, init_variable, float(math.ceil(init_value)))]))
+    heapq.heappush(branches, _Branch(init_result, [(-1, init_variable, _js_ceil(init_value))]))
     heapq.heappush(branches, _Branch(init_result, [(1, init_variable, float(math.floor(init_value)))]))
 
     max_extra_rows = len(integers) * 2
@@ -130,7 +135,7 @@ def branch_and_cut(simplex, tabmod, init_result, options):
                         cuts_upper.append(cut)
                         cuts_lower.append(cut)
                 cuts_lower.append((1, variable, float(math.floor(value))))
-                cuts_upper.append((-1, variable, float(math.ceil(value))))
+                cuts_upper.append((-1, variable, _js_ceil(value)))
                 heapq.heappush(branches, _Branch(result, cuts_upper))
                 heapq.heappush(branches, _Branch(result, cuts_lower))
         timedout = now() >= stop_time
@@ -157,7 +162,7 @@ def branch_and_cut_batched(tabmod, init_result, options, node_batch, stats=None)
         return tabmod, "optimal", init_result
 
     branches = []
-    heapq.heappush(branches, _Branch(init_result, ((-1, init_variable, float(math.ceil(init_value))),)))
+    heapq.heappush(branches, _Branch(init_result, ((-1, init_variable, _js_ceil(init_value)),)))
     heapq.heappush(branches, _Branch(init_result, ((1, init_variable, float(math.floor(init_value))),)))
 
     max_extra_rows = len(integers) * 2
@@ -217,7 +222,7 @@ def branch_and_cut_batched(tabmod, init_result, options, node_batch, stats=None)
                             cuts_upper.append(cut)
                             cuts_lower.append(cut)
                     cuts_lower.append((1, variable, float(math.floor(value))))
-                    cuts_upper.append((-1, variable, float(math.ceil(value))))
+                    cuts_upper.append((-1, variable, _js_ceil(value)))
                     heapq.heappush(branches, _Branch(result, tuple(cuts_upper)))
                     heapq.heappush(branches, _Branch(result, tuple(cuts_lower)))
             timedout = now() >= stop_time
@@ -246,7 +251,7 @@ def branch_and_cut_device(tabmod, root, node, init_result, options, stats=None):
         return tabmod, "optimal", init_result
 
     branches = []
-    heapq.heappush(branches, _Branch(init_result, [(-1, init_variable, float(math.ceil(init_value)))]))
+    heapq.heappush(branches, _Branch(init_result, [(-1, init_variable, _js_ceil(init_value))]))
     heapq.heappush(branches, _Branch(init_result, [(1, init_variable, float(math.floor(init_value)))]))
     optimal_threshold = init_result * (1.0 - sign * tolerance)
     now = lambda: time.time() * 1000.0  # noqa: E731  Date.now()
@@ -279,7 +284,7 @@ def branch_and_cut_device(tabmod, root, node, init_result, options, stats=None):
                         cuts_upper.append(cut)
                         cuts_lower.append(cut)
                 cuts_lower.append((1, variable, float(math.floor(value))))
-                cuts_upper.append((-1, variable, float(math.ceil(value))))
+                cuts_upper.append((-1, variable, _js_ceil(value)))
                 heapq.heappush(branches, _Branch(result, cuts_upper))
                 heapq.heappush(branches, _Branch(result, cuts_lower))
         timedout = now() >= stop_time

@@ -3,9 +3,10 @@
 // yalps_milp_f64 = the reference's solve() flow for a model with integer variables, from the initial tableau to
 // the best integer tableau, in ONE native call: simplex() on the root (src/YALPS.ts:79), then branchAndCut
 // (src/branchAndCut.ts:89-176) with every node LP on the GPU.  The queue is a binary heap with CPython heapq's
-// sift rules (the reference's queue is npm `heap`, package.json:157, described by its authors as a port of heapq; it is not
-// vendored here, so node order is pinned at status / objective level only, DESIGN.md section 2), ordered by the parent's
-// evaluation only (:100), so nodes are popped in the reference's order; results are committed in pop order.
+// sift rules (the reference's queue is npm `heap`, package.json:157, described by its authors as a port of heapq), ordered
+// by the parent's evaluation only (:100), so nodes are popped in the reference's order; results are committed in pop order.
+// Node order is pinned to the reference's branchAndCut by tests/golden/simplex_milp.json.gz (a heapq stand-in for `heap`
+// assumed, DESIGN.md section 2): tests/test_milp_paths.py checks every model's node count, best tableau and result.
 // Node evaluation, by root size:
 //   * root + cuts fit in LDS:        host-side applyCuts (:22-61) + the zero-copy single-workgroup solve
 //                                    (or, node_batch > 1: batches of frontier nodes, one workgroup per node)

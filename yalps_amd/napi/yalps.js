@@ -85,6 +85,10 @@ const roundToPrecision = (num, precision) => {
 
 // src/YALPS.ts:8-50 on column 0 and the permutations of a tableau of `height` rows
 function solution(tm, height, status, result, options) {
+  // An optimal result is roundToPrecision of the best tableau's objective cell (src/simplex.ts:78), whose column 0 the
+  // addon wrote back.  A NaN result (precision 0: inf / inf) loses its sign bit on the way through N-API (V8 makes every
+  // NaN it is handed its canonical one); rounding the cell here again gives the reference's own NaN.
+  if (status === "optimal" && Number.isNaN(result)) result = roundToPrecision(tm.matrix[0], options.precision)
   if (status === "optimal" || (status === "timedout" && !Number.isNaN(result))) {
     const variables = []
     tm.variables.forEach(([key], i) => {
