@@ -869,6 +869,8 @@ def test_every_spilling_launch_per_pivot_instantiation(nat, monkeypatch, M, N, c
         c.close()
     assert info["last_path"] == "streaming" and info["streaming"] == kernel, info
     assert decide is None or info["decide"] == decide, info
+    # (checkCycles: APPLY launches, then the DECIDE launches of the pivot_kernel `decide` names)
+    assert info["launched"] == "+".join(dict.fromkeys([kernel] + ([info["decide"]] if check else []))), info
     assert (status, npiv) == (est, epiv) and G.same_number(result, eres)
     assert np.array_equal(gpos, rpos) and np.array_equal(gvar, rvar)
     assert np.array_equal(got.view(np.int64), ref.view(np.int64))
@@ -970,6 +972,10 @@ SWEEP = [  # M, N, pivots, env, expected kernel, checkCycles
     (4300, 4000, 61, {"YALPS_HIP_DELAY_NT": "1", "YALPS_HIP_DELAY_KERNEL": "2"}, "stream2_kernel<1024,2,nt>", False),
     (900, 7000, 60, {"YALPS_HIP_DELAY_KERNEL": "2"}, "stream2_kernel<512,8>", False),
 ]
+# the checkCycles rows of SWEEP by (M, N, pivots): the form that ran (`inplace=` names the plain one; four rows per workgroup
+# sweep straight from L2, and rows of 16 units per lane have no panel form with the detector)
+SWEEP_CHECK_LAUNCHED = {(900, 7000, 60): "sweep_kernel<512,8,check>", (900, 7000, 61): "stream3_kernel<512,8,check,direct>",
+                        (2100, 12345, 23): "stream3_kernel<512,16,check,direct>"}
 
 
 @pytest.mark.parametrize("M,N,pivots,env,kernel,check", SWEEP)
@@ -999,6 +1005,7 @@ def test_sweep_kernel_matches_restatement(nat, ctx, monkeypatch, M, N, pivots, e
     finally:
         t.close()
     assert info["last_path"] == "inplace" and info["inplace"] == kernel, info
+    assert not check or info["launched"] == SWEEP_CHECK_LAUNCHED[M, N, pivots], info
     assert (status, npiv) == (est, epiv) and G.same_number(result, eres)
     assert np.array_equal(gpos, rpos) and np.array_equal(gvar, rvar)
     assert np.array_equal(got.view(np.int64), ref.view(np.int64))

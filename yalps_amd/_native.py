@@ -305,8 +305,9 @@ class DeviceTableau:
         return STATUS[st], res.value, npiv.value, ms.value
 
     def info(self):
-        buf = C.create_string_buffer(512)
-        check(lib().yalps_tableau_info(self.handle, buf, 512))
+        """yalps_tableau_info as {key: value}; `launched` is every kernel the last solve launched, '+'-separated."""
+        buf = C.create_string_buffer(2048)
+        check(lib().yalps_tableau_info(self.handle, buf, 2048))
         return dict(kv.split("=", 1) for kv in buf.value.decode().split(" ") if "=" in kv)
 
     def debug_stamps(self, reset=True):

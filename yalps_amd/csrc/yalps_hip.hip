@@ -38,6 +38,7 @@
 #include <chrono>
 #include <climits>
 #include <cmath>
+#include <cstdarg>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -395,9 +396,51 @@ struct yalps_tableau {
     size_t cut_pin_bytes = 0;
     bool node_occupancy_ok = false;
     int64_t node_fused_runs = 0;
+    // every kernel the last solve (or sharded run since yalps_shard_begin) launched, once each in the order of its first
+    // launch, spelt as tests/_census.py spells the compiled symbols (yalps_tableau_info's `launched=`)
+    std::vector<std::string> launched;
+    std::string shard_step_name; // the in-place step kernel of a row shard (set_shard): dshard_kernel or wide_kernel<.., inplace>
 };
 
 namespace {
+
+// ---- the record behind `launched=`: one name per compiled symbol, template arguments in template order, bool switches
+// spelt as the flags that select them (,nt ,check ,panel|,direct ,lds ,tag ,inplace) --------------------------------
+void note_launch(yalps_tableau *t, const std::string &name) {
+    for (const std::string &k : t->launched)
+        if (k == name) return;
+    t->launched.push_back(name);
+}
+
+std::string kname(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
+std::string kname(const char *fmt, ...) {
+    char buf[96];
+    va_list ap;
+    va_start(ap, fmt);
+    std::vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    return buf;
+}
+
+// the kernel of a persistent launch: pv is one of rvar / rvar_tag / svar / svar_check / svar2 / svar2_check
+std::string persistent_name(const yalps_tableau *t, const RVariant &pv, bool in_place, bool delayed, bool check) {
+    if (!in_place) {
+        if (t->rvar_tag.fn && pv.fn == t->rvar_tag.fn) return kname("resident_kernel<%d,%d,%d,tag>", pv.T, pv.J, pv.R);
+        if (t->d.extra) return kname("resident_kernel<%d,%d,%d,lds>", pv.T, pv.J, pv.R);
+        return kname("resident%s_kernel<%d,%d,%d>", t->rgen == 2 ? "2" : "", pv.T, pv.J, pv.R);
+    }
+    if (delayed && t->stream3)
+        return kname("stream3_kernel<%d,%d%s%s,%s>", pv.T, pv.J, (pv.R & 1) ? ",nt" : "", check ? ",check" : "", (pv.R & 2) ? "panel" : "direct");
+    if (delayed) return kname("stream2_kernel<%d,%d%s>", pv.T, pv.J, pv.R ? ",nt" : "");
+    if (t->sweep) return kname("sweep_kernel<%d,%d%s%s>", pv.T, pv.J, check ? ",check" : "", pv.R ? ",nt" : "");
+    return kname("stream_kernel<%d,%d%s>", pv.T, pv.J, check ? ",check" : "");
+}
+
+// the kernel of launch_one's launches in `mode`
+std::string launch_one_name(const yalps_tableau *t, int mode) {
+    if (t->wfn && mode != MODE_DECIDE) return kname("wide_kernel<%d,%d>", t->var.T, t->var.J);
+    return kname("pivot_kernel<%d,%d,%d>", t->var.T, t->var.J, t->var.R);
+}
 
 void launch_one(yalps_tableau *t, int parity, int mode, int force, const double *gather = nullptr) {
     const int grid = mode == MODE_DECIDE ? 1 : t->nb;
@@ -410,6 +453,8 @@ void launch_one(yalps_tableau *t, int parity, int mode, int force, const double 
 // the elimination step of a row shard (MODE_SHARD): in place where the shard has the kernel for it
 void launch_shard(yalps_tableau *t, const double *gathered) {
     const int force = t->ctx->nt_stores ? 64 : 0;
+    if (t->shard_check) note_launch(t, "shard_cycle_kernel");
+    note_launch(t, (t->dfn || t->wfn_inplace) ? t->shard_step_name : launch_one_name(t, MODE_SHARD));
     if (t->shard_check) // checkCycles: the detector's verdict on the pivot this step is about to decide (shard_kernels.cuh)
         shard_cycle_kernel<<<dim3(1), dim3(1024), 0, t->ctx->stream>>>(t->d, t->shard_parity, gathered, (t->dfn || t->wfn_inplace) ? 1 : 0);
     if (t->dfn)
@@ -981,6 +1026,8 @@ int32_t yalps_tableau_info(const yalps_tableau *t, char *buf, int32_t len) {
                       t->stream3 ? ((t->svar2.R & 2) ? " sweep=panels" : " sweep=direct") : "");
     else if (t->svar.fn)
         std::snprintf(inp, sizeof inp, "%s_kernel<%d,%d%s>", t->sweep ? "sweep" : "stream", t->svar.T, t->svar.J, t->sweep && t->d.sw_nt ? ",nt" : "");
+    std::string launched;
+    for (const std::string &k : t->launched) launched += (launched.empty() ? "" : "+") + k;
     char str[64];
     if (t->dfn)
         std::snprintf(str, sizeof str, "dshard_kernel<512,%d%s%s>,delay_depth:%d", t->dJ, t->dnt ? ",nt" : "", t->dpanel ? ",panel" : "", t->d.delay_depth);
@@ -989,7 +1036,7 @@ int32_t yalps_tableau_info(const yalps_tableau *t, char *buf, int32_t len) {
     else
         std::snprintf(str, sizeof str, "pivot_kernel<%d,%d,%d>", t->var.T, t->var.J, t->var.R);
     std::snprintf(buf, (size_t)len, "streaming=%s workgroups=%d resident=%s inplace=%s giveups=%lld resident_off_for=%d inplace_off_for=%d "
-                  "last_path=%s last_resident_launches=%lld node_fused_runs=%lld lock_giveups=%lld decide=pivot_kernel<%d,%d,%d> shard_sweep=%s", str,
+                  "last_path=%s last_resident_launches=%lld node_fused_runs=%lld lock_giveups=%lld decide=pivot_kernel<%d,%d,%d> shard_sweep=%s launched=%s", str,
                   t->nb, res, inp, (long long)t->giveups, t->ctx->resident ? t->ctx->resident_skip : -1,
                   t->ctx->inplace ? t->ctx->inplace_skip : -1,
                   t->last_path == 1 ? "resident" : t->last_path == 2 ? "streaming" : t->last_path == 3 ? "resident+streaming"
@@ -997,7 +1044,8 @@ int32_t yalps_tableau_info(const yalps_tableau *t, char *buf, int32_t len) {
                   : t->last_path == 9 ? "resident+inplace" : t->last_path == 11 ? "resident+inplace+streaming"
                   : t->last_path == 16 ? "generic" : "none",
                   (long long)(t->last_path & 9 ? t->last_launches : 0), (long long)t->node_fused_runs, (long long)t->ctx->lock_giveups,
-                  t->var.T, t->var.J, t->var.R, !t->dfn ? "none" : t->d.ext_sweep ? "launch" : "inline"); // (decide: the single-workgroup DECIDE launches of checkCycles on the launch-per-pivot path)
+                  t->var.T, t->var.J, t->var.R, !t->dfn ? "none" : t->d.ext_sweep ? "launch" : "inline",
+                  launched.empty() ? "none" : launched.c_str()); // (decide: the single-workgroup DECIDE launches of checkCycles on the launch-per-pivot path)
     return 0;
 }
 
@@ -1328,6 +1376,8 @@ static int32_t solve_generic(yalps_tableau *t, double precision, double maxPivot
     if (gpu_ms_out) HIP_TRY(hipEventRecord(c->ev0, s));
     t->last_path = 16;
     t->last_launches = 0;
+    note_launch(t, "generic_decide_kernel");
+    note_launch(t, "generic_apply_kernel");
     int64_t hist_have = 0;
     YState fin;
     for (;;) {
@@ -1364,15 +1414,17 @@ static int32_t solve_generic(yalps_tableau *t, double precision, double maxPivot
     return fin.status;
 }
 
+// 16-byte units to sweep per pivot; 1024 lanes from 1024 units on (36x101: 3.8 -> 3.3 us/pivot, 101x61: 5.1 -> 4.0;
+// 64 lanes were slower even at 33x33)
+static int small_big(const SmallDesc &sd) { return (size_t)sd.h * (size_t)(small_pcols(sd.n) / 2) >= 1024 ? 1 : 0; }
+
 // One launch of small_kernel on the context's stream and the wait for it; the kernel leaves status /
 // result / pivot count in pinned host memory.
 static int32_t run_small(yalps_ctx *c, SmallDesc sd, int32_t checkCycles, double *result_out, int64_t *pivots_out,
                          float *gpu_ms_out) {
     hipStream_t s = c->stream;
     const size_t shmem = small_lds_bytes(sd.w, sd.h);
-    // 16-byte units to sweep per pivot; 1024 lanes from 1024 units on (36x101: 3.8 -> 3.3 us/pivot, 101x61: 5.1 -> 4.0;
-    // 64 lanes were slower even at 33x33)
-    const int big = (size_t)sd.h * (size_t)(small_pcols(sd.n) / 2) >= 1024 ? 1 : 0;
+    const int big = small_big(sd);
     const int which = 2 * (checkCycles ? 1 : 0) + big;
     using Fn = void (*)(SmallDesc);
     static const Fn fns[4] = {small_kernel<256, false>, small_kernel<1024, false>, small_kernel<256, true>,
@@ -1423,6 +1475,7 @@ int32_t yalps_tableau_solve(yalps_tableau *t, double precision, double maxPivots
     yalps_ctx *c = t->ctx;
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t s = c->stream;
+    t->launched.clear();
     // (0) the tableau fits in the LDS of one CU: one workgroup, one launch, in place
     if (t->d.nshards == 1 && fits_small(c, t->d.w, t->height)) {
         SmallDesc sd{};
@@ -1439,6 +1492,7 @@ int32_t yalps_tableau_solve(yalps_tableau *t, double precision, double maxPivots
         sd.max_pivots = maxPivots;
         t->last_path = 4;
         t->last_launches = 1;
+        note_launch(t, kname("small_kernel<%d%s>", small_big(sd) ? 1024 : 256, checkCycles ? ",check" : ""));
         return run_small(c, sd, checkCycles, result_out, pivots_out, gpu_ms_out);
     }
     // (a path switched off by a give-up comes back after PERSISTENT_RETRY_AFTER solves)
@@ -1550,6 +1604,7 @@ int32_t yalps_tableau_solve(yalps_tableau *t, double precision, double maxPivots
                 lock_expired = !one_grid_of_all_processes.held;
                 if (!lock_expired) { // (else nothing of this launch is enqueued but the copies aside)
                 pv.fn<<<dim3(t->nb), dim3(pv.T), shmem, s>>>(t->d, parity, chunk);
+                note_launch(t, persistent_name(t, pv, in_place, delayed, checkCycles != 0));
                 t->last_path |= in_place ? 8 : 1;
                 t->last_launches++;
                 c->persistent_launches++;
@@ -1640,6 +1695,8 @@ int32_t yalps_tableau_solve(yalps_tableau *t, double precision, double maxPivots
         rc = ensure_graph(t, which);
         if (rc) return rc;
         t->last_path |= 2;
+        note_launch(t, launch_one_name(t, which == 0 ? MODE_FUSED : MODE_APPLY)); // (launch_batch: APPLY, DECIDE, APPLY, ...)
+        if (which == 1) note_launch(t, launch_one_name(t, MODE_DECIDE));
     }
     // keep one batch in flight while the previous batch's state is inspected
     int issued = 0, checked = 0;
@@ -1773,6 +1830,8 @@ static int32_t node_fused_solve(yalps_tableau *dst, const yalps_tableau *root, i
         dst->node_occupancy_ok = true;
     }
     const int prep_blocks = std::max<int>(ncuts, (int)std::min<int64_t>(1024, ((int64_t)root->d.pitch * h0 / 2 + 255) / 256));
+    dst->launched.clear();
+    note_launch(dst, "node_prepare_kernel");
     node_prepare_kernel<<<dim3(prep_blocks), dim3(256), 0, s>>>(dst->d, root->d.mat[root->cur], root->d.rhs[root->cur], root->d.pos, root->d.var, h0,
                                                                ncuts, stage, (int)STATE_BYTES, static_cast<unsigned long long *>(dst->rc_sync),
                                                                (long long)(dst->rc_sync_bytes / 8));
@@ -1790,6 +1849,8 @@ static int32_t node_fused_solve(yalps_tableau *dst, const yalps_tableau *root, i
             return 0;
         }
         pv.fn<<<dim3(dst->nb), dim3(pv.T), shmem, s>>>(dst->d, 0, c->resident_chunk);
+        note_launch(dst, persistent_name(dst, pv, false, false, checkCycles != 0));
+        note_launch(dst, "node_finish_kernel");
         HIP_TRY(hipGetLastError());
         node_finish_kernel<<<dim3(8), dim3(256), 0, s>>>(dst->d, h, dst->perm_len, dst->perm_cap, (int)(16 + 2 * sizeof(YState)), dst->host_ctl,
                                                          static_cast<char *>(dst->pin_out));
@@ -1937,6 +1998,7 @@ int32_t yalps_tableau_set_shard(yalps_tableau *t, int32_t rank, int32_t nranks, 
             if (v.T == t->var.T && v.J == t->var.J) {
                 t->wfn_inplace = v.fn[nt ? 1 : 0];
                 t->wT_inplace = v.launchT;
+                t->shard_step_name = kname("wide_kernel<%d,%d,inplace%s>", v.launchT, v.T * v.J / v.launchT, nt ? ",nt" : "");
             }
         if (t->wfn_inplace) {
             if (t->wshmem > 48 * 1024)
@@ -1988,6 +2050,7 @@ int32_t yalps_tableau_set_shard(yalps_tableau *t, int32_t rank, int32_t nranks, 
                 t->dJ = dJ;
                 t->dnt = nt ? 1 : 0;
                 t->dpanel = panel ? 1 : 0;
+                t->shard_step_name = kname("dshard_kernel<512,%d%s%s>", dJ, nt ? ",nt" : "", panel ? ",panel" : "");
                 d.delay_depth = depth;
                 // the sweep as a launch of its own, rows mapped to workgroups by (panel, row block): one fill per workgroup, no barrier
                 // between its waves afterwards -- whatever the rows per workgroup of the step kernel (YALPS_HIP_SHARD_XSWEEP=0: the step kernel sweeps)
@@ -2060,6 +2123,8 @@ int32_t yalps_shard_begin(yalps_tableau *t, double precision, double maxPivots, 
         if (int rc0 = grow_history(t, SHARD_HIST_MARGIN, 0)) return rc0;
     int rc = init_state(t, precision, maxPivots, checkCycles);
     if (rc) return rc;
+    t->launched.clear();
+    note_launch(t, launch_one_name(t, MODE_FUSED));
     launch_one(t, 0, MODE_FUSED, 0); // bootstrap scan: emits this rank's first partials
     HIP_TRY(hipGetLastError());
     t->shard_parity = 1;
@@ -2081,11 +2146,13 @@ static void launch_select(yalps_tableau *t, double *send) {
     using SelectFn = void (*)(Desc, int, double *);
     if (t->dfn) {
         const int lanes = t->nb <= 256 ? 256 : 1024; // (dshard_select_kernel<256>: four times the workgroups)
+        note_launch(t, kname("dshard_select_kernel<%d>", lanes));
         const int blocks = std::min(256, std::max(1, (t->d.pitch + lanes - 1) / lanes));
         reinterpret_cast<SelectFn>(const_cast<void *>(yalps_dshard_select_fn(lanes)))<<<dim3(blocks), dim3(lanes), 0, t->ctx->stream>>>(t->d, t->shard_parity, send);
-    }
-    else
+    } else {
+        note_launch(t, "shard_select_kernel");
         shard_select_kernel<<<dim3(shard_select_blocks(t)), dim3(1024), 0, t->ctx->stream>>>(t->d, t->shard_parity, send);
+    }
 }
 
 int32_t yalps_shard_select(yalps_tableau *t, double *send_dev) {
@@ -2284,6 +2351,7 @@ static int shard_step(yalps_tableau *t, yalps_comm *c, size_t slot) {
     launch_shard(t, c->recv);
     if (t->d.ext_sweep && ++t->shard_pend == t->d.delay_depth) { // `depth` pivots pending behind this step: the sweep, a launch of its own
         using SweepFn = void (*)(Desc, int);
+        note_launch(t, t->dnt ? "dshard_sweep_kernel<nt>" : "dshard_sweep_kernel");
         reinterpret_cast<SweepFn>(const_cast<void *>(t->xsweep_fn))<<<dim3(t->xsweep_grid), dim3(512), t->xsweep_lds, t->ctx->stream>>>(t->d, t->shard_parity);
         t->shard_pend = 0;
     }
