@@ -109,20 +109,14 @@ const WInplace kWideInplace[] = {
 };
 
 using ResidentFn = void (*)(Desc, int, int);
-struct RVariant {
-    int T, J, R;
-    ResidentFn fn;
-};
 // The persistent kernels' instantiations live in translation units of their own (persistent_*.hip, compiled side by
 // side; persistent_tables.h).  A tableau takes the feasible resident variant (T * J 16-byte units span a row, R rows
 // per workgroup) with the fewest row registers J * R -- few, fat lanes: the loop is latency-bound, and <= 8 waves per
 // CU leave each lane 256 VGPRs; J = 3 / 5 keep 1025..1536 / 2049..2560 units out of the next power of two.
+using RVariant = PersistentEntry; // (fn: launched as a ResidentFn, or as a KernelFn for kDshard)
 std::vector<RVariant> variants_of(std::initializer_list<PersistentTable> tables) {
     std::vector<RVariant> out;
-    for (const PersistentTable &t : tables)
-        for (int i = 0; i < t.count; i++)
-            out.push_back({t.entries[i].T, t.entries[i].J, t.entries[i].R,
-                           reinterpret_cast<ResidentFn>(const_cast<void *>(t.entries[i].fn))});
+    for (const PersistentTable &t : tables) out.insert(out.end(), t.entries, t.entries + t.count);
     return out;
 }
 const std::vector<RVariant> kResident = variants_of({yalps_resident_table_a(), yalps_resident_table_b()});
@@ -273,6 +267,331 @@ int env_int(const char *name, int dflt) {
     return (e && *e) ? std::atoi(e) : dflt;
 }
 
+std::string kname(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
+std::string kname(const char *fmt, ...) {
+    char buf[96];
+    va_list ap;
+    va_start(ap, fmt);
+    std::vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    return buf;
+}
+
+// ---- the plan: which kernels a tableau gets ----------------------------------------------------------
+// One launchable kernel, filled completely where it is chosen; fn == nullptr: the tableau has no such kernel.  The name is
+// the record behind `launched=`: one per compiled symbol, template arguments in template order, bool switches spelt as the
+// flags that select them (,nt ,check ,panel|,direct ,lds ,tag ,inplace), as tests/_census.py spells the compiled symbols.
+struct Kernel {
+    const void *fn = nullptr;
+    int lanes = 0;        // per workgroup
+    size_t lds = 0;       // dynamic LDS bytes (the resident kernel without LDS rows: 0 -- both permutations, resident_lds())
+    std::string name;
+    bool big_lds = false; // the attribute for more than 48 KB of dynamic LDS has been raised for fn (need_lds)
+    std::string info, info_tail; // stream3_kernel: what yalps_tableau_info's `inplace=` prints around the depth in use, where that is not the name
+    template <class Fn> Fn as() const { return reinterpret_cast<Fn>(const_cast<void *>(fn)); }
+};
+
+// Everything the dispatcher reads.  Filled by the plan_* functions below (create) and plan_shard (set_shard); after that
+// nobody looks at a table entry's R again.
+struct Plan {
+    int T = 0, J = 0;  // lanes x units per lane of the launch-per-pivot tables that span the row
+    Kernel decide;     // pivot_kernel: the single-workgroup DECIDE launches of checkCycles, and every launch where ...
+    Kernel step;       // ... no wide_kernel stands in for it (FUSED / APPLY / SHARD launches)
+    bool wide = false; // ... one does: `step` is a wide_kernel
+    Kernel resident;   // resident_kernel / resident2_kernel; the tagged form where it exists
+    bool tagged = false;
+    int extra = 0, xl_ofs = 0;    // resident kernel with LDS rows: rows per workgroup parked there, their offset (Desc)
+    Kernel inplace[2];            // stream_kernel / sweep_kernel, one sweep per pivot: [checkCycles]
+    bool sweep = false;           // ... they are sweep_kernel forms
+    int sw_nt = 0;                // ... with non-temporal row traffic (Desc)
+    Kernel delayed[2];            // stream3_kernel / stream2_kernel, delayed row updates: [checkCycles] (stream3_kernel only)
+    bool stream3 = false;         // ... they are stream3_kernel forms
+    bool ob_park = false;         // ... of 6+ units per lane: the objective replicas are parked in HBM during a sweep
+    int delay_depth = 0;          // ... their pending pivots (Desc)
+    Kernel shard_step;            // row shard (set_shard): dshard_kernel or wide_kernel<.., inplace>, else `step` does it
+    bool shard_delayed = false;   // ... it is a dshard_kernel
+    Kernel shard_sweep;           // dshard_sweep_kernel: the shard's sweep as a launch of its own (dsweep_kernel.cuh)
+    int shard_sweep_grid = 0;     // ... its workgroups (panels x row blocks)
+};
+
+// The shape as the selection sees it.  The plan_* functions take it with the context's CUs / workgroups and read the
+// YALPS_HIP_* switches; they make no HIP call.
+struct Shape {
+    int width, hcap;
+    int n, units;       // columns beside column 0; 16-byte units of a row
+    int pitch;          // doubles of a stored row (128-byte rows)
+    bool too_wide;      // rows wider than 16385 columns: the any-shape pair of generic_kernels.cuh (run-time loops only)
+    int T, J;           // launch-per-pivot / stream_kernel tables: lanes x units per lane that span the row
+    int nb, rows_per_block;
+    size_t tab_bytes;
+};
+
+Shape shape_of(int width, int hcap, int max_blocks) {
+    const int n = width - 1, units = (n + 1) / 2, pitch = std::max(16, (n + 15) / 16 * 16);
+    // kernel variant: lanes x units-per-lane must span the row; rows in flight sized so that
+    // one workgroup per CU covers the tableau in one batch when it can
+    const int T = units <= 512 ? 256 : 1024;
+    int J = 1;
+    while (T * J < units) J *= 2;
+    const bool too_wide = J > 8; // (the tables end at <1024,8>)
+    // spread the rows over all workgroups
+    const int nb = std::min(hcap, max_blocks);
+    return {width, hcap, n, units, pitch, too_wide, T, too_wide ? 8 : J, nb, (hcap + nb - 1) / nb, sizeof(double) * (size_t)pitch * hcap};
+}
+
+// launch per pivot: pivot_kernel, and wide_kernel where that is too wide / tall for register batches
+void plan_launch_per_pivot(const Shape &s, Plan &p) {
+    const int forceR = env_int("YALPS_HIP_ROWS", 0);
+    // rows in flight per lane R >= rows per workgroup if any
+    // variant allows it (one batch per launch), else the largest R (several batches)
+    const Variant *pick = nullptr;
+    for (const Variant &v : kVariants) {
+        if (v.T != s.T || v.J != s.J) continue;
+        pick = &v; // candidates are listed by increasing R
+        if (v.R >= (forceR ? forceR : s.rows_per_block)) break;
+    }
+    p.T = s.T;
+    p.J = s.J;
+    p.decide = Kernel{reinterpret_cast<const void *>(pick->fn), s.T, 0, kname("pivot_kernel<%d,%d,%d>", s.T, s.J, pick->R)};
+    p.step = p.decide;
+    // (pivot_kernel's <1024,2,*> variants spill at the 128-VGPR cap: 47 us/pivot on a 1477x2388 tableau
+    // against 27 us for wide_kernel)
+    p.wide = s.J >= 4 || (s.T == 1024 && s.J >= 2) || s.rows_per_block > pick->R || env_int("YALPS_HIP_WIDE", 0);
+    const size_t lds = sizeof(double) * ((size_t)s.pitch + 4 * (size_t)s.rows_per_block); // (+ 2 per row: in-place shards)
+    for (const WVariant &v : kWide) // (one for every T, J of kVariants)
+        if (p.wide && v.T == s.T && v.J == s.J) p.step = Kernel{reinterpret_cast<const void *>(v.fn), s.T, lds, kname("wide_kernel<%d,%d>", s.T, s.J)};
+}
+
+// resident (on-chip) solver: needs every workgroup co-resident (one per CU) and the rows of a
+// workgroup in registers
+void plan_resident(const Shape &s, Plan &p) {
+    // (16 waves per CU were tried for 2049^2: <1024,1,9> spills at the 128-VGPR cap and its barriers
+    // cost more: 92 K pivots/s against 144 K for <512,2,9>)
+    int best = INT_MAX, fT = 0, fJ = 0, fR = 0;
+    if (const char *force = std::getenv("YALPS_HIP_RVARIANT")) std::sscanf(force, "%d,%d,%d", &fT, &fJ, &fR);
+    RVariant pick{0, 0, 0, nullptr};
+    const char *gen = "", *mark = "";
+    size_t lds = 0;
+    for (const RVariant &v : kResident) {
+        if (v.T * v.J < s.units || v.R < s.rows_per_block) continue;
+        if (fT && (v.T != fT || v.J != fJ || v.R != fR)) continue; // experiments: YALPS_HIP_RVARIANT=T,J,R
+        const int regs = v.J * v.R * 1024 + v.T; // fewest row registers, then fewest waves
+        if (regs < best) {
+            best = regs;
+            pick = v;
+        }
+    }
+    if (pick.fn && env_int("YALPS_HIP_RESIDENT_GEN", 2) >= 2)
+        for (const RVariant &v : kResident2)
+            if (v.T == pick.T && v.J == pick.J && v.R == pick.R) {
+                pick = v;
+                gen = "2";
+            }
+    if (!pick.fn && env_int("YALPS_HIP_LDS_ROWS", 1)) { // a little too tall: park the rows that are missing in LDS
+        const int xl_ofs = (2 * (s.width + s.hcap) + 3) / 4 * 4;
+        int best_extra = INT_MAX;
+        for (const RVariant &v : kResidentLds) {
+            const int extra = s.rows_per_block - v.R;
+            if (v.T * v.J < s.units || extra < 1 || extra > XROWS) continue;
+            if (fT && (v.T != fT || v.J != fJ || v.R != fR)) continue;
+            const size_t bytes = sizeof(int32_t) * (size_t)xl_ofs + sizeof(double) * (size_t)extra * s.pitch;
+            if (bytes > LDS_DYNAMIC_MAX || extra >= best_extra) continue;
+            best_extra = extra;
+            pick = v;
+            lds = bytes;
+            mark = ",lds";
+            p.extra = extra;
+            p.xl_ofs = xl_ofs;
+        }
+    }
+    // narrow rows: the tagged form of the same variant, if built (YALPS_HIP_TAG=0 switches it off)
+    if (pick.fn && !p.extra && env_int("YALPS_HIP_TAG", 1))
+        for (const RVariant &v : kResidentTag)
+            if (v.T == pick.T && v.J == pick.J && v.R == pick.R) {
+                pick = v;
+                gen = "";
+                mark = ",tag";
+                p.tagged = true;
+            }
+    if (pick.fn)
+        p.resident = Kernel{pick.fn, pick.T, lds, kname("resident%s_kernel<%d,%d,%d%s>", gen, pick.T, pick.J, pick.R, mark)};
+}
+
+// persistent in-place kernel for what does not fit on chip: lanes x units span the row, the normalised
+// pivot row + my rows' scalars fit in LDS
+void plan_inplace(const Shape &s, Plan &p) {
+    const size_t rows = (size_t)s.rows_per_block;
+    const size_t stream_lds = sizeof(double) * ((size_t)s.pitch + 3 * rows) + sizeof(int32_t) * rows;
+    if (stream_lds <= 150 * 1024) {
+        for (int check = 0; check < 2; check++)
+            for (const RVariant &v : check ? kStreamCheck : kStream)
+                if (v.T == s.T && v.J == s.J) p.inplace[check] = Kernel{v.fn, v.T, stream_lds, kname("stream_kernel<%d,%d%s>", v.T, v.J, check ? ",check" : "")};
+    }
+    // what streams from HBM anyway goes to sweep_kernel: rows of 8194 .. 16385 columns (no stream_kernel spans them), and
+    // 4098 .. 8193-column tableaux too big for the Infinity Cache (measured at 8193 x 8193: stream_kernel 5.1 TB/s)
+    const int sweep_mode = env_int("YALPS_HIP_SWEEP", 1); // 0: never, 1: by size, 2: wherever a variant exists
+    if (sweep_mode && (s.J == 8 || (s.J == 4 && (s.tab_bytes > SWEEP_BEYOND_CACHE || sweep_mode == 2)))) {
+        const size_t lds = sizeof(double) * 2 * 512 * (size_t)(2 * s.J) + (4 * sizeof(double) + sizeof(int32_t)) * rows + 64;
+        if (lds <= 150 * 1024) {
+            int want_nt = s.tab_bytes > SWEEP_BEYOND_CACHE ? 1 : 0;
+            if (const char *e = std::getenv("YALPS_HIP_SWEEP_NT")) want_nt = std::atoi(e) != 0;
+            const int sT = 512, sJ = 2 * s.J; // (sweep_kernel runs 512 lanes x 8 / 16 units: persistent_sweep.hip; R = non-temporal)
+            for (const RVariant &v : kSweep)
+                if (v.T == sT && v.J == sJ && v.R == want_nt) {
+                    p.inplace[0] = Kernel{v.fn, sT, lds, kname("sweep_kernel<%d,%d%s>", sT, sJ, want_nt ? ",nt" : "")};
+                    p.sweep = true;
+                }
+            if (p.sweep) {
+                p.inplace[1] = Kernel();
+                for (const RVariant &v : kSweepCheck)
+                    if (v.T == sT && v.J == sJ && v.R == want_nt)
+                        p.inplace[1] = Kernel{v.fn, sT, lds, kname("sweep_kernel<%d,%d,check%s>", sT, sJ, want_nt ? ",nt" : "")};
+                p.sw_nt = want_nt;
+            }
+        }
+    }
+}
+
+// The delayed-update arithmetic of stream3_kernel and dshard_kernel (512 lanes; the pending pivots' scalars of my rows
+// in LDS, and one panel of the pending rows where the sweep goes through LDS panels -- panel_flush.cuh).
+int delayed_units_per_lane(int units) { // 16-byte units per lane that span a row of `units` (0: no form does)
+    for (int cand : {1, 2, 4, 6, 8, 16})
+        if (512 * cand >= units) return cand;
+    return 0;
+}
+// The depth: YALPS_HIP_DELAY_DEPTH or depth_default, within 2 .. max_depth, shrunk until its LDS (*lds) fits `lds_cap`; 0: not even then
+// (panel_units = 0: the sweep reads the pending rows straight from L2)
+int delayed_fit(int depth_default, int max_depth, int rows_per_block, size_t panel_units, size_t lds_cap, size_t *lds) {
+    auto lds_of = [&](int dep) {
+        return sizeof(double) * (2 * (size_t)dep + 2) * (size_t)rows_per_block + 3 * sizeof(int32_t) * (((size_t)rows_per_block + 3) / 4 * 4) +
+               sizeof(double) * (size_t)dep * 2 * panel_units;
+    };
+    int depth = std::min(max_depth, std::max(2, env_int("YALPS_HIP_DELAY_DEPTH", depth_default)));
+    while (depth > 2 && lds_of(depth) > lds_cap) depth--;
+    *lds = lds_of(depth);
+    return *lds <= lds_cap ? depth : 0;
+}
+
+// Delayed row updates: where an in-place kernel applies (and no checkCycles), several pivots per sweep.
+//   stream3_kernel<512, J> (objective replica in LDS, the pending pivot rows in a global scratch shared by all workgroups,
+//   up to 8 of them): rows of up to 16385 columns with at least 4 rows per workgroup;
+//   stream2_kernel (pending rows in LDS, up to 4): fewer rows per workgroup, and where YALPS_HIP_DELAY_KERNEL=2 asks for it.
+// Measured against each other on one box, us per pivot, stream3 / stream2: 4097^2 20.2 / 26.2, 6001^2 33.6 / 50.0,
+// 8193 x 4097 30.0 / 42.8, 8193^2 48.3 / 105, 12001 x 1501 21.8 / 26.4, 11001 x 901 17.2 / 24.0, 16385^2 159 / --;
+// 1025 x 16385: stream3 34.3, sweep_kernel 50.3.
+void plan_delayed(const Shape &s, Plan &p) {
+    if (!p.inplace[0].fn || !env_int("YALPS_HIP_DELAY", 1)) return;
+    const int rows_per_block = s.rows_per_block;
+    int want_nt = s.tab_bytes > SWEEP_BEYOND_CACHE ? 1 : 0;
+    if (const char *e = std::getenv("YALPS_HIP_DELAY_NT")) want_nt = std::atoi(e) != 0;
+    const int sJ = delayed_units_per_lane(s.pitch / 2);
+    if (env_int("YALPS_HIP_DELAY_KERNEL", 3) == 3 && sJ && s.nb <= 256 && rows_per_block >= env_int("YALPS_HIP_DELAY_MIN_ROWS", 4)) { // (256: its table of the workgroups' XCDs)
+        // depth: a pivot's head grows with the pivots pending (the candidate row gets them all applied before it is
+        // published), the sweep shrinks: measured best 8 at 65 and 33 rows per workgroup, 6-8 at 17, 4 at 5-9
+        // (with the two-step exchange of the 8- and 16-unit forms only the winner's row gets them applied: 2049 x 16385 at
+        // depth 4 / 6 / 8: 48.1 / 46.2 / 44.8 us per pivot, 4097 x 8193 40.6 / 36.7 / 35.1, 4097 x 16385 73.8 / 64.5 / 60.5,
+        // 1025 x 16385 31.6 / 31.4 / 32.3)
+        // (round 3: the sweep stages the pending rows in LDS one 1024-column panel at a time -- panel_flush.cuh -- and the objective
+        // replica moved to registers: up to STREAM3_MAXD = 16 pending pivots, the deepest form whose scalars + panel fit in LDS)
+        // The panels pay from STREAM3_PANEL_MIN_ROWS rows per workgroup on (YALPS_HIP_STREAM3_PANEL=0|1 forces); below, the sweep reads
+        // the pending rows straight from the XCD's scratch and the depths are round 2's (shape sweep, us per pivot with panels
+        // / straight from L2, same build: 4 rows per workgroup -- 1025 x 8001 23.6 / 19.1, 1025 x 16385 38.3 / 28.5; 8 rows -- 2049 x 16385
+        // 40.2 / 38.1; 17 rows -- 4097 x 16385 48.9 / 54.9, 4097^2 19.7 / 20.4; 20 rows -- 5001^2 24.8 / 28.2; beyond: panels only,
+        // 6001^2 28.1, 8193^2 37.5, 16385^2 87.8 -- round 2: 33.4, 45.5, 141).
+        const bool panel = env_int("YALPS_HIP_STREAM3_PANEL", rows_per_block >= STREAM3_PANEL_MIN_ROWS ? 1 : 0) != 0;
+        const int depth_default = panel ? (sJ == 16 ? STREAM3_DEPTH_J16 : STREAM3_DEFAULT_DEPTH_WIDE)
+                                        : sJ >= 8 ? (rows_per_block >= 8 ? 12 : 6) : std::min(8, std::max(4, (rows_per_block + 1) / 3)); // (2049 x 16385 from L2 at depth 8 / 12 / 16: 35.8 / 34.8 / 34.9 us per pivot)
+        const size_t lds_cap = panel ? LDS_DYNAMIC_MAX : 150 * 1024; // (the panels take what the CU has: 160 KB less the kernel's static arrays)
+        size_t lds = 0;
+        const int depth = delayed_fit(depth_default, STREAM3_MAXD, rows_per_block, panel ? (size_t)stream3_panel_units(sJ) : 0, lds_cap, &lds);
+        if (depth) {
+            // the tables' R of stream3_kernel: non-temporal | panel << 1
+            for (int check = 0; check < 2 && (!check || p.delayed[0].fn); check++) {
+                // (checkCycles with rows of 16 units per lane: the form that sweeps straight from L2 -- with the panels it does not fit the registers; same LDS layout, the panel area unused)
+                const bool kpanel = panel && !(check && sJ == 16);
+                for (const RVariant &v : check ? kStream3Check : kStream3)
+                    if (v.T == 512 && v.J == sJ && v.R == (want_nt | (kpanel ? 2 : 0)))
+                        p.delayed[check] = Kernel{v.fn, 512, lds, kname("stream3_kernel<512,%d%s%s,%s>", sJ, want_nt ? ",nt" : "", check ? ",check" : "", kpanel ? "panel" : "direct")};
+            }
+        }
+        if (p.delayed[0].fn) {
+            p.delayed[0].info = kname("stream3_kernel<512,%d%s>", sJ, want_nt ? ",nt" : "");
+            p.delayed[0].info_tail = panel ? " sweep=panels" : " sweep=direct";
+            p.delay_depth = depth;
+            p.ob_park = sJ >= 6; // (rows of 6+ units per lane: the objective replicas during a sweep)
+            p.stream3 = true;
+        }
+    }
+    // (with two or three rows per workgroup there is nothing to save: 257 x 8193 16.6 us delayed against 14.5)
+    if (!p.delayed[0].fn && s.T * s.J <= 4096 && rows_per_block >= env_int("YALPS_HIP_DELAY_MIN_ROWS", 4)) { // stream2_kernel: as many pending pivots as LDS holds pivot rows (+ two scalars per row of mine) for, at most 4
+        const size_t per_pivot = sizeof(double) * ((size_t)s.pitch + 2 * (size_t)rows_per_block);
+        const size_t fixed = sizeof(double) * 2 * (size_t)rows_per_block + sizeof(int32_t) * (size_t)rows_per_block;
+        int depth = (int)std::min<size_t>(4, (150 * 1024 - fixed) / per_pivot);
+        depth = std::min(depth, std::max(1, env_int("YALPS_HIP_DELAY_DEPTH", 4)));
+        if (depth >= 2) {
+            for (int nt = want_nt; nt >= 0 && !p.delayed[0].fn; nt--) // (the plain form where no non-temporal one is built; R = non-temporal)
+                for (const RVariant &v : kStream2)
+                    if (v.T * v.J == s.T * s.J && v.R == nt) // (same row span; its own lane count)
+                        p.delayed[0] = Kernel{v.fn, v.T, fixed + (size_t)depth * per_pivot, kname("stream2_kernel<%d,%d%s>", v.T, v.J, nt ? ",nt" : "")};
+            p.delay_depth = depth;
+        }
+    }
+}
+
+// The kernels of a row shard (yalps_tableau_set_shard; `height`: the rows uploaded, objective row + own rows): the step in
+// place where a wide_kernel does it, with delayed row updates where that pays, its sweep then perhaps a launch of its own.
+void plan_shard(int pitch, int hcap, int nb, int height, Plan &p) {
+    p.shard_step = p.shard_sweep = Kernel();
+    p.shard_delayed = false;
+    // rows wide enough for wide_kernel are swept in place (YALPS_HIP_SHARD_INPLACE=0: ping-pong as in round 1)
+    if (!p.wide || !env_int("YALPS_HIP_SHARD_INPLACE", 1)) return;
+    const bool nt = env_int("YALPS_HIP_SHARD_NT", sizeof(double) * (size_t)pitch * (size_t)height > SWEEP_BEYOND_CACHE ? 1 : 0) != 0;
+    for (const WInplace &v : kWideInplace)
+        if (v.T == p.T && v.J == p.J)
+            p.shard_step = Kernel{reinterpret_cast<const void *>(v.fn[nt ? 1 : 0]), v.launchT, p.step.lds,
+                                     kname("wide_kernel<%d,%d,inplace%s>", v.launchT, v.T * v.J / v.launchT, nt ? ",nt" : "")};
+    // Delayed row updates (dshard_kernel.cuh): a pivot costs the shard its scalars, the sweep comes once per `depth` pivots.
+    // Shards swept in place with at least YALPS_HIP_DELAY_MIN_ROWS rows per workgroup; YALPS_HIP_SHARD_DELAY=0: one sweep per pivot.
+    const int rows_per_block = (hcap + nb - 1) / nb;
+    const int dJ = delayed_units_per_lane(pitch / 2);
+    if (!p.shard_step.fn || !dJ || !env_int("YALPS_HIP_SHARD_DELAY", 1) || rows_per_block < env_int("YALPS_HIP_DELAY_MIN_ROWS", 4)) return;
+    // (measured, us per pivot at depth 2 / 4 / 6 / 8: 2049 x 16385 73 / 53 / 48 / 46, 8193 x 16385 207 / 125 / 105 / 97:
+    // a launch-per-pivot step has a larger fixed part than stream3_kernel's, the deepest form wins everywhere)
+    // round 3: the sweep stages the pending rows in LDS one 1024-column panel at a time (panel_flush.cuh) -- up to 16
+    // pending pivots; the deepest form whose scalars + panel fit the LDS of a CU
+    // the sweep through LDS panels pays from DSHARD_PANEL_MIN_ROWS rows per workgroup on (below: the pending rows straight from L2,
+    // at most 8 pending pivots) -- YALPS_HIP_SHARD_PANEL=0|1 forces one or the other
+    const bool panel = env_int("YALPS_HIP_SHARD_PANEL", rows_per_block >= DSHARD_PANEL_MIN_ROWS ? 1 : 0) != 0;
+    // (measured, one rank, 16385 columns, us per pivot: 2049 rows -- 8 per workgroup -- straight from L2 48 at depth 8, panels 52;
+    // 4097 rows 63 / 59.5 at depth 8 / 16 from L2, panels 60; 8193 rows 91 from L2, panels 86 / 74 at depth 8 / 16; 16385 rows panels 102)
+    // (round 3, after the panel sweep lost its chains of round trips -- one rank, 16385 columns, us per pivot from L2 / through panels at
+    // depth 8, 12, 16: 2049 rows (8 per workgroup) 45.3 43.8 43.3 / 48.3 46.9 46.3; 4097 rows (16) 60.5 57.7 56.6 / 56.0 51.0 49.1;
+    // 6001 rows (24) 74.0 70.3 74.5 / 70.7 61.0 58.5)
+    const int depth_default = panel ? DSHARD_DEFAULT_DEPTH_PANEL : rows_per_block >= 8 ? 16 : DSHARD_DEFAULT_DEPTH;
+    size_t lds = 0;
+    const int depth = delayed_fit(depth_default, DSHARD_MAXD, rows_per_block, panel ? (size_t)DSHARD_PANEL_UNITS : 0, 150 * 1024, &lds);
+    if (!depth) return;
+    for (const RVariant &v : kDshard) // (the table's R: non-temporal | panel << 1)
+        if (v.T == 512 && v.J == dJ && v.R == ((nt ? 1 : 0) | (panel ? 2 : 0))) {
+            p.shard_step = Kernel{v.fn, 512, lds, kname("dshard_kernel<512,%d%s%s>", dJ, nt ? ",nt" : "", panel ? ",panel" : "")};
+            p.shard_delayed = true;
+        }
+    if (!p.shard_delayed) return;
+    p.delay_depth = depth;
+    // the sweep as a launch of its own, rows mapped to workgroups by (panel, row block): one fill per workgroup, no barrier
+    // between its waves afterwards -- whatever the rows per workgroup of the step kernel (YALPS_HIP_SHARD_XSWEEP=0: the step kernel sweeps)
+    // Measured, one rank, 16385 columns, us per pivot with the sweep inside the step kernel / as its own launch: 2049 rows (8 per
+    // workgroup) 42.9 / 38.7, 4097 (16) 49.6 / 46.6, 8193 (32) 61.2 / 63.0, 16385 (64) 93.3 / 95.8 (the launch sweeps at 3.6-3.9 TB/s
+    // whatever the rows; a row-major copy of the coefficients for it -- one cache line per row instead of 32 lines 131 KB apart per pair of
+    // rows -- changed nothing: 96.0 / 62.3 / 46.3 / 39.2) -- hence below 24 rows per workgroup.
+    if (env_int("YALPS_HIP_SHARD_XSWEEP", rows_per_block < DSHARD_XSWEEP_BELOW_ROWS ? 1 : 0)) {
+        p.shard_sweep = Kernel{yalps_dshard_sweep_fn(nt ? 1 : 0), 512, sizeof(double) * 2 * DSHARD_PANEL_UNITS * (size_t)depth,
+                                  nt ? "dshard_sweep_kernel<nt>" : "dshard_sweep_kernel"};
+        const int npan = (pitch / 2 + DSHARD_PANEL_UNITS - 1) / DSHARD_PANEL_UNITS;
+        p.shard_sweep_grid = npan * std::max(1, 256 / npan);
+    }
+}
+
 } // namespace
 
 struct yalps_ctx {
@@ -324,30 +643,14 @@ struct yalps_tableau {
     bool prefer_generic = false; // 8194..16385 columns, unsharded: the any-shape pair is on par with wide_kernel<1024,8>
                                  // on dense tableaux (60 vs 74 us/pivot at 1025x16385, 130 vs 126 at 4097x9001) and skips untouched rows
     int shard_parity = 0;
-    RVariant rvar{0, 0, 0, nullptr}; // resident kernel variant, fn == nullptr: tableau does not fit
-    int rgen = 1;                    // 2: rvar is a resident2_kernel
+    Plan plan; // every kernel this tableau can launch (plan_* at creation, plan_shard in set_shard)
     void *rc_sync = nullptr; // flags[2], verdict[2], error word of the persistent kernels (one allocation)
     size_t rc_sync_bytes = 0;
-    RVariant svar{0, 0, 0, nullptr}; // stream_kernel variant (persistent, in place)
-    RVariant svar_check{0, 0, 0, nullptr}; // the same with hasCycle (options.checkCycles)
-    bool sweep = false;                    // svar / svar_check are sweep_kernel variants
-    RVariant svar2{0, 0, 0, nullptr};      // stream3_kernel / stream2_kernel variant: delayed row updates (YALPS_HIP_DELAY=0: never)
-    RVariant svar2_check{0, 0, 0, nullptr}; // ... with hasCycle (stream3_kernel only)
-    bool sattr2_check = false;
-    size_t sshmem2 = 0;
-    bool sattr2 = false;
     bool last_delayed = true; // what the last in-place solve ran (before the first one: what it would run)
-    bool stream3 = false;     // svar2 is a stream3_kernel variant (rows of 8194 .. 16385 columns)
-    bool sattr_check = false;
-    size_t sshmem = 0;
-    bool sattr = false;
     bool occupancy_warned = false;
     int64_t giveups = 0;             // persistent launches of this tableau that gave up waiting (fell back)
     int last_path = 0;               // what the last solve ran: 1 resident, 2 streaming, 4 small, 8 in place (sums: fallbacks)
     int64_t last_launches = 0;       // kernel launches of the last solve that did work (resident: chunks)
-    size_t rshmem = 0;
-    size_t rx_shmem = 0; // resident kernel with LDS rows: its (fixed) dynamic LDS size
-    RVariant rvar_tag{0, 0, 0, nullptr}; // the same variant with tagged candidate rows (fn == nullptr: not for this shape)
     // Control block, ONE device allocation: [flags of both parities | verdict words | granules of the tagged variant |
     // error word (16 B)] [st0 | st1 | cst].  rc_sync / rc_sync_bytes = its first part, zeroed by one memset before every
     // persistent launch; [error word .. st1] comes back in one copy after it; [st0 .. cst] goes up in one copy when a solve
@@ -358,21 +661,10 @@ struct yalps_tableau {
     int32_t perm_cap = 0;
     int32_t *perm_backup = nullptr; // basis before the resident launch in flight (restored if it fails)
     int32_t perm_len = 0; // entries of pos / var (width + GLOBAL height)
-    Variant var{};
-    int wT_inplace = 0;
-    KernelFn dfn = nullptr;         // row shard with delayed row updates: dshard_kernel<512, dJ, nt> (d.dpend / dcolv / dnqv / dlav / dstate)
-    int dJ = 0, dnt = 0, dpanel = 0;
-    const void *xsweep_fn = nullptr; // dshard_sweep_kernel: the shard's sweep as a launch of its own (dsweep_kernel.cuh)
-    int xsweep_grid = 0, shard_pend = 0; // its workgroups (panels x row blocks); pivots the host knows to be pending
-    size_t xsweep_lds = 0;
-    size_t dshmem = 0;
-    void *dsh_block = nullptr;      // ... its arrays, one allocation
+    int shard_pend = 0;             // row shard: pivots the host knows to be pending behind the step kernel (plan.shard_sweep)
+    void *dsh_block = nullptr;      // row shard with delayed row updates (dshard_kernel): d.dpend / dcolv / dnqv / dlav / dstate, one allocation
     int32_t *cyc_block = nullptr;   // row shard: shard_cycle_kernel's verdict words (Desc::cyc_verdict)
     bool shard_check = false;       // ... the running sharded solve has checkCycles on (yalps_shard_begin)
-    KernelFn wfn_inplace = nullptr; // row shard: wide_kernel<.., true, nt> for the MODE_SHARD launches (in place; d.obj holds the objective replicas)
-    KernelFn wfn = nullptr; // wide_kernel variant used for FUSED / APPLY / SHARD launches when the tableau is
-                            // too wide or too tall for pivot_kernel's register-resident batches
-    size_t wshmem = 0;
     int nb = 1;
     hipGraph_t graph[2] = {nullptr, nullptr}; // [0] fused, [1] decide/apply (checkCycles)
     hipGraphExec_t graph_exec[2] = {nullptr, nullptr};
@@ -399,70 +691,44 @@ struct yalps_tableau {
     // every kernel the last solve (or sharded run since yalps_shard_begin) launched, once each in the order of its first
     // launch, spelt as tests/_census.py spells the compiled symbols (yalps_tableau_info's `launched=`)
     std::vector<std::string> launched;
-    std::string shard_step_name; // the in-place step kernel of a row shard (set_shard): dshard_kernel or wide_kernel<.., inplace>
 };
 
 namespace {
 
-// ---- the record behind `launched=`: one name per compiled symbol, template arguments in template order, bool switches
-// spelt as the flags that select them (,nt ,check ,panel|,direct ,lds ,tag ,inplace) --------------------------------
+// the record behind `launched=`: every kernel once, by its plan record's name, in the order of its first launch
 void note_launch(yalps_tableau *t, const std::string &name) {
     for (const std::string &k : t->launched)
         if (k == name) return;
     t->launched.push_back(name);
 }
 
-std::string kname(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
-std::string kname(const char *fmt, ...) {
-    char buf[96];
-    va_list ap;
-    va_start(ap, fmt);
-    std::vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    return buf;
+// Dynamic LDS beyond 48 KB: the attribute is raised once per kernel, before its first launch that needs it.
+int need_lds(const yalps_ctx *c, Kernel &k, size_t lds) {
+    if (lds <= 48 * 1024 || k.big_lds) return 0;
+    if (int rc = allow_big_lds(c->device, k.fn)) return rc;
+    k.big_lds = true;
+    return 0;
 }
 
-// the kernel of a persistent launch: pv is one of rvar / rvar_tag / svar / svar_check / svar2 / svar2_check
-std::string persistent_name(const yalps_tableau *t, const RVariant &pv, bool in_place, bool delayed, bool check) {
-    if (!in_place) {
-        if (t->rvar_tag.fn && pv.fn == t->rvar_tag.fn) return kname("resident_kernel<%d,%d,%d,tag>", pv.T, pv.J, pv.R);
-        if (t->d.extra) return kname("resident_kernel<%d,%d,%d,lds>", pv.T, pv.J, pv.R);
-        return kname("resident%s_kernel<%d,%d,%d>", t->rgen == 2 ? "2" : "", pv.T, pv.J, pv.R);
-    }
-    if (delayed && t->stream3)
-        return kname("stream3_kernel<%d,%d%s%s,%s>", pv.T, pv.J, (pv.R & 1) ? ",nt" : "", check ? ",check" : "", (pv.R & 2) ? "panel" : "direct");
-    if (delayed) return kname("stream2_kernel<%d,%d%s>", pv.T, pv.J, pv.R ? ",nt" : "");
-    if (t->sweep) return kname("sweep_kernel<%d,%d%s%s>", pv.T, pv.J, check ? ",check" : "", pv.R ? ",nt" : "");
-    return kname("stream_kernel<%d,%d%s>", pv.T, pv.J, check ? ",check" : "");
-}
-
-// the kernel of launch_one's launches in `mode`
-std::string launch_one_name(const yalps_tableau *t, int mode) {
-    if (t->wfn && mode != MODE_DECIDE) return kname("wide_kernel<%d,%d>", t->var.T, t->var.J);
-    return kname("pivot_kernel<%d,%d,%d>", t->var.T, t->var.J, t->var.R);
+// the resident kernel's dynamic LDS: its LDS rows (a fixed size), else both permutations
+size_t resident_lds(const yalps_tableau *t) {
+    return t->plan.resident.lds ? t->plan.resident.lds : sizeof(int32_t) * 2 * (size_t)t->perm_len;
 }
 
 void launch_one(yalps_tableau *t, int parity, int mode, int force, const double *gather = nullptr) {
-    const int grid = mode == MODE_DECIDE ? 1 : t->nb;
-    if (t->wfn && mode != MODE_DECIDE)
-        t->wfn<<<dim3(grid), dim3(t->var.T), t->wshmem, t->ctx->stream>>>(t->d, parity, mode, force, gather);
-    else
-        t->var.fn<<<dim3(grid), dim3(t->var.T), 0, t->ctx->stream>>>(t->d, parity, mode, force, gather);
+    const Kernel &k = mode == MODE_DECIDE ? t->plan.decide : t->plan.step;
+    k.as<KernelFn>()<<<dim3(mode == MODE_DECIDE ? 1 : t->nb), dim3(k.lanes), k.lds, t->ctx->stream>>>(t->d, parity, mode, force, gather);
 }
 
 // the elimination step of a row shard (MODE_SHARD): in place where the shard has the kernel for it
 void launch_shard(yalps_tableau *t, const double *gathered) {
     const int force = t->ctx->nt_stores ? 64 : 0;
+    const Kernel &k = t->plan.shard_step.fn ? t->plan.shard_step : t->plan.step;
     if (t->shard_check) note_launch(t, "shard_cycle_kernel");
-    note_launch(t, (t->dfn || t->wfn_inplace) ? t->shard_step_name : launch_one_name(t, MODE_SHARD));
+    note_launch(t, k.name);
     if (t->shard_check) // checkCycles: the detector's verdict on the pivot this step is about to decide (shard_kernels.cuh)
-        shard_cycle_kernel<<<dim3(1), dim3(1024), 0, t->ctx->stream>>>(t->d, t->shard_parity, gathered, (t->dfn || t->wfn_inplace) ? 1 : 0);
-    if (t->dfn)
-        t->dfn<<<dim3(t->nb), dim3(512), t->dshmem, t->ctx->stream>>>(t->d, t->shard_parity, MODE_SHARD, force, gathered);
-    else if (t->wfn_inplace)
-        t->wfn_inplace<<<dim3(t->nb), dim3(t->wT_inplace), t->wshmem, t->ctx->stream>>>(t->d, t->shard_parity, MODE_SHARD, force, gathered);
-    else
-        launch_one(t, t->shard_parity, MODE_SHARD, force, gathered);
+        shard_cycle_kernel<<<dim3(1), dim3(1024), 0, t->ctx->stream>>>(t->d, t->shard_parity, gathered, t->plan.shard_step.fn ? 1 : 0);
+    k.as<KernelFn>()<<<dim3(t->nb), dim3(k.lanes), k.lds, t->ctx->stream>>>(t->d, t->shard_parity, MODE_SHARD, force, gathered);
 }
 
 int launch_batch(yalps_tableau *t, int which) {
@@ -510,6 +776,26 @@ int grow_history(yalps_tableau *t, int64_t need, int64_t keep) {
     return 0;
 }
 
+// checkCycles: grow the cycle history and tell the device where it lives now (the caller knows that nothing in flight reads it)
+int regrow_history(yalps_tableau *t, int64_t need, int64_t keep) {
+    if (int rc = grow_history(t, need, keep)) return rc;
+    YConst hc;
+    HIP_TRY(hipMemcpy(&hc, t->d.cst, sizeof(YConst), hipMemcpyDeviceToHost));
+    hc.hist_cap = t->hist_cap;
+    hc.hist_leaving = t->hist[0];
+    hc.hist_entering = t->hist[1];
+    HIP_TRY(hipMemcpy(t->d.cst, &hc, sizeof(YConst), hipMemcpyHostToDevice));
+    return 0;
+}
+
+// the tableau and its column 0 from buffer `from` to the other one
+int copy_buffer(yalps_tableau *t, int from) {
+    const Desc &d = t->d;
+    HIP_TRY(hipMemcpyAsync(d.mat[from ^ 1], d.mat[from], sizeof(double) * (size_t)d.pitch * t->height, hipMemcpyDeviceToDevice, t->ctx->stream));
+    HIP_TRY(hipMemcpyAsync(d.rhs[from ^ 1], d.rhs[from], sizeof(double) * (size_t)t->height, hipMemcpyDeviceToDevice, t->ctx->stream));
+    return 0;
+}
+
 int init_state(yalps_tableau *t, double precision, double maxPivots, int32_t checkCycles, bool wait = true) {
     hipStream_t s = t->ctx->stream;
     if (checkCycles && !t->hist_cap) {
@@ -517,10 +803,7 @@ int init_state(yalps_tableau *t, double precision, double maxPivots, int32_t che
         if (rc) return rc;
     }
     if (t->cur != 0) { // FUSED graphs derive the buffer index from the launch parity: start from 0
-        const Desc &d = t->d;
-        HIP_TRY(hipMemcpyAsync(d.mat[0], d.mat[1], sizeof(double) * (size_t)d.pitch * t->height,
-                               hipMemcpyDeviceToDevice, s));
-        HIP_TRY(hipMemcpyAsync(d.rhs[0], d.rhs[1], sizeof(double) * (size_t)t->height, hipMemcpyDeviceToDevice, s));
+        if (int rc = copy_buffer(t, 1)) return rc;
         t->cur = 0;
     }
     YConst &hc = *reinterpret_cast<YConst *>(t->host_state + 4); // pinned, like the state slots
@@ -697,49 +980,30 @@ void yalps_ctx_destroy(yalps_ctx *c) {
 
 static int32_t tableau_create_impl(yalps_ctx *ctx, int32_t width, int32_t hcap, yalps_tableau **out) {
     if ((int64_t)width + hcap > INT32_MAX / 2) return fail(YALPS_E_ARG, "tableau too large");
-    const int n = width - 1, units = (n + 1) / 2;
-    // kernel variant: lanes x units-per-lane must span the row; rows in flight sized so that
-    // one workgroup per CU covers the tableau in one batch when it can
-    int T = units <= 512 ? 256 : 1024;
-    int J = 1;
-    while (T * J < units) J *= 2;
     HIP_TRY(hipSetDevice(ctx->device));
     yalps_tableau *t = new yalps_tableau();
     t->ctx = ctx;
     *out = t; // reachable from now on: the wrapper frees a half-built object on failure
-    if (J > 8) { // rows wider than 16385 columns: the any-shape pair of generic_kernels.cuh (run-time loops only)
-        t->generic = true;
-        T = 1024;
-        J = 8;
+    // ---- selection: the plan, from the shape and the switches alone
+    const Shape shape = shape_of(width, hcap, ctx->max_blocks);
+    Plan &p = t->plan;
+    plan_launch_per_pivot(shape, p);
+    t->generic = shape.too_wide || env_int("YALPS_HIP_GENERIC", 0) || // (test hook: any shape through the any-shape pair)
+                 p.step.lds > 150 * 1024;                             // (pivot row + per-row scalars exceed LDS)
+    t->prefer_generic = shape.J == 8 && !env_int("YALPS_HIP_WIDE8", 0);
+    t->nb = shape.nb;
+    if (t->nb <= ctx->num_cus && !t->generic) { // (in place also where a resident variant exists: the fallback order is resident, in place, launches)
+        plan_resident(shape, p);
+        plan_inplace(shape, p);
+        plan_delayed(shape, p);
     }
-    if (env_int("YALPS_HIP_GENERIC", 0)) t->generic = true; // (test hook: any shape through the any-shape pair)
-    t->prefer_generic = J == 8 && !env_int("YALPS_HIP_WIDE8", 0);
-    const int forceR = env_int("YALPS_HIP_ROWS", 0);
-    // spread the rows over all workgroups; rows in flight per lane R >= rows per workgroup if any
-    // variant allows it (one batch per launch), else the largest R (several batches)
-    t->nb = hcap < ctx->max_blocks ? hcap : ctx->max_blocks;
-    const int rows_per_block = (hcap + t->nb - 1) / t->nb;
-    const Variant *pick = nullptr;
-    for (const Variant &v : kVariants) {
-        if (v.T != T || v.J != J) continue;
-        pick = &v; // candidates are listed by increasing R
-        if (v.R >= (forceR ? forceR : rows_per_block)) break;
-    }
-    t->var = *pick;
-    // (pivot_kernel's <1024,2,*> variants spill at the 128-VGPR cap: 47 us/pivot on a 1477x2388 tableau
-    // against 27 us for wide_kernel)
-    if (J >= 4 || (T == 1024 && J >= 2) || rows_per_block > pick->R || env_int("YALPS_HIP_WIDE", 0)) {
-        for (const WVariant &v : kWide)
-            if (v.T == T && v.J == J) t->wfn = v.fn;
-        t->wshmem = sizeof(double) * ((size_t)((n + 15) / 16 * 16 < 16 ? 16 : (n + 15) / 16 * 16) + 4 * (size_t)rows_per_block); // (+ 2 per row: in-place shards)
-        if (t->wshmem > 150 * 1024) t->generic = true; // (pivot row + per-row scalars exceed LDS)
-        if (!t->generic && t->wshmem > 48 * 1024)
-            if (int rc = allow_big_lds(ctx->device, reinterpret_cast<const void *>(t->wfn))) return rc;
-    }
+    if (!t->generic)
+        if (int rc = need_lds(ctx, p.step, p.step.lds)) return rc;
 
+    // ---- allocation and the control block's layout: read the plan
     Desc &d = t->d;
     d.w = width;
-    d.n = n;
+    d.n = shape.n;
     d.hcap = hcap;
     d.nb = t->nb;
     d.nshards = 1;
@@ -747,8 +1011,11 @@ static int32_t tableau_create_impl(yalps_ctx *ctx, int32_t width, int32_t hcap, 
     d.row_base = 0;
     for (int k = 0; k <= MAX_SHARDS; k++) d.bounds[k] = k == 0 ? 0 : INT_MAX;
     t->perm_len = width + hcap;
-    d.pitch = (n + 15) / 16 * 16; // 128-byte rows
-    if (d.pitch < 16) d.pitch = 16;
+    d.pitch = shape.pitch;
+    d.extra = p.extra;
+    d.xl_ofs = p.xl_ofs;
+    d.sw_nt = p.sw_nt;
+    d.delay_depth = p.delay_depth;
     const size_t mat_bytes = sizeof(double) * (size_t)d.pitch * hcap;
     hipStream_t s = ctx->stream;
     for (int k = 0; k < (t->generic ? 1 : 2); k++) { // (the any-shape pair works in place: one buffer)
@@ -768,151 +1035,13 @@ static int32_t tableau_create_impl(yalps_ctx *ctx, int32_t width, int32_t hcap, 
         HIP_TRY(hipMalloc(&d.part_ratio[k], sizeof(Part) * MAX_BLOCKS));
         HIP_TRY(hipMalloc(&d.part_rhs[k], sizeof(Part) * MAX_BLOCKS));
     }
-    // resident (on-chip) solver: needs every workgroup co-resident (one per CU) and the rows of a
-    // workgroup in registers
     d.perm_len = t->perm_len;
-    if (t->nb <= ctx->num_cus && !t->generic) {
-        // (16 waves per CU were tried for 2049^2: <1024,1,9> spills at the 128-VGPR cap and its barriers
-        // cost more: 92 K pivots/s against 144 K for <512,2,9>)
-        int best = INT_MAX, fT = 0, fJ = 0, fR = 0;
-        if (const char *force = std::getenv("YALPS_HIP_RVARIANT")) std::sscanf(force, "%d,%d,%d", &fT, &fJ, &fR);
-        for (const RVariant &v : kResident) {
-            if (v.T * v.J < units || v.R < rows_per_block) continue;
-            if (fT && (v.T != fT || v.J != fJ || v.R != fR)) continue; // experiments: YALPS_HIP_RVARIANT=T,J,R
-            const int regs = v.J * v.R * 1024 + v.T; // fewest row registers, then fewest waves
-            if (regs < best) {
-                best = regs;
-                t->rvar = v;
-            }
-        }
-        if (t->rvar.fn && env_int("YALPS_HIP_RESIDENT_GEN", 2) >= 2)
-            for (const RVariant &v : kResident2)
-                if (v.T == t->rvar.T && v.J == t->rvar.J && v.R == t->rvar.R) {
-                    t->rvar = v;
-                    t->rgen = 2;
-                }
-        if (!t->rvar.fn && env_int("YALPS_HIP_LDS_ROWS", 1)) { // a little too tall: park the rows that are missing in LDS
-            const int xl_ofs = (2 * (width + hcap) + 3) / 4 * 4;
-            int best_extra = INT_MAX;
-            for (const RVariant &v : kResidentLds) {
-                const int extra = rows_per_block - v.R;
-                if (v.T * v.J < units || extra < 1 || extra > XROWS) continue;
-                if (fT && (v.T != fT || v.J != fJ || v.R != fR)) continue;
-                const size_t bytes = sizeof(int32_t) * (size_t)xl_ofs + sizeof(double) * (size_t)extra * d.pitch;
-                if (bytes > LDS_DYNAMIC_MAX || extra >= best_extra) continue;
-                best_extra = extra;
-                t->rvar = v;
-                t->rx_shmem = bytes;
-                d.extra = extra;
-                d.xl_ofs = xl_ofs;
-            }
-        }
+    if (p.stream3) {
+        HIP_TRY(hipMalloc(&d.pend, sizeof(double) * 8 * 2 * (size_t)p.delay_depth * d.pitch)); // (per XCD: two sets of `depth` rows, shared by its workgroups)
+        if (p.ob_park) HIP_TRY(hipMalloc(&d.ob_park, sizeof(double) * (size_t)t->nb * d.pitch));
     }
-    // persistent in-place kernel for what does not fit on chip: lanes x units span the row, the normalised
-    // pivot row + my rows' scalars fit in LDS
-    if (t->nb <= ctx->num_cus && !t->generic) { // (also where a resident variant exists: the fallback order is resident, in place, launches)
-        for (const RVariant &v : kStream)
-            if (v.T == T && v.J == J) t->svar = v;
-        for (const RVariant &v : kStreamCheck)
-            if (v.T == T && v.J == J) t->svar_check = v;
-        t->sshmem = sizeof(double) * ((size_t)d.pitch + 3 * (size_t)rows_per_block) + sizeof(int32_t) * (size_t)rows_per_block;
-        if (t->sshmem > 150 * 1024) t->svar.fn = t->svar_check.fn = nullptr;
-        // what streams from HBM anyway goes to sweep_kernel: rows of 8194 .. 16385 columns (no stream_kernel spans them), and
-        // 4098 .. 8193-column tableaux too big for the Infinity Cache (measured at 8193 x 8193: stream_kernel 5.1 TB/s)
-        const size_t tab_bytes = sizeof(double) * (size_t)d.pitch * hcap;
-        const int sweep_mode = env_int("YALPS_HIP_SWEEP", 1); // 0: never, 1: by size, 2: wherever a variant exists
-        if (sweep_mode && (J == 8 || (J == 4 && (tab_bytes > SWEEP_BEYOND_CACHE || sweep_mode == 2)))) {
-            const size_t lds = sizeof(double) * 2 * 512 * (size_t)(2 * J) + (4 * sizeof(double) + sizeof(int32_t)) * (size_t)rows_per_block + 64;
-            if (lds <= 150 * 1024) {
-                int want_nt = tab_bytes > SWEEP_BEYOND_CACHE ? 1 : 0;
-                if (const char *e = std::getenv("YALPS_HIP_SWEEP_NT")) want_nt = std::atoi(e) != 0;
-                const int sT = 512, sJ = 2 * J; // (sweep_kernel runs 512 lanes x 8 / 16 units: persistent_sweep.hip)
-                for (const RVariant &v : kSweep)
-                    if (v.T == sT && v.J == sJ && v.R == want_nt) {
-                        t->svar = v;
-                        t->sweep = true;
-                    }
-                if (t->sweep) {
-                    t->svar_check.fn = nullptr;
-                    for (const RVariant &v : kSweepCheck)
-                        if (v.T == sT && v.J == sJ && v.R == want_nt) t->svar_check = v;
-                    t->sshmem = lds;
-                    d.sw_nt = want_nt;
-                }
-            }
-        }
-    }
-    // Delayed row updates: where an in-place kernel applies (and no checkCycles), several pivots per sweep.
-    //   stream3_kernel<512, J> (objective replica in LDS, the pending pivot rows in a global scratch shared by all workgroups,
-    //   up to 8 of them): rows of up to 16385 columns with at least 4 rows per workgroup;
-    //   stream2_kernel (pending rows in LDS, up to 4): fewer rows per workgroup, and where YALPS_HIP_DELAY_KERNEL=2 asks for it.
-    // Measured against each other on one box, us per pivot, stream3 / stream2: 4097^2 20.2 / 26.2, 6001^2 33.6 / 50.0,
-    // 8193 x 4097 30.0 / 42.8, 8193^2 48.3 / 105, 12001 x 1501 21.8 / 26.4, 11001 x 901 17.2 / 24.0, 16385^2 159 / --;
-    // 1025 x 16385: stream3 34.3, sweep_kernel 50.3.
-    if (t->svar.fn && env_int("YALPS_HIP_DELAY", 1)) {
-        const int units = d.pitch / 2;
-        const size_t tab_bytes2 = sizeof(double) * (size_t)d.pitch * hcap;
-        int want_nt2 = tab_bytes2 > SWEEP_BEYOND_CACHE ? 1 : 0;
-        if (const char *e = std::getenv("YALPS_HIP_DELAY_NT")) want_nt2 = std::atoi(e) != 0;
-        int sJ = 0;
-        for (int cand : {1, 2, 4, 6, 8, 16})
-            if (!sJ && 512 * cand >= units) sJ = cand;
-        const int want_kernel = env_int("YALPS_HIP_DELAY_KERNEL", 3);
-        if (want_kernel == 3 && sJ && t->nb <= 256 && rows_per_block >= env_int("YALPS_HIP_DELAY_MIN_ROWS", 4)) { // (256: its table of the workgroups' XCDs)
-            // depth: a pivot's head grows with the pivots pending (the candidate row gets them all applied before it is
-            // published), the sweep shrinks: measured best 8 at 65 and 33 rows per workgroup, 6-8 at 17, 4 at 5-9
-            // (with the two-step exchange of the 8- and 16-unit forms only the winner's row gets them applied: 2049 x 16385 at
-            // depth 4 / 6 / 8: 48.1 / 46.2 / 44.8 us per pivot, 4097 x 8193 40.6 / 36.7 / 35.1, 4097 x 16385 73.8 / 64.5 / 60.5,
-            // 1025 x 16385 31.6 / 31.4 / 32.3)
-            // (round 3: the sweep stages the pending rows in LDS one 1024-column panel at a time -- panel_flush.cuh -- and the objective
-            // replica moved to registers: up to STREAM3_MAXD = 16 pending pivots, the deepest form whose scalars + panel fit in LDS)
-            // The panels pay from STREAM3_PANEL_MIN_ROWS rows per workgroup on (YALPS_HIP_STREAM3_PANEL=0|1 forces); below, the sweep reads
-            // the pending rows straight from the XCD's scratch and the depths are round 2's (shape sweep, us per pivot with panels
-            // / straight from L2, same build: 4 rows per workgroup -- 1025 x 8001 23.6 / 19.1, 1025 x 16385 38.3 / 28.5; 8 rows -- 2049 x 16385
-            // 40.2 / 38.1; 17 rows -- 4097 x 16385 48.9 / 54.9, 4097^2 19.7 / 20.4; 20 rows -- 5001^2 24.8 / 28.2; beyond: panels only,
-            // 6001^2 28.1, 8193^2 37.5, 16385^2 87.8 -- round 2: 33.4, 45.5, 141).
-            const bool panel3 = env_int("YALPS_HIP_STREAM3_PANEL", rows_per_block >= STREAM3_PANEL_MIN_ROWS ? 1 : 0) != 0;
-            const int depth_default = panel3 ? (sJ == 16 ? STREAM3_DEPTH_J16 : STREAM3_DEFAULT_DEPTH_WIDE)
-                                             : sJ >= 8 ? (rows_per_block >= 8 ? 12 : 6) : std::min(8, std::max(4, (rows_per_block + 1) / 3)); // (2049 x 16385 from L2 at depth 8 / 12 / 16: 35.8 / 34.8 / 34.9 us per pivot)
-            int depth3 = std::min(STREAM3_MAXD, std::max(2, env_int("YALPS_HIP_DELAY_DEPTH", depth_default)));
-            auto lds3_of = [&](int dep) {
-                return sizeof(double) * (2 * (size_t)dep + 2) * (size_t)rows_per_block + 3 * sizeof(int32_t) * (((size_t)rows_per_block + 3) / 4 * 4) +
-                       (panel3 ? sizeof(double) * (size_t)dep * 2 * stream3_panel_units(sJ) : 0);
-            };
-            const size_t lds3_cap = panel3 ? LDS_DYNAMIC_MAX : 150 * 1024; // (the panels take what the CU has: 160 KB less the kernel's static arrays)
-            while (depth3 > 2 && lds3_of(depth3) > lds3_cap) depth3--;
-            const size_t lds3 = lds3_of(depth3);
-            const int want_r = want_nt2 | (panel3 ? 2 : 0);
-            if (lds3 <= lds3_cap)
-                for (const RVariant &v : kStream3)
-                    if (v.T == 512 && v.J == sJ && v.R == want_r) t->svar2 = v;
-            if (t->svar2.fn)
-                for (const RVariant &v : kStream3Check) // (checkCycles with rows of 16 units per lane: the form that sweeps straight from L2 -- with the panels it does not fit the registers; same LDS layout, the panel area unused)
-                    if (v.T == 512 && v.J == sJ && v.R == (sJ == 16 ? want_nt2 : want_r)) t->svar2_check = v;
-            if (t->svar2.fn) {
-                t->sshmem2 = lds3;
-                d.delay_depth = depth3;
-                HIP_TRY(hipMalloc(&d.pend, sizeof(double) * 8 * 2 * (size_t)depth3 * d.pitch)); // (per XCD: two sets of `depth` rows, shared by its workgroups)
-                if (sJ >= 6) HIP_TRY(hipMalloc(&d.ob_park, sizeof(double) * (size_t)t->nb * d.pitch)); // (rows of 6+ units per lane: the objective replicas during a sweep)
-                t->stream3 = true;
-            }
-        }
-        // (with two or three rows per workgroup there is nothing to save: 257 x 8193 16.6 us delayed against 14.5)
-        if (!t->svar2.fn && T * J <= 4096 && rows_per_block >= env_int("YALPS_HIP_DELAY_MIN_ROWS", 4)) { // stream2_kernel: as many pending pivots as LDS holds pivot rows (+ two scalars per row of mine) for, at most 4
-            const size_t per_pivot = sizeof(double) * ((size_t)d.pitch + 2 * (size_t)rows_per_block);
-            const size_t fixed = sizeof(double) * 2 * (size_t)rows_per_block + sizeof(int32_t) * (size_t)rows_per_block;
-            int depth = (int)std::min<size_t>(4, (150 * 1024 - fixed) / per_pivot);
-            depth = std::min(depth, std::max(1, env_int("YALPS_HIP_DELAY_DEPTH", 4)));
-            if (depth >= 2) {
-                for (int nt = want_nt2; nt >= 0 && !t->svar2.fn; nt--) // (the plain form where no non-temporal one is built)
-                    for (const RVariant &v : kStream2)
-                        if (v.T * v.J == T * J && v.R == nt) t->svar2 = v; // (same row span; its own lane count)
-                t->sshmem2 = fixed + (size_t)depth * per_pivot;
-                d.delay_depth = depth;
-            }
-        }
-    }
-    if (t->rvar.fn || t->svar.fn) {
+    const bool persistent = p.resident.fn || p.inplace[0].fn;
+    if (persistent) {
         for (int k = 0; k < 2; k++) {
             HIP_TRY(hipMalloc(&d.rc_rows[k], sizeof(double) * (size_t)t->nb * d.pitch));
             HIP_TRY(hipMalloc(&d.rc_key[k], sizeof(double) * ((size_t)t->nb + 8)));
@@ -920,19 +1049,14 @@ static int32_t tableau_create_impl(yalps_ctx *ctx, int32_t width, int32_t hcap, 
     }
     {
         static_assert(sizeof(YState) % 8 == 0 && sizeof(YConst) % 8 == 0, "control block layout");
-        const bool persistent = t->rvar.fn || t->svar.fn;
         const size_t nflag = persistent ? 2 * (size_t)t->nb : 0;
-        // narrow rows: the tagged form of the same variant, if built (YALPS_HIP_TAG=0 switches it off)
-        if (t->rvar.fn && !d.extra && env_int("YALPS_HIP_TAG", 1))
-            for (const RVariant &v : kResidentTag)
-                if (v.T == t->rvar.T && v.J == t->rvar.J && v.R == t->rvar.R) t->rvar_tag = v;
         const size_t tag_row = 2 * (size_t)d.pitch + 2;
-        const size_t tag_bytes = t->rvar_tag.fn ? sizeof(double) * 2 * (size_t)t->nb * tag_row : 0;
-        const size_t sweep_bytes = t->sweep ? ((size_t)yalps_sweep_sync_bytes() + 15) / 16 * 16 + 32 * 2 * (size_t)t->nb : 0;
+        const size_t tag_bytes = p.tagged ? sizeof(double) * 2 * (size_t)t->nb * tag_row : 0;
+        const size_t sweep_bytes = p.sweep ? ((size_t)yalps_sweep_sync_bytes() + 15) / 16 * 16 + 32 * 2 * (size_t)t->nb : 0;
         // stream3_kernel's two-step exchange: [nb] XCD ids (int32, padded to 16 B) | [2][nb] slice flags | [2][nb][HP_SCAL] candidate scalars
-        const size_t hp_xcc_bytes = t->stream3 ? (sizeof(int32_t) * (size_t)t->nb + 15) / 16 * 16 : 0;
-        const size_t hp_flag_bytes = t->stream3 ? sizeof(unsigned long long) * 2 * (size_t)t->nb : 0;
-        const size_t hp_scal_bytes = t->stream3 ? sizeof(double) * 2 * (size_t)t->nb * HP_SCAL : 0;
+        const size_t hp_xcc_bytes = p.stream3 ? (sizeof(int32_t) * (size_t)t->nb + 15) / 16 * 16 : 0;
+        const size_t hp_flag_bytes = p.stream3 ? sizeof(unsigned long long) * 2 * (size_t)t->nb : 0;
+        const size_t hp_scal_bytes = p.stream3 ? sizeof(double) * 2 * (size_t)t->nb * HP_SCAL : 0;
         const size_t hp_bytes = hp_xcc_bytes + hp_flag_bytes + hp_scal_bytes;
         t->rc_sync_bytes = sizeof(unsigned long long) * (2 * nflag + 2) + tag_bytes + sweep_bytes + hp_bytes + 32 + 16; // (a multiple of 16; 32: rc_rowflag)
         HIP_TRY(hipMalloc(&t->ctl_block, t->rc_sync_bytes + 2 * sizeof(YState) + sizeof(YConst)));
@@ -942,16 +1066,16 @@ static int32_t tableau_create_impl(yalps_ctx *ctx, int32_t width, int32_t hcap, 
         d.rc_flag[0] = base;
         d.rc_flag[1] = base + nflag;
         d.rc_verdict = base + 2 * nflag;
-        if (t->rvar_tag.fn) {
+        if (p.tagged) {
             d.rc_tag[0] = reinterpret_cast<double *>(base + 2 * nflag + 2);
             d.rc_tag[1] = d.rc_tag[0] + (size_t)t->nb * tag_row;
         }
-        if (t->sweep) {
+        if (p.sweep) {
             char *sw = reinterpret_cast<char *>(base + 2 * nflag + 2) + tag_bytes;
             d.sw_sync = reinterpret_cast<unsigned long long *>(sw);
             d.sw_recs = reinterpret_cast<unsigned long long *>(sw + ((size_t)yalps_sweep_sync_bytes() + 15) / 16 * 16);
         }
-        if (t->stream3) {
+        if (p.stream3) {
             char *hp = reinterpret_cast<char *>(base + 2 * nflag + 2) + tag_bytes + sweep_bytes;
             d.hp_xcc = reinterpret_cast<int32_t *>(hp);
             d.hp_flag = reinterpret_cast<unsigned long long *>(hp + hp_xcc_bytes);
@@ -1017,34 +1141,25 @@ int32_t yalps_tableau_height(const yalps_tableau *t) { return t ? t->height : 0;
 
 int32_t yalps_tableau_info(const yalps_tableau *t, char *buf, int32_t len) {
     if (!t || !buf || len < 1) return fail(YALPS_E_ARG, "yalps_tableau_info: bad argument");
-    char res[96] = "none", inp[64] = "none";
-    if (t->rvar.fn)
-        std::snprintf(res, sizeof res, "resident%s_kernel<%d,%d,%d%s> chunk=%d lds_rows=%d", t->rgen == 2 && !t->rvar_tag.fn ? "2" : "", t->rvar.T, t->rvar.J, t->rvar.R,
-                      t->d.extra ? ",lds" : t->rvar_tag.fn ? ",tag" : "", RESIDENT_CHUNK, t->d.extra);
-    if (t->svar2.fn && t->last_delayed)
-        std::snprintf(inp, sizeof inp, "stream%d_kernel<%d,%d%s> delay_depth=%d%s", t->stream3 ? 3 : 2, t->svar2.T, t->svar2.J, (t->svar2.R & 1) ? ",nt" : "", t->d.delay_depth,
-                      t->stream3 ? ((t->svar2.R & 2) ? " sweep=panels" : " sweep=direct") : "");
-    else if (t->svar.fn)
-        std::snprintf(inp, sizeof inp, "%s_kernel<%d,%d%s>", t->sweep ? "sweep" : "stream", t->svar.T, t->svar.J, t->sweep && t->d.sw_nt ? ",nt" : "");
-    std::string launched;
+    const Plan &p = t->plan;
+    std::string res = "none", inp = "none", launched;
+    if (p.resident.fn) res = p.resident.name + kname(" chunk=%d lds_rows=%d", RESIDENT_CHUNK, t->d.extra);
+    if (p.delayed[0].fn && t->last_delayed)
+        inp = (p.delayed[0].info.empty() ? p.delayed[0].name : p.delayed[0].info) + kname(" delay_depth=%d", t->d.delay_depth) + p.delayed[0].info_tail;
+    else if (p.inplace[0].fn)
+        inp = p.inplace[0].name;
     for (const std::string &k : t->launched) launched += (launched.empty() ? "" : "+") + k;
-    char str[64];
-    if (t->dfn)
-        std::snprintf(str, sizeof str, "dshard_kernel<512,%d%s%s>,delay_depth:%d", t->dJ, t->dnt ? ",nt" : "", t->dpanel ? ",panel" : "", t->d.delay_depth);
-    else if (t->wfn)
-        std::snprintf(str, sizeof str, "wide_kernel<%d,%d>", t->var.T, t->var.J);
-    else
-        std::snprintf(str, sizeof str, "pivot_kernel<%d,%d,%d>", t->var.T, t->var.J, t->var.R);
+    const std::string str = p.shard_delayed ? p.shard_step.name + kname(",delay_depth:%d", t->d.delay_depth) : p.step.name;
     std::snprintf(buf, (size_t)len, "streaming=%s workgroups=%d resident=%s inplace=%s giveups=%lld resident_off_for=%d inplace_off_for=%d "
-                  "last_path=%s last_resident_launches=%lld node_fused_runs=%lld lock_giveups=%lld decide=pivot_kernel<%d,%d,%d> shard_sweep=%s launched=%s", str,
-                  t->nb, res, inp, (long long)t->giveups, t->ctx->resident ? t->ctx->resident_skip : -1,
+                  "last_path=%s last_resident_launches=%lld node_fused_runs=%lld lock_giveups=%lld decide=%s shard_sweep=%s launched=%s", str.c_str(),
+                  t->nb, res.c_str(), inp.c_str(), (long long)t->giveups, t->ctx->resident ? t->ctx->resident_skip : -1,
                   t->ctx->inplace ? t->ctx->inplace_skip : -1,
                   t->last_path == 1 ? "resident" : t->last_path == 2 ? "streaming" : t->last_path == 3 ? "resident+streaming"
                   : t->last_path == 4 ? "small" : t->last_path == 8 ? "inplace" : t->last_path == 10 ? "inplace+streaming"
                   : t->last_path == 9 ? "resident+inplace" : t->last_path == 11 ? "resident+inplace+streaming"
                   : t->last_path == 16 ? "generic" : "none",
                   (long long)(t->last_path & 9 ? t->last_launches : 0), (long long)t->node_fused_runs, (long long)t->ctx->lock_giveups,
-                  t->var.T, t->var.J, t->var.R, !t->dfn ? "none" : t->d.ext_sweep ? "launch" : "inline",
+                  p.decide.name.c_str(), !p.shard_delayed ? "none" : t->d.ext_sweep ? "launch" : "inline",
                   launched.empty() ? "none" : launched.c_str()); // (decide: the single-workgroup DECIDE launches of checkCycles on the launch-per-pivot path)
     return 0;
 }
@@ -1382,14 +1497,8 @@ static int32_t solve_generic(yalps_tableau *t, double precision, double maxPivot
     YState fin;
     for (;;) {
         if (checkCycles && hist_have + PAIRS > t->hist_cap) { // room for every pivot a batch can record
-            rc = grow_history(t, hist_have + PAIRS, hist_have);
+            rc = regrow_history(t, hist_have + PAIRS, hist_have);
             if (rc) return rc;
-            YConst hc;
-            HIP_TRY(hipMemcpy(&hc, t->d.cst, sizeof(YConst), hipMemcpyDeviceToHost));
-            hc.hist_cap = t->hist_cap;
-            hc.hist_leaving = t->hist[0];
-            hc.hist_entering = t->hist[1];
-            HIP_TRY(hipMemcpy(t->d.cst, &hc, sizeof(YConst), hipMemcpyHostToDevice));
         }
         for (int i = 0; i < PAIRS; i++) {
             generic_decide_kernel<<<dim3(1), dim3(1024), 0, s>>>(t->d);
@@ -1469,6 +1578,32 @@ static bool fits_small(const yalps_ctx *c, int32_t w, int32_t h) {
     return c->small && small_lds_bytes(w, h) <= SMALL_LDS_MAX;
 }
 
+// "An in-place kernel exists for this checkCycles": the one-sweep-per-pivot form, or the delayed form where only that has a check form.
+static bool has_inplace(const Plan &p, bool check) { return check ? (p.inplace[1].fn || p.delayed[1].fn) : p.inplace[0].fn != nullptr; }
+
+enum Family { RESIDENT, INPLACE, DELAYED };
+
+// Which persistent kernel the solve tries next (nullptr: none), given which paths are on: resident, then in place -- delayed
+// where that exists for this checkCycles, else one sweep per pivot.
+static Kernel *next_persistent(yalps_tableau *t, bool check, bool resident_on, bool inplace_on, Family *family) {
+    Plan &p = t->plan;
+    if (t->d.nshards != 1) return nullptr;
+    *family = RESIDENT;
+    if (resident_on && t->ctx->resident_skip == 0 && p.resident.fn) return &p.resident; // (checkCycles: one more exchange per pivot)
+    if (!inplace_on || t->ctx->inplace_skip != 0 || !has_inplace(p, check)) return nullptr;
+    *family = p.delayed[check].fn ? DELAYED : INPLACE; // stream3_kernel / stream2_kernel: several pivots per sweep
+    return *family == DELAYED ? &p.delayed[check] : &p.inplace[check];
+}
+
+// after an occupancy refusal: the family is not tried again on this tableau, in either check form
+static void drop_family(Plan &p, Family family) {
+    Kernel *forms = family == DELAYED ? p.delayed : p.inplace;
+    if (family == RESIDENT)
+        p.resident.fn = nullptr;
+    else
+        forms[0].fn = forms[1].fn = nullptr;
+}
+
 int32_t yalps_tableau_solve(yalps_tableau *t, double precision, double maxPivots, int32_t checkCycles,
                             double *result_out, int64_t *pivots_out, float *gpu_ms_out) {
     if (!t || t->height < 1) return fail(YALPS_E_ARG, "yalps_tableau_solve: no tableau uploaded");
@@ -1499,7 +1634,7 @@ int32_t yalps_tableau_solve(yalps_tableau *t, double precision, double maxPivots
     const bool resident_on = c->resident && (c->resident_skip == 0 || --c->resident_skip == 0);
     const bool inplace_on = c->inplace && (c->inplace_skip == 0 || --c->inplace_skip == 0);
     // (rows of 8194 .. 16385 columns: sweep_kernel where it applies, else the any-shape pair)
-    const bool sweep_ok = t->sweep && t->d.nshards == 1 && inplace_on && (checkCycles ? (t->svar_check.fn || t->svar2_check.fn) : t->svar.fn != nullptr);
+    const bool sweep_ok = t->plan.sweep && t->d.nshards == 1 && inplace_on && has_inplace(t->plan, checkCycles != 0);
     if (t->generic || (t->prefer_generic && t->d.nshards == 1 && !sweep_ok))
         return solve_generic(t, precision, maxPivots, checkCycles, result_out, pivots_out, gpu_ms_out);
     const int which = checkCycles ? 1 : 0;
@@ -1517,42 +1652,25 @@ int32_t yalps_tableau_solve(yalps_tableau *t, double precision, double maxPivots
     // (fall-back order: resident -> in place -> one launch per pivot; a path that fails is not tried again on this context)
     int64_t hist_have = 0; // checkCycles: pivots recorded in the current phase at the next launch's start
     for (int attempt = 0; attempt < 2 && !finished; attempt++) {
-        const bool persistent_ok = t->d.nshards == 1;
-        const bool use_resident = persistent_ok && resident_on && c->resident_skip == 0 && t->rvar.fn; // (checkCycles: one more exchange per pivot)
-        const bool use_stream = persistent_ok && !use_resident && inplace_on && c->inplace_skip == 0 &&
-                                (checkCycles ? (t->svar_check.fn || t->svar2_check.fn) : t->svar.fn != nullptr);
-        if (!use_resident && !use_stream) break;
-        const bool in_place = use_stream;
-        const bool delayed = in_place && (checkCycles ? t->svar2_check.fn : t->svar2.fn); // stream3_kernel / stream2_kernel: several pivots per sweep
+        Family family;
+        Kernel *next = next_persistent(t, checkCycles != 0, resident_on, inplace_on, &family);
+        if (!next) break;
+        Kernel &pv = *next; // (a record of the plan: the big-LDS mark made below stays with it)
+        const bool in_place = family != RESIDENT, delayed = family == DELAYED;
         if (in_place) t->last_delayed = delayed;
-        const RVariant &pv = delayed ? (checkCycles ? t->svar2_check : t->svar2)
-                             : in_place ? (checkCycles ? t->svar_check : t->svar) : t->rvar_tag.fn ? t->rvar_tag : t->rvar;
-        bool &sattr = delayed ? (checkCycles ? t->sattr2_check : t->sattr2) : checkCycles ? t->sattr_check : t->sattr;
-        const size_t shmem = delayed ? t->sshmem2 : in_place ? t->sshmem : t->rx_shmem ? t->rx_shmem : sizeof(int32_t) * 2 * (size_t)t->perm_len;
-        if (in_place ? !sattr : shmem != t->rshmem) {
-            if (shmem > 48 * 1024)
-                if (int rc2 = allow_big_lds(c->device, reinterpret_cast<const void *>(pv.fn))) return rc2;
-            if (in_place)
-                sattr = true;
-            else
-                t->rshmem = shmem;
-        }
+        const size_t shmem = in_place ? pv.lds : resident_lds(t);
+        if (int rc2 = need_lds(c, pv, shmem)) return rc2;
         // every workgroup of the grid must be resident at once: ask the runtime what fits (registers, LDS, waves) before
         // launching a grid that would wait for workgroups that cannot start
         {
             int per_cu = 0;
-            HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(pv.fn), pv.T, shmem));
+            HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, pv.fn, pv.lanes, shmem));
             if (per_cu < 1 || t->nb > c->num_cus * per_cu) {
                 if (!t->occupancy_warned)
-                    std::fprintf(stderr, "yalps_hip: %s<%d,%d,%d>: %d workgroups do not fit on %d CUs x %d; using the next path\n",
-                                 in_place ? "stream_kernel" : "resident_kernel", pv.T, pv.J, pv.R, t->nb, c->num_cus, per_cu);
+                    std::fprintf(stderr, "yalps_hip: %s: %d workgroups do not fit on %d CUs x %d; using the next path\n",
+                                 pv.name.c_str(), t->nb, c->num_cus, per_cu);
                 t->occupancy_warned = true;
-                if (delayed)
-                    t->svar2.fn = t->svar2_check.fn = nullptr;
-                else if (in_place)
-                    t->svar.fn = t->svar_check.fn = nullptr;
-                else
-                    t->rvar.fn = t->rvar_tag.fn = nullptr;
+                drop_family(t->plan, family);
                 continue;
             }
         }
@@ -1569,14 +1687,8 @@ int32_t yalps_tableau_solve(yalps_tableau *t, double precision, double maxPivots
             if (checkCycles) { // room for every pivot this launch can record (no pause inside a persistent launch)
                 const int64_t have = hist_have;
                 if (have + chunk > t->hist_cap) {
-                    rc = grow_history(t, have + chunk, have);
+                    rc = regrow_history(t, have + chunk, have);
                     if (rc) return rc;
-                    YConst hc;
-                    HIP_TRY(hipMemcpy(&hc, t->d.cst, sizeof(YConst), hipMemcpyDeviceToHost));
-                    hc.hist_cap = t->hist_cap;
-                    hc.hist_leaving = t->hist[0];
-                    hc.hist_entering = t->hist[1];
-                    HIP_TRY(hipMemcpy(t->d.cst, &hc, sizeof(YConst), hipMemcpyHostToDevice));
                 }
             }
             // the kernel rewrites the basis (and, in place, the tableau): keep the old ones until the launch is known good
@@ -1588,13 +1700,8 @@ int32_t yalps_tableau_solve(yalps_tableau *t, double precision, double maxPivots
                 if (!t->perm_backup) HIP_TRY(hipMalloc(&t->perm_backup, sizeof(int32_t) * 2 * (size_t)t->perm_cap));
                 HIP_TRY(hipMemcpyAsync(t->perm_backup, t->perm_block, sizeof(int32_t) * 2 * (size_t)t->perm_cap, hipMemcpyDeviceToDevice, s));
             }
-            if (in_place) {
-                const Desc &d = t->d;
-                HIP_TRY(hipMemcpyAsync(d.mat[t->cur ^ 1], d.mat[t->cur], sizeof(double) * (size_t)d.pitch * t->height,
-                                       hipMemcpyDeviceToDevice, s));
-                HIP_TRY(hipMemcpyAsync(d.rhs[t->cur ^ 1], d.rhs[t->cur], sizeof(double) * (size_t)t->height,
-                                       hipMemcpyDeviceToDevice, s));
-            }
+            if (in_place)
+                if (int rc2 = copy_buffer(t, t->cur)) return rc2;
             {
                 // A persistent kernel needs every workgroup of ITS grid on the chip.  Two of them from two contexts
                 // (threads) could each get half of the CUs and wait for the rest until their bounded spins give up:
@@ -1603,8 +1710,8 @@ int32_t yalps_tableau_solve(yalps_tableau *t, double precision, double maxPivots
                 DeviceLock one_grid_of_all_processes(c->lock_fd, c->lock_wait_ms);
                 lock_expired = !one_grid_of_all_processes.held;
                 if (!lock_expired) { // (else nothing of this launch is enqueued but the copies aside)
-                pv.fn<<<dim3(t->nb), dim3(pv.T), shmem, s>>>(t->d, parity, chunk);
-                note_launch(t, persistent_name(t, pv, in_place, delayed, checkCycles != 0));
+                pv.as<ResidentFn>()<<<dim3(t->nb), dim3(pv.lanes), shmem, s>>>(t->d, parity, chunk);
+                note_launch(t, pv.name);
                 t->last_path |= in_place ? 8 : 1;
                 t->last_launches++;
                 c->persistent_launches++;
@@ -1664,11 +1771,7 @@ int32_t yalps_tableau_solve(yalps_tableau *t, double precision, double maxPivots
                 HIP_TRY(hipMemcpy(&last, t->d.st + parity, sizeof(YState), hipMemcpyDeviceToHost));
                 t->cur = in_place ? last.mbuf ^ 1 : last.mbuf;
                 if (t->cur != 0) {
-                    const Desc &d = t->d;
-                    HIP_TRY(hipMemcpyAsync(d.mat[0], d.mat[1], sizeof(double) * (size_t)d.pitch * t->height,
-                                           hipMemcpyDeviceToDevice, s));
-                    HIP_TRY(hipMemcpyAsync(d.rhs[0], d.rhs[1], sizeof(double) * (size_t)t->height,
-                                           hipMemcpyDeviceToDevice, s));
+                    if (int rc2 = copy_buffer(t, 1)) return rc2;
                     t->cur = 0;
                 }
                 hist_have = last.hist_len;
@@ -1695,8 +1798,8 @@ int32_t yalps_tableau_solve(yalps_tableau *t, double precision, double maxPivots
         rc = ensure_graph(t, which);
         if (rc) return rc;
         t->last_path |= 2;
-        note_launch(t, launch_one_name(t, which == 0 ? MODE_FUSED : MODE_APPLY)); // (launch_batch: APPLY, DECIDE, APPLY, ...)
-        if (which == 1) note_launch(t, launch_one_name(t, MODE_DECIDE));
+        note_launch(t, t->plan.step.name); // (launch_batch: FUSED, or APPLY, DECIDE, APPLY, ...)
+        if (which == 1) note_launch(t, t->plan.decide.name);
     }
     // keep one batch in flight while the previous batch's state is inspected
     int issued = 0, checked = 0;
@@ -1726,14 +1829,8 @@ int32_t yalps_tableau_solve(yalps_tableau *t, double precision, double maxPivots
                 fin = now;
                 break;
             }
-            rc = grow_history(t, t->hist_cap * 2, now.hist_len);
+            rc = regrow_history(t, t->hist_cap * 2, now.hist_len);
             if (rc) return rc;
-            YConst hc;
-            HIP_TRY(hipMemcpy(&hc, t->d.cst, sizeof(YConst), hipMemcpyDeviceToHost));
-            hc.hist_cap = t->hist_cap;
-            hc.hist_leaving = t->hist[0];
-            hc.hist_entering = t->hist[1];
-            HIP_TRY(hipMemcpy(t->d.cst, &hc, sizeof(YConst), hipMemcpyHostToDevice));
             now.pause = 0;
             HIP_TRY(hipMemcpy(t->d.st, &now, sizeof(YState), hipMemcpyHostToDevice));
         }
@@ -1769,7 +1866,7 @@ static int32_t node_fused_solve(yalps_tableau *dst, const yalps_tableau *root, i
     if (!enabled || checkCycles || ncuts < 1 || !dst->fetch_col0 || !dst->ctl_block || !dst->perm_block || !root->perm_block ||
         dst->generic || dst->d.nshards != 1 || root->d.nshards != 1 || dst->d.w != root->d.w || dst->ctx != root->ctx ||
         (int64_t)root->height + ncuts > dst->d.hcap || !c->resident || c->resident_skip != 0 || c->resident_fault > 0 ||
-        !dst->rvar.fn || fits_small(c, dst->d.w, root->height + ncuts))
+        !dst->plan.resident.fn || fits_small(c, dst->d.w, root->height + ncuts))
         return 0;
     for (int32_t i = 0; i < ncuts; i++)
         if (cut_variable[i] < 0 || cut_variable[i] >= root->d.w + root->height)
@@ -1816,16 +1913,12 @@ static int32_t node_fused_solve(yalps_tableau *dst, const yalps_tableau *root, i
     std::memcpy(cuts, cut_value, sizeof(double) * (size_t)ncuts);
     std::memcpy(cuts + sizeof(double) * (size_t)ncuts, cut_sign, sizeof(int32_t) * (size_t)ncuts);
     std::memcpy(cuts + 12 * (size_t)ncuts, cut_variable, sizeof(int32_t) * (size_t)ncuts);
-    const RVariant &pv = dst->rvar_tag.fn ? dst->rvar_tag : dst->rvar;
-    const size_t shmem = dst->rx_shmem ? dst->rx_shmem : sizeof(int32_t) * 2 * (size_t)dst->perm_len;
-    if (shmem != dst->rshmem) {
-        if (shmem > 48 * 1024)
-            if (int rc2 = allow_big_lds(c->device, reinterpret_cast<const void *>(pv.fn))) return rc2;
-        dst->rshmem = shmem;
-    }
+    Kernel &pv = dst->plan.resident;
+    const size_t shmem = resident_lds(dst);
+    if (int rc2 = need_lds(c, pv, shmem)) return rc2;
     if (!dst->node_occupancy_ok) {
         int per_cu = 0;
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(pv.fn), pv.T, shmem));
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, pv.fn, pv.lanes, shmem));
         if (per_cu < 1 || dst->nb > c->num_cus * per_cu) return 0; // (the ordinary path reports it and moves on)
         dst->node_occupancy_ok = true;
     }
@@ -1848,8 +1941,8 @@ static int32_t node_fused_solve(yalps_tableau *dst, const yalps_tableau *root, i
                          PERSISTENT_RETRY_AFTER);
             return 0;
         }
-        pv.fn<<<dim3(dst->nb), dim3(pv.T), shmem, s>>>(dst->d, 0, c->resident_chunk);
-        note_launch(dst, persistent_name(dst, pv, false, false, checkCycles != 0));
+        pv.as<ResidentFn>()<<<dim3(dst->nb), dim3(pv.lanes), shmem, s>>>(dst->d, 0, c->resident_chunk);
+        note_launch(dst, pv.name);
         note_launch(dst, "node_finish_kernel");
         HIP_TRY(hipGetLastError());
         node_finish_kernel<<<dim3(8), dim3(256), 0, s>>>(dst->d, h, dst->perm_len, dst->perm_cap, (int)(16 + 2 * sizeof(YState)), dst->host_ctl,
@@ -1989,95 +2082,31 @@ int32_t yalps_tableau_set_shard(yalps_tableau *t, int32_t rank, int32_t nranks, 
     HIP_TRY(hipStreamSynchronize(s));
     t->perm_len = (int32_t)n;
     d.perm_len = t->perm_len;
-    t->rvar.fn = nullptr; // a shard is driven step by step
-    // rows wide enough for wide_kernel are swept in place (YALPS_HIP_SHARD_INPLACE=0: ping-pong as in round 1)
-    t->wfn_inplace = nullptr;
-    if (t->wfn && env_int("YALPS_HIP_SHARD_INPLACE", 1)) {
-        const bool nt = env_int("YALPS_HIP_SHARD_NT", sizeof(double) * (size_t)d.pitch * (size_t)t->height > SWEEP_BEYOND_CACHE ? 1 : 0) != 0;
-        for (const WInplace &v : kWideInplace)
-            if (v.T == t->var.T && v.J == t->var.J) {
-                t->wfn_inplace = v.fn[nt ? 1 : 0];
-                t->wT_inplace = v.launchT;
-                t->shard_step_name = kname("wide_kernel<%d,%d,inplace%s>", v.launchT, v.T * v.J / v.launchT, nt ? ",nt" : "");
-            }
-        if (t->wfn_inplace) {
-            if (t->wshmem > 48 * 1024)
-                if (int rc = allow_big_lds(t->ctx->device, reinterpret_cast<const void *>(t->wfn_inplace))) return rc;
-            if (!d.obj[0]) {
-                HIP_TRY(hipMalloc(&d.obj[0], sizeof(double) * 2 * (size_t)d.pitch));
-                d.obj[1] = d.obj[0] + d.pitch;
-            }
+    Plan &p = t->plan;
+    p.resident.fn = nullptr; // a shard is driven step by step
+    plan_shard(d.pitch, d.hcap, t->nb, t->height, p);
+    if (p.shard_step.fn) { // swept in place: the objective row's replicas
+        if (int rc = need_lds(t->ctx, p.shard_step, p.shard_step.lds)) return rc;
+        if (!d.obj[0]) {
+            HIP_TRY(hipMalloc(&d.obj[0], sizeof(double) * 2 * (size_t)d.pitch));
+            d.obj[1] = d.obj[0] + d.pitch;
         }
     }
-    // Delayed row updates (dshard_kernel.cuh): a pivot costs the shard its scalars, the sweep comes once per `depth` pivots.
-    // Shards swept in place with at least YALPS_HIP_DELAY_MIN_ROWS rows per workgroup; YALPS_HIP_SHARD_DELAY=0: one sweep per pivot.
-    t->dfn = nullptr;
-    t->xsweep_fn = nullptr;
-    {
-        const int rows_per_block = (d.hcap + t->nb - 1) / t->nb, units = d.pitch / 2;
-        int dJ = 0;
-        for (int cand : {1, 2, 4, 6, 8, 16})
-            if (!dJ && 512 * cand >= units) dJ = cand;
-        if (t->wfn_inplace && dJ && env_int("YALPS_HIP_SHARD_DELAY", 1) && rows_per_block >= env_int("YALPS_HIP_DELAY_MIN_ROWS", 4)) {
-            // (measured, us per pivot at depth 2 / 4 / 6 / 8: 2049 x 16385 73 / 53 / 48 / 46, 8193 x 16385 207 / 125 / 105 / 97:
-            // a launch-per-pivot step has a larger fixed part than stream3_kernel's, the deepest form wins everywhere)
-            // round 3: the sweep stages the pending rows in LDS one 1024-column panel at a time (panel_flush.cuh) -- up to 16
-            // pending pivots; the deepest form whose scalars + panel fit the LDS of a CU
-            // the sweep through LDS panels pays from DSHARD_PANEL_MIN_ROWS rows per workgroup on (below: the pending rows straight from L2,
-            // at most 8 pending pivots) -- YALPS_HIP_SHARD_PANEL=0|1 forces one or the other
-            const bool panel = env_int("YALPS_HIP_SHARD_PANEL", rows_per_block >= DSHARD_PANEL_MIN_ROWS ? 1 : 0) != 0;
-            // (measured, one rank, 16385 columns, us per pivot: 2049 rows -- 8 per workgroup -- straight from L2 48 at depth 8, panels 52;
-            // 4097 rows 63 / 59.5 at depth 8 / 16 from L2, panels 60; 8193 rows 91 from L2, panels 86 / 74 at depth 8 / 16; 16385 rows panels 102)
-            // (round 3, after the panel sweep lost its chains of round trips -- one rank, 16385 columns, us per pivot from L2 / through panels at
-            // depth 8, 12, 16: 2049 rows (8 per workgroup) 45.3 43.8 43.3 / 48.3 46.9 46.3; 4097 rows (16) 60.5 57.7 56.6 / 56.0 51.0 49.1;
-            // 6001 rows (24) 74.0 70.3 74.5 / 70.7 61.0 58.5)
-            const int depth_default = panel ? DSHARD_DEFAULT_DEPTH_PANEL : rows_per_block >= 8 ? 16 : DSHARD_DEFAULT_DEPTH;
-            int depth = std::min(DSHARD_MAXD, std::max(2, env_int("YALPS_HIP_DELAY_DEPTH", depth_default)));
-            auto lds_of = [&](int dep) {
-                return sizeof(double) * (2 * (size_t)dep + 2) * (size_t)rows_per_block + 3 * sizeof(int32_t) * (((size_t)rows_per_block + 3) / 4 * 4) +
-                       (panel ? sizeof(double) * (size_t)dep * 2 * DSHARD_PANEL_UNITS : 0);
-            };
-            while (depth > 2 && lds_of(depth) > 150 * 1024) depth--;
-            const bool nt = env_int("YALPS_HIP_SHARD_NT", sizeof(double) * (size_t)d.pitch * (size_t)t->height > SWEEP_BEYOND_CACHE ? 1 : 0) != 0;
-            const size_t lds = lds_of(depth);
-            if (lds <= 150 * 1024)
-                for (const RVariant &v : kDshard)
-                    if (v.T == 512 && v.J == dJ && v.R == ((nt ? 1 : 0) | (panel ? 2 : 0))) t->dfn = reinterpret_cast<KernelFn>(v.fn);
-            if (t->dfn) {
-                if (lds > 48 * 1024)
-                    if (int rc = allow_big_lds(t->ctx->device, reinterpret_cast<const void *>(t->dfn))) return rc;
-                t->dshmem = lds;
-                t->dJ = dJ;
-                t->dnt = nt ? 1 : 0;
-                t->dpanel = panel ? 1 : 0;
-                t->shard_step_name = kname("dshard_kernel<512,%d%s%s>", dJ, nt ? ",nt" : "", panel ? ",panel" : "");
-                d.delay_depth = depth;
-                // the sweep as a launch of its own, rows mapped to workgroups by (panel, row block): one fill per workgroup, no barrier
-                // between its waves afterwards -- whatever the rows per workgroup of the step kernel (YALPS_HIP_SHARD_XSWEEP=0: the step kernel sweeps)
-                // Measured, one rank, 16385 columns, us per pivot with the sweep inside the step kernel / as its own launch: 2049 rows (8 per
-                // workgroup) 42.9 / 38.7, 4097 (16) 49.6 / 46.6, 8193 (32) 61.2 / 63.0, 16385 (64) 93.3 / 95.8 (the launch sweeps at 3.6-3.9 TB/s
-                // whatever the rows; a row-major copy of the coefficients for it -- one cache line per row instead of 32 lines 131 KB apart per pair of
-                // rows -- changed nothing: 96.0 / 62.3 / 46.3 / 39.2) -- hence below 24 rows per workgroup.
-                t->xsweep_fn = env_int("YALPS_HIP_SHARD_XSWEEP", rows_per_block < DSHARD_XSWEEP_BELOW_ROWS ? 1 : 0) ? yalps_dshard_sweep_fn(nt ? 1 : 0) : nullptr;
-                if (t->xsweep_fn) {
-                    const int npan = (d.pitch / 2 + DSHARD_PANEL_UNITS - 1) / DSHARD_PANEL_UNITS;
-                    t->xsweep_grid = npan * std::max(1, 256 / npan);
-                    t->xsweep_lds = sizeof(double) * 2 * DSHARD_PANEL_UNITS * (size_t)depth;
-                    if (int rc = allow_big_lds(t->ctx->device, t->xsweep_fn)) return rc;
-                }
-                if (t->dsh_block) HIP_TRY(hipFree(t->dsh_block));
-                t->dsh_block = nullptr;
-                const size_t hc = ((size_t)d.hcap + 1) / 2 * 2; // (16-byte parts)
-                const size_t doubles = (size_t)depth * d.pitch + 2 * (size_t)depth * hc + hc;
-                HIP_TRY(hipMalloc(&t->dsh_block, sizeof(double) * doubles + 2 * sizeof(DelayState)));
-                HIP_TRY(hipMemsetAsync(t->dsh_block, 0, sizeof(double) * doubles + 2 * sizeof(DelayState), s));
-                d.dpend = static_cast<double *>(t->dsh_block);
-                d.dcolv = d.dpend + (size_t)depth * d.pitch;
-                d.dnqv = d.dcolv + (size_t)depth * hc;
-                d.dlav = d.dnqv + (size_t)depth * hc;
-                d.dstate = reinterpret_cast<DelayState *>(d.dlav + hc);
-            }
-        }
+    if (p.shard_delayed) { // dshard_kernel's arrays
+        const int depth = d.delay_depth = p.delay_depth;
+        if (p.shard_sweep.fn)
+            if (int rc = allow_big_lds(t->ctx->device, p.shard_sweep.fn)) return rc;
+        if (t->dsh_block) HIP_TRY(hipFree(t->dsh_block));
+        t->dsh_block = nullptr;
+        const size_t hc = ((size_t)d.hcap + 1) / 2 * 2; // (16-byte parts)
+        const size_t doubles = (size_t)depth * d.pitch + 2 * (size_t)depth * hc + hc;
+        HIP_TRY(hipMalloc(&t->dsh_block, sizeof(double) * doubles + 2 * sizeof(DelayState)));
+        HIP_TRY(hipMemsetAsync(t->dsh_block, 0, sizeof(double) * doubles + 2 * sizeof(DelayState), s));
+        d.dpend = static_cast<double *>(t->dsh_block);
+        d.dcolv = d.dpend + (size_t)depth * d.pitch;
+        d.dnqv = d.dcolv + (size_t)depth * hc;
+        d.dlav = d.dnqv + (size_t)depth * hc;
+        d.dstate = reinterpret_cast<DelayState *>(d.dlav + hc);
     }
     if (!t->cyc_block) {
         HIP_TRY(hipMalloc(&t->cyc_block, 16));
@@ -2103,14 +2132,7 @@ constexpr int64_t SHARD_HIST_MARGIN = 8192;
 static int shard_hist_reserve(yalps_tableau *t, int64_t have) {
     if (!t->shard_check || have + SHARD_HIST_MARGIN <= t->hist_cap) return 0;
     HIP_TRY(hipStreamSynchronize(t->ctx->stream));
-    if (int rc = grow_history(t, have + 2 * SHARD_HIST_MARGIN, have)) return rc;
-    YConst hc;
-    HIP_TRY(hipMemcpy(&hc, t->d.cst, sizeof(YConst), hipMemcpyDeviceToHost));
-    hc.hist_cap = t->hist_cap;
-    hc.hist_leaving = t->hist[0];
-    hc.hist_entering = t->hist[1];
-    HIP_TRY(hipMemcpy(t->d.cst, &hc, sizeof(YConst), hipMemcpyHostToDevice));
-    return 0;
+    return regrow_history(t, have + 2 * SHARD_HIST_MARGIN, have);
 }
 
 int32_t yalps_shard_begin(yalps_tableau *t, double precision, double maxPivots, int32_t checkCycles) {
@@ -2124,14 +2146,14 @@ int32_t yalps_shard_begin(yalps_tableau *t, double precision, double maxPivots, 
     int rc = init_state(t, precision, maxPivots, checkCycles);
     if (rc) return rc;
     t->launched.clear();
-    note_launch(t, launch_one_name(t, MODE_FUSED));
+    note_launch(t, t->plan.step.name);
     launch_one(t, 0, MODE_FUSED, 0); // bootstrap scan: emits this rank's first partials
     HIP_TRY(hipGetLastError());
     t->shard_parity = 1;
-    if (t->dfn) HIP_TRY(hipMemsetAsync(t->d.dstate, 0, 2 * sizeof(DelayState), t->ctx->stream)); // nothing pending
+    if (t->plan.shard_delayed) HIP_TRY(hipMemsetAsync(t->d.dstate, 0, 2 * sizeof(DelayState), t->ctx->stream)); // nothing pending
     t->d.ext_sweep = 0; // (yalps_shard_run turns the sweep launch on: it knows the batch length)
     t->shard_pend = 0;
-    if (t->wfn_inplace) // (the scan left the tableau in buffer 1 and the partials in set 1: the first in-place launch reads replica 1)
+    if (t->plan.shard_step.fn) // (the scan left the tableau in buffer 1 and the partials in set 1: the first in-place launch reads replica 1)
         HIP_TRY(hipMemcpyAsync(t->d.obj[1], t->d.mat[1], sizeof(double) * (size_t)t->d.pitch, hipMemcpyDeviceToDevice, t->ctx->stream));
     return 0;
 }
@@ -2144,7 +2166,7 @@ static int shard_select_blocks(const yalps_tableau *t) { // 16-byte units of the
 // this rank's candidates + their rows into its slot of the all-gather (delayed row updates: with the pending pivots applied)
 static void launch_select(yalps_tableau *t, double *send) {
     using SelectFn = void (*)(Desc, int, double *);
-    if (t->dfn) {
+    if (t->plan.shard_delayed) {
         const int lanes = t->nb <= 256 ? 256 : 1024; // (dshard_select_kernel<256>: four times the workgroups)
         note_launch(t, kname("dshard_select_kernel<%d>", lanes));
         const int blocks = std::min(256, std::max(1, (t->d.pitch + lanes - 1) / lanes));
@@ -2350,9 +2372,9 @@ static int shard_step(yalps_tableau *t, yalps_comm *c, size_t slot) {
     c->collectives++;
     launch_shard(t, c->recv);
     if (t->d.ext_sweep && ++t->shard_pend == t->d.delay_depth) { // `depth` pivots pending behind this step: the sweep, a launch of its own
-        using SweepFn = void (*)(Desc, int);
-        note_launch(t, t->dnt ? "dshard_sweep_kernel<nt>" : "dshard_sweep_kernel");
-        reinterpret_cast<SweepFn>(const_cast<void *>(t->xsweep_fn))<<<dim3(t->xsweep_grid), dim3(512), t->xsweep_lds, t->ctx->stream>>>(t->d, t->shard_parity);
+        const Kernel &sweep = t->plan.shard_sweep;
+        note_launch(t, sweep.name);
+        sweep.as<void (*)(Desc, int)>()<<<dim3(t->plan.shard_sweep_grid), dim3(sweep.lanes), sweep.lds, t->ctx->stream>>>(t->d, t->shard_parity);
         t->shard_pend = 0;
     }
     t->shard_parity ^= 1;
@@ -2374,7 +2396,7 @@ int32_t yalps_shard_run(yalps_tableau *t, yalps_comm *c, double precision, doubl
     check_every &= ~1; // (even: the launch parity is back where it started after a batch, so one captured batch serves every replay)
     if (int rc = yalps_shard_begin(t, precision, maxPivots, checkCycles)) return rc;
     // (the host counts the pending pivots: a batch has to end with none of them pending for one captured batch to serve every replay)
-    t->d.ext_sweep = (t->dfn && t->xsweep_fn && check_every % t->d.delay_depth == 0) ? 1 : 0;
+    t->d.ext_sweep = (t->plan.shard_delayed && t->plan.shard_sweep.fn && check_every % t->d.delay_depth == 0) ? 1 : 0;
     if (gpu_ms_out) HIP_TRY(hipEventRecord(ctx->ev0, s));
     // The first batch runs eagerly (RCCL sets its channels up on first use); from the second on the batch is ONE
     // hipGraph replay where the transport can be captured (RCCL's collectives can; the host transport waits per pivot).
