@@ -1,4 +1,4 @@
-"""ctypes binding of libyalps_hip.so (include/yalps_hip.h).
+"""ctypes binding of libyalps_hip.so (include/yalps_hip.h) and libyalps_lpbatch.so (include/yalps_lpbatch.h).
 
 There is no CPU path: if the library is missing, or no gfx950 device is usable,
 every call raises.  Nothing here imports the oracle.
@@ -26,6 +26,14 @@ SYMBOLS = (
     "yalps_tableau_debug_stamps", "yalps_tableau_padding_check", "yalps_comm_unique_id", "yalps_comm_create", "yalps_comm_create_host", "yalps_comm_destroy",
     "yalps_comm_info", "yalps_shard_run",
 )
+# every symbol include/yalps_lpbatch.h declares (a library of its own, loaded on first use)
+LPBATCH_LIB_PATH = os.environ.get("YALPS_LPBATCH_LIB") or os.path.join(HERE, "libyalps_lpbatch.so")
+SYMBOLS_LPBATCH = (
+    "yalps_lpbatch_last_error", "yalps_lpbatch_create", "yalps_lpbatch_destroy", "yalps_lpbatch_class", "yalps_lpbatch_lds_bytes",
+    "yalps_lpbatch_validate", "yalps_lpbatch_solve", "yalps_lpbatch_solution", "yalps_lpbatch_tableau", "yalps_lpbatch_info",
+)
+LPBATCH_MAX_BYTES = 4 << 20  # YALPS_LPBATCH_MAX_BYTES
+LPBATCH_HBM_CLASS = 4        # yalps_lpbatch_class: 0..3 the LDS form, 4 the HBM form
 
 
 class NativeError(RuntimeError):
@@ -478,3 +486,148 @@ def dense_lp_rows(M, N, seed, row_begin, row_end):
 
 def round_to_precision(x, precision):
     return lib().yalps_round_to_precision(x, precision)
+
+
+_lpbatch_lib = None
+
+
+def lpbatch_lib():
+    global _lpbatch_lib
+    if _lpbatch_lib is None:
+        if not os.path.exists(LPBATCH_LIB_PATH):
+            raise NativeError(f"{LPBATCH_LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
+                              "(there is no CPU fallback)")
+        L = C.CDLL(LPBATCH_LIB_PATH)
+        vp, i32, f64p = C.c_void_p, C.c_int32, C.POINTER(C.c_double)
+        L.yalps_lpbatch_last_error.restype = C.c_char_p
+        L.yalps_lpbatch_create.restype = i32
+        L.yalps_lpbatch_create.argtypes = [i32, vp, C.POINTER(vp)]
+        L.yalps_lpbatch_destroy.restype = None
+        L.yalps_lpbatch_destroy.argtypes = [vp]
+        L.yalps_lpbatch_class.restype = i32
+        L.yalps_lpbatch_class.argtypes = [i32, i32]
+        L.yalps_lpbatch_lds_bytes.restype = C.c_int64
+        L.yalps_lpbatch_lds_bytes.argtypes = [i32, i32]
+        L.yalps_lpbatch_validate.restype = i32
+        L.yalps_lpbatch_validate.argtypes = [i32, vp, vp, vp, vp, vp]
+        L.yalps_lpbatch_solve.restype = i32
+        L.yalps_lpbatch_solve.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, C.POINTER(C.c_float)]
+        L.yalps_lpbatch_solution.restype = i32
+        L.yalps_lpbatch_solution.argtypes = [vp, i32, vp, vp, vp]
+        L.yalps_lpbatch_tableau.restype = i32
+        L.yalps_lpbatch_tableau.argtypes = [vp, i32, vp]
+        L.yalps_lpbatch_info.restype = i32
+        L.yalps_lpbatch_info.argtypes = [vp, C.c_char_p, i32]
+        _lpbatch_lib = L
+    return _lpbatch_lib
+
+
+def lpbatch_check(rc):
+    if rc < 0:
+        raise NativeError("yalps_lpbatch error %d: %s" % (rc, lpbatch_lib().yalps_lpbatch_last_error().decode()))
+    return rc
+
+
+def lpbatch_class(width, height):
+    """Size class of a width x height LP: 0..3 the LDS form, 4 the HBM form, -1 not batchable (host only)."""
+    return lpbatch_lib().yalps_lpbatch_class(int(width), int(height))
+
+
+def lpbatch_lds_bytes(width, height):
+    return lpbatch_lib().yalps_lpbatch_lds_bytes(int(width), int(height))
+
+
+class PackedLps:
+    """A heterogeneous batch as yalps_lpbatch_solve takes it: per LP width, height and options, all cells in three arrays."""
+
+    def __init__(self, lps):
+        """lps: a sequence of (width, height, row, col, val, precision, max_pivots, check_cycles)."""
+        n = len(lps)
+        self.count = n
+        self.width = np.fromiter((lp[0] for lp in lps), np.int32, n)
+        self.height = np.fromiter((lp[1] for lp in lps), np.int32, n)
+        self.offsets = np.zeros(n + 1, np.int64)
+        self.offsets[1:] = np.cumsum([lp[2].size for lp in lps])
+        cat = lambda k, dt: np.ascontiguousarray(np.concatenate([lp[k] for lp in lps]), dt) if n else np.zeros(0, dt)
+        self.row, self.col, self.val = cat(2, np.int32), cat(3, np.int32), cat(4, np.float64)
+        assert self.row.size == self.col.size == self.val.size == self.offsets[-1]
+        self.precision = np.fromiter((lp[5] for lp in lps), np.float64, n)
+        self.max_pivots = np.fromiter((float(lp[6]) for lp in lps), np.float64, n)
+        self.check_cycles = np.fromiter((int(bool(lp[7])) for lp in lps), np.int32, n)
+
+    def validate(self):
+        """The argument checks of yalps_lpbatch_solve, on the host (raises NativeError naming the LP)."""
+        lpbatch_check(lpbatch_lib().yalps_lpbatch_validate(self.count, self.width.ctypes.data, self.height.ctypes.data,
+                                                           self.offsets.ctypes.data, self.row.ctypes.data, self.col.ctypes.data))
+
+
+def dense_cells(matrix, width, height):
+    """(row, col, val) of a dense row-major tableau: every entry whose bits are not +0.0 (a -0.0 is a written cell)."""
+    idx = np.flatnonzero(np.ascontiguousarray(matrix[:width * height]).view(np.int64))
+    return (idx // width).astype(np.int32), (idx % width).astype(np.int32), np.ascontiguousarray(matrix[idx])
+
+
+class LpBatch:
+    """Many independent LPs per call, one workgroup per LP (yalps_lpbatch_*).  Belongs to one thread at a time."""
+
+    def __init__(self, device=0, stream=None):
+        self.handle = C.c_void_p()
+        lpbatch_check(lpbatch_lib().yalps_lpbatch_create(device, C.c_void_p(stream) if stream is not None else None,
+                                                         C.byref(self.handle)))
+        self.packed = None
+
+    def solve(self, lps, keep_tableaux=False):
+        """lps: a PackedLps or the sequence it is made from.  Returns (status names, results, pivot counts, gpu_ms)."""
+        p = lps if isinstance(lps, PackedLps) else PackedLps(lps)
+        n = p.count
+        st, res, piv, ms = np.empty(n, np.int32), np.empty(n, np.float64), np.empty(n, np.int64), C.c_float()
+        self.packed = None
+        lpbatch_check(lpbatch_lib().yalps_lpbatch_solve(
+            self.handle, n, p.width.ctypes.data, p.height.ctypes.data, p.offsets.ctypes.data, p.row.ctypes.data,
+            p.col.ctypes.data, p.val.ctypes.data, p.precision.ctypes.data, p.max_pivots.ctypes.data, p.check_cycles.ctypes.data,
+            int(bool(keep_tableaux)), st.ctypes.data, res.ctypes.data, piv.ctypes.data, C.byref(ms)))
+        self.packed = p
+        return [STATUS[k] for k in st], res, piv, ms.value
+
+    def _shape(self, i):
+        if self.packed is None or not 0 <= i < self.packed.count:
+            raise NativeError("LpBatch: no such LP in the last solve: %r" % (i,))
+        return int(self.packed.width[i]), int(self.packed.height[i])
+
+    def solution(self, i):
+        """(col0, positionOfVariable, variableAtPosition) of LP i of the last solve."""
+        w, h = self._shape(i)
+        col0 = np.empty(h, np.float64)
+        pos, var = np.empty(w + h, np.int32), np.empty(w + h, np.int32)
+        lpbatch_check(lpbatch_lib().yalps_lpbatch_solution(self.handle, i, col0.ctypes.data, pos.ctypes.data, var.ctypes.data))
+        return col0, pos, var
+
+    def tableau(self, i):
+        """The whole final matrix of LP i of the last solve (solve(..., keep_tableaux=True)), flat row-major."""
+        w, h = self._shape(i)
+        m = np.empty(w * h, np.float64)
+        lpbatch_check(lpbatch_lib().yalps_lpbatch_tableau(self.handle, i, m.ctypes.data))
+        return m
+
+    def info(self):
+        """{"launches": n, "reruns": n, "rerun_lps": [...], "kernels": [{kernel, class, lps, grid, lds, pass, hist_cap}], "text"}"""
+        buf = C.create_string_buffer(1 << 12)
+        need = lpbatch_check(lpbatch_lib().yalps_lpbatch_info(self.handle, buf, len(buf)))
+        if need >= len(buf):  # (the text names every rerun LP: as long as the batch makes it)
+            buf = C.create_string_buffer(need + 1)
+            lpbatch_check(lpbatch_lib().yalps_lpbatch_info(self.handle, buf, len(buf)))
+        text = buf.value.decode()
+        lines = text.splitlines()
+        head = dict(kv.split("=", 1) for kv in lines[0].split()) if lines else {}
+        ids = head.get("rerun_lps", "[]").strip("[]")
+        kernels = []
+        for line in lines[1:]:
+            kv = dict(x.split("=", 1) for x in line.split())
+            kernels.append({k: (v if k == "kernel" else int(v)) for k, v in kv.items()})
+        return {"launches": int(head.get("launches", 0)), "reruns": int(head.get("reruns", 0)),
+                "rerun_lps": [int(x) for x in ids.split(",") if x], "kernels": kernels, "text": text}
+
+    def close(self):
+        if self.handle:
+            lpbatch_lib().yalps_lpbatch_destroy(self.handle)
+            self.handle = C.c_void_p()

@@ -1,6 +1,7 @@
 """Builds the native pieces in-tree (gfx950 only).  Used by __graft_entry__.build().
 
   yalps_amd/libyalps_hip.so   HIP kernels + C ABI (include/yalps_hip.h)      hipcc
+  yalps_amd/libyalps_lpbatch.so   batches of independent LPs (include/yalps_lpbatch.h)   hipcc
   yalps_amd/napi/yalps_napi.node  thin N-API shim over the C ABI (optional)  g++
 
 The .so files are git-ignored but travel to the GPU box with the tree.
@@ -19,7 +20,12 @@ HIP_SRC = os.path.join(CSRC, "yalps_hip.hip")  # host side + C ABI + the launch-
 # the persistent kernels' instantiations, one translation unit per group: compiled side by side (the device compile of
 # ~40 register-heavy kernels in one unit took 2.5 minutes)
 HIP_UNITS = [HIP_SRC] + [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.startswith("persistent_") and f.endswith(".hip")]
-HIP_DEPS = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith((".cuh", ".inc", ".h"))]
+HIP_DEPS = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith((".cuh", ".inc", ".h")) and not f.startswith("lp_batch")]
+# the batch library: one translation unit of its own around the shared workgroup loop, never linked into libyalps_hip.so
+LIB_LPBATCH = os.path.join(HERE, "libyalps_lpbatch.so")
+LPBATCH_SRC = os.path.join(CSRC, "lp_batch.hip")
+LPBATCH_DEPS = [os.path.join(CSRC, f) for f in ("lp_batch_kernel.cuh", "wg_simplex.cuh", "common.cuh")]
+LPBATCH_HEADER = os.path.join(ROOT, "include", "yalps_lpbatch.h")
 OBJ_DIR = os.path.join(HERE, "build")
 HEADER = os.path.join(ROOT, "include", "yalps_hip.h")
 NAPI_SRC = os.path.join(HERE, "napi", "yalps_napi.cc")
@@ -74,10 +80,13 @@ def kernel_metadata(lib=LIB):
 # Kernels whose rows / tableaux live in registers or LDS behind hand-written sc1 loads and stores: built without
 # scratch and without accumulator registers, or not at all.  (Two instantiations that broke this rule computed wrong
 # rows on the GPU -- DESIGN.md 4.7 -- so the rule is part of the build, not of an optional test.)
+# ("batch_kernel" also matches libyalps_lpbatch.so's lp_batch_kernel.)
 NO_SCRATCH = ("dshard_kernel", "dshard_select_kernel", "dshard_sweep_kernel", "small_kernel", "batch_kernel", "assemble", "resident_kernel", "resident2_kernel", "stream_kernel", "stream2_kernel", "stream3_kernel", "sweep_kernel")
 
 
 def check_register_budgets(lib=LIB, min_resident=15):
+    """min_resident=0: a library without the register-resident kernels (libyalps_lpbatch.so); the no-scratch rule holds as it is,
+    and the kernels under it may not use accumulator registers either."""
     ks = kernel_metadata(lib)
     resident = {k: v for k, v in ks.items() if "resident_kernel" in k or "resident2_kernel" in k}
     bad = []
@@ -88,6 +97,11 @@ def check_register_budgets(lib=LIB, min_resident=15):
             bad.append("%s: vgpr_count %s agpr_count %s" % (name, md["vgpr_count"], md["agpr_count"]))
         if any(tag in name for tag in NO_SCRATCH) and int(md["private_segment_fixed_size"]) != 0:
             bad.append("%s: private_segment_fixed_size %s (scratch)" % (name, md["private_segment_fixed_size"]))
+        if "lp_batch_kernel" in name and int(md["agpr_count"]) != 0:
+            bad.append("%s: agpr_count %s" % (name, md["agpr_count"]))
+        # its dynamic LDS block (tableau and pivot row, swept 16 bytes at a time) starts where the static LDS ends
+        if "lp_batch_kernel" in name and int(md["group_segment_fixed_size"]) % 16 != 0:
+            bad.append("%s: group_segment_fixed_size %s is not a multiple of 16 (misaligned 128-bit LDS accesses)" % (name, md["group_segment_fixed_size"]))
     if bad and os.environ.get("YALPS_BUILD_ALLOW_SCRATCH") == "1":  # (experiments only: a same-box A/B of a form that does not fit yet)
         print("register budget violated (YALPS_BUILD_ALLOW_SCRATCH=1: building anyway):\n  " + "\n  ".join(bad))
         return ks
@@ -130,6 +144,25 @@ def build_hip(force=False, verbose=False, stamps=False):
     return lib_out
 
 
+def build_lpbatch(force=False, verbose=False):
+    """libyalps_lpbatch.so: lp_batch.hip alone (it includes common.cuh / wg_simplex.cuh itself), same flags as the main library."""
+    if not force and not _stale(LIB_LPBATCH, LPBATCH_HEADER, LPBATCH_SRC, *LPBATCH_DEPS):
+        return LIB_LPBATCH
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    os.makedirs(OBJ_DIR, exist_ok=True)
+    obj = os.path.join(OBJ_DIR, "lp_batch.o")
+    for cmd in ([hipcc, *HIPCC_FLAGS, "-c", "-o", obj, LPBATCH_SRC],
+                [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB_LPBATCH + ".tmp", obj]):
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        subprocess.run(cmd, check=True)
+    ks = check_register_budgets(LIB_LPBATCH + ".tmp", min_resident=0)
+    if not any("lp_batch_kernel" in k for k in ks):
+        raise RuntimeError("no lp_batch_kernel in the code object of %s" % LIB_LPBATCH)
+    os.replace(LIB_LPBATCH + ".tmp", LIB_LPBATCH)
+    return LIB_LPBATCH
+
+
 def build_napi(force=False, verbose=False):
     """The Node addon; skipped (returns None) where node's headers are absent."""
     inc = "/usr/include/node"
@@ -151,4 +184,5 @@ if __name__ == "__main__":
         print(build_hip(verbose=True, stamps=True))
         raise SystemExit(0)
     print(build_hip(force=True, verbose=True))
+    print(build_lpbatch(force=True, verbose=True))
     print(build_napi(force=True, verbose=True))

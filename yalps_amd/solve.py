@@ -6,6 +6,7 @@ hot path -- `simplex(tableau, options)`, src/simplex.ts:144 -- is libyalps_hip.s
 CPU fallback: without the HIP library and a gfx950 device `solve` raises.
 """
 import math
+import threading
 
 from . import _native
 from .branch_and_cut import branch_and_cut
@@ -181,3 +182,67 @@ def solve(model, options=None, node_batch=None, stats=None, sparse=True, device_
     if node_batch is None:
         node_batch = 32 if native else 0
     return _solve_with(hip_simplex, model, options, node_batch, stats, sparse, device_nodes, native)
+
+
+_lpbatch = None  # the process's LpBatch: stream, events and device buffers are kept and grown between solve_many calls
+_lpbatch_lock = threading.Lock()  # (a handle belongs to one thread at a time)
+
+
+def lpbatch_simplex(tableaux, options, stats=None):
+    """The batched backend of solve_many: every tableau (built with sparse=True, no dense matrix) through ONE
+    yalps_lpbatch_solve; column 0 and the permutations land in the tableaux as hip_simplex leaves them.
+    Returns [(status, result)]."""
+    global _lpbatch
+    with _lpbatch_lock:
+        if _lpbatch is None:
+            _lpbatch = _native.LpBatch(0)
+        batch = _lpbatch
+        statuses, results, _, _ = batch.solve(
+            [(t.width, t.height, *t.cells, o["precision"], o["maxPivots"], o["checkCycles"]) for t, o in zip(tableaux, options)])
+        for i, t in enumerate(tableaux):
+            t.col0, t.position_of_variable, t.variable_at_position = batch.solution(i)
+        if stats is not None:
+            info = batch.info()
+            stats.update(launches=info["launches"], reruns=info["reruns"], kernels=info["kernels"])
+    return [(s, float(r)) for s, r in zip(statuses, results)]
+
+
+def _solve_many_with(batch_simplex, solve_one, models, options=None, stats=None):
+    """solve_many with both backends as parameters (tests drive the routing and the marshalling with the CPU oracle):
+    batch_simplex(tableaux, options, stats) -> [(status, result)] for the models without integers whose tableau is at most
+    NODE_BATCH_MAX_BYTES, solve_one(model, options) for every other model (integers, larger LPs), results in input order."""
+    models = list(models)
+    opts = list(options) if isinstance(options, (list, tuple)) else [options] * len(models)
+    if len(opts) != len(models):
+        raise ValueError("solve_many: %d models but %d option sets" % (len(models), len(opts)))
+    out = [None] * len(models)
+    batched = []  # (index, tabmod, merged options)
+    routed = {"batched": 0, "milp": 0, "large": 0}
+    for i, (model, o) in enumerate(zip(models, opts)):
+        tabmod = tableau_model(model, sparse=True)
+        t = tabmod.tableau
+        if tabmod.integers or 8 * t.width * t.height > NODE_BATCH_MAX_BYTES:
+            routed["milp" if tabmod.integers else "large"] += 1
+            out[i] = solve_one(model, o)
+            continue
+        opt = dict(_DEFAULTS)
+        if o:
+            opt.update({k: v for k, v in o.items() if v is not None})
+        batched.append((i, tabmod, opt))
+    routed["batched"] = len(batched)
+    if stats is not None:
+        stats.update(routed)
+    if batched:
+        results = batch_simplex([b[1].tableau for b in batched], [b[2] for b in batched], stats)
+        for (i, tabmod, opt), (status, result) in zip(batched, results):
+            out[i] = solution(tabmod, status, result, opt)
+    return out
+
+
+def solve_many(models, options=None, stats=None):
+    """[solve(m, o) for m, o in zip(models, options)] -- same dicts, same order -- with every model that has no integer
+    variables and a tableau of at most 4 MiB solved in ONE batched GPU call (one workgroup per LP, yalps_lpbatch_solve).
+    `options` is one dict for all models or one per model.  Models with integers and larger LPs go through solve() one
+    by one.  stats (a dict, optional) receives how many models went which way ("batched", "milp", "large") and the
+    batch's launches."""
+    return _solve_many_with(lpbatch_simplex, solve, models, options, stats)
