@@ -1,4 +1,5 @@
-"""ctypes binding of libyalps_hip.so (include/yalps_hip.h) and libyalps_lpbatch.so (include/yalps_lpbatch.h).
+"""ctypes binding of libyalps_hip.so (include/yalps_hip.h), libyalps_lpbatch.so (include/yalps_lpbatch.h) and
+libyalps_milpbatch.so (include/yalps_milpbatch.h).
 
 There is no CPU path: if the library is missing, or no gfx950 device is usable,
 every call raises.  Nothing here imports the oracle.
@@ -33,6 +34,14 @@ SYMBOLS_LPBATCH = (
     "yalps_lpbatch_validate", "yalps_lpbatch_solve", "yalps_lpbatch_solution", "yalps_lpbatch_tableau", "yalps_lpbatch_info",
 )
 LPBATCH_MAX_BYTES = 4 << 20  # YALPS_LPBATCH_MAX_BYTES
+# every symbol include/yalps_milpbatch.h declares (a third library, loaded on first use)
+MILPBATCH_LIB_PATH = os.environ.get("YALPS_MILPBATCH_LIB") or os.path.join(HERE, "libyalps_milpbatch.so")
+SYMBOLS_MILPBATCH = (
+    "yalps_milpbatch_last_error", "yalps_milpbatch_create", "yalps_milpbatch_destroy", "yalps_milpbatch_roots", "yalps_milpbatch_root",
+    "yalps_milpbatch_nodes", "yalps_milpbatch_validate_nodes", "yalps_milpbatch_node", "yalps_milpbatch_node_tableau",
+    "yalps_milpbatch_solve", "yalps_milpbatch_validate", "yalps_milpbatch_solution", "yalps_milpbatch_search", "yalps_milpbatch_info",
+)
+MILPBATCH_MAX_BYTES = 4 << 20  # YALPS_MILPBATCH_MAX_BYTES: a node's tableau, root height + cuts rows
 LPBATCH_HBM_CLASS = 4        # yalps_lpbatch_class: 0..3 the LDS form, 4 the HBM form
 
 
@@ -631,3 +640,300 @@ class LpBatch:
         if self.handle:
             lpbatch_lib().yalps_lpbatch_destroy(self.handle)
             self.handle = C.c_void_p()
+
+
+# ---------------------------------------------------------------------------------------------- libyalps_milpbatch.so
+
+_milpbatch_lib = None
+
+# yalps_milpbatch_eval_fn / yalps_milpbatch_consumed_fn
+MILP_EVAL_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int32),
+                           C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_double),
+                           C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int32))
+MILP_CONSUMED_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int32, C.c_double, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                               C.POINTER(C.c_double))
+
+
+def milpbatch_lib():
+    global _milpbatch_lib
+    if _milpbatch_lib is None:
+        if not os.path.exists(MILPBATCH_LIB_PATH):
+            raise NativeError(f"{MILPBATCH_LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
+                              "(there is no CPU fallback)")
+        L = C.CDLL(MILPBATCH_LIB_PATH)
+        vp, i32 = C.c_void_p, C.c_int32
+        L.yalps_milpbatch_last_error.restype = C.c_char_p
+        L.yalps_milpbatch_create.restype = i32
+        L.yalps_milpbatch_create.argtypes = [i32, vp, C.POINTER(vp)]
+        L.yalps_milpbatch_destroy.restype = None
+        L.yalps_milpbatch_destroy.argtypes = [vp]
+        L.yalps_milpbatch_roots.restype = i32
+        L.yalps_milpbatch_roots.argtypes = [vp, i32] + [vp] * 12
+        L.yalps_milpbatch_root.restype = i32
+        L.yalps_milpbatch_root.argtypes = [vp, i32, vp, vp, vp, vp]
+        L.yalps_milpbatch_nodes.restype = i32
+        L.yalps_milpbatch_nodes.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
+        L.yalps_milpbatch_validate_nodes.restype = i32
+        L.yalps_milpbatch_validate_nodes.argtypes = [i32, vp, vp, i32, vp, vp, vp]
+        L.yalps_milpbatch_node.restype = i32
+        L.yalps_milpbatch_node.argtypes = [vp, i32, vp, vp, vp]
+        L.yalps_milpbatch_node_tableau.restype = i32
+        L.yalps_milpbatch_node_tableau.argtypes = [vp, i32, vp]
+        L.yalps_milpbatch_solve.restype = i32
+        L.yalps_milpbatch_solve.argtypes = [vp, i32] + [vp] * 15 + [i32, vp, vp, vp, vp]
+        L.yalps_milpbatch_validate.restype = i32
+        L.yalps_milpbatch_validate.argtypes = [i32, vp, vp, vp, vp, i32]
+        L.yalps_milpbatch_solution.restype = i32
+        L.yalps_milpbatch_solution.argtypes = [vp, i32, C.POINTER(i32), vp, vp, vp]
+        L.yalps_milpbatch_search.restype = i32
+        L.yalps_milpbatch_search.argtypes = [i32] + [vp] * 14 + [i32, MILP_EVAL_FN, MILP_CONSUMED_FN, vp] + [vp] * 8
+        L.yalps_milpbatch_info.restype = i32
+        L.yalps_milpbatch_info.argtypes = [vp, C.c_char_p, i32]
+        _milpbatch_lib = L
+    return _milpbatch_lib
+
+
+def milpbatch_check(rc):
+    if rc < 0:
+        raise NativeError("yalps_milpbatch error %d: %s" % (rc, milpbatch_lib().yalps_milpbatch_last_error().decode()))
+    return rc
+
+
+class PackedMilps:
+    """A batch of models with integers as yalps_milpbatch_solve takes it: PackedLps for the root LPs plus, per model, the integer
+    variables, the objective sign and the branch-and-cut options."""
+
+    def __init__(self, milps):
+        """milps: a sequence of (width, height, row, col, val, integers, sign, options) with the reference's option keys
+        (precision, maxPivots, checkCycles, tolerance, timeout, maxIterations)."""
+        n = len(milps)
+        self.lps = PackedLps([(m[0], m[1], m[2], m[3], m[4], m[7]["precision"], m[7]["maxPivots"], m[7]["checkCycles"]) for m in milps])
+        self.count = n
+        self.n_integers = np.fromiter((len(m[5]) for m in milps), np.int64, n)
+        self.int_offsets = np.zeros(n + 1, np.int64)
+        self.int_offsets[1:] = np.cumsum(self.n_integers)
+        self.integers = np.ascontiguousarray(np.concatenate([np.asarray(m[5], np.int32) for m in milps]) if n else np.zeros(0), np.int32)
+        f = lambda get: np.fromiter((float(get(m)) for m in milps), np.float64, n)
+        self.sign = f(lambda m: m[6])
+        self.tolerance, self.timeout = f(lambda m: m[7]["tolerance"]), f(lambda m: m[7]["timeout"])
+        self.max_iterations = f(lambda m: m[7]["maxIterations"])
+
+    def validate(self, node_batch=1):
+        """The argument checks of yalps_milpbatch_solve on the integers and the node sizes, on the host."""
+        milpbatch_check(milpbatch_lib().yalps_milpbatch_validate(self.count, self.lps.width.ctypes.data, self.lps.height.ctypes.data,
+                                                                 self.int_offsets.ctypes.data, self.integers.ctypes.data, int(node_batch)))
+
+
+def _pack_cuts(cut_lists):
+    """cut_lists: per node a sequence of (sign, variable, value) -> (offsets, sign, var, val) as the C ABI takes them."""
+    off = np.zeros(len(cut_lists) + 1, np.int64)
+    off[1:] = np.cumsum([len(c) for c in cut_lists])
+    flat = [c for cuts in cut_lists for c in cuts]
+    return (off, np.array([c[0] for c in flat], np.int32), np.array([c[1] for c in flat], np.int32),
+            np.array([c[2] for c in flat], np.float64))
+
+
+def milp_validate_nodes(root_width, root_height, root_index, cut_lists):
+    """The argument checks of yalps_milpbatch_nodes against roots of the given shapes, on the host (raises NativeError naming the node)."""
+    rw, rh = np.ascontiguousarray(root_width, np.int32), np.ascontiguousarray(root_height, np.int32)
+    ri = np.ascontiguousarray(root_index, np.int32)
+    off, _, var, _ = cut_lists if isinstance(cut_lists, tuple) else _pack_cuts(cut_lists)
+    milpbatch_check(milpbatch_lib().yalps_milpbatch_validate_nodes(rw.size, rw.ctypes.data, rh.ctypes.data, ri.size, ri.ctypes.data,
+                                                                   off.ctypes.data, var.ctypes.data))
+
+
+class MilpBatch:
+    """Many independent MILPs per call (yalps_milpbatch_*): a root pass that keeps every optimal root on the device, node passes
+    over nodes of any mix of roots, and the lockstep branch and cut over both.  Belongs to one thread at a time."""
+
+    def __init__(self, device=0, stream=None):
+        self.handle = C.c_void_p()
+        milpbatch_check(milpbatch_lib().yalps_milpbatch_create(device, C.c_void_p(stream) if stream is not None else None,
+                                                               C.byref(self.handle)))
+        self.root_shapes, self.node_shapes, self.packed = None, None, None
+
+    def roots(self, lps):
+        """lps: a PackedLps or the sequence it is made from.  Returns (status names, results, pivot counts)."""
+        p = lps if isinstance(lps, PackedLps) else PackedLps(lps)
+        n = p.count
+        st, res, piv = np.empty(n, np.int32), np.empty(n, np.float64), np.empty(n, np.int64)
+        self.root_shapes = self.node_shapes = self.packed = None
+        milpbatch_check(milpbatch_lib().yalps_milpbatch_roots(
+            self.handle, n, p.width.ctypes.data, p.height.ctypes.data, p.offsets.ctypes.data, p.row.ctypes.data, p.col.ctypes.data,
+            p.val.ctypes.data, p.precision.ctypes.data, p.max_pivots.ctypes.data, p.check_cycles.ctypes.data, st.ctypes.data,
+            res.ctypes.data, piv.ctypes.data))
+        self.root_shapes = (p.width.copy(), p.height.copy())
+        return [STATUS[k] for k in st], res, piv
+
+    def root(self, i, matrix=False):
+        """(col0, positionOfVariable, variableAtPosition[, matrix]) of root i of the last root pass."""
+        if self.root_shapes is None or not 0 <= i < self.root_shapes[0].size:
+            raise NativeError("MilpBatch: no such root in the last root pass: %r" % (i,))
+        w, h = int(self.root_shapes[0][i]), int(self.root_shapes[1][i])
+        col0, pos, var = np.empty(h, np.float64), np.empty(w + h, np.int32), np.empty(w + h, np.int32)
+        m = np.empty(w * h, np.float64) if matrix else None
+        milpbatch_check(milpbatch_lib().yalps_milpbatch_root(self.handle, i, col0.ctypes.data, pos.ctypes.data, var.ctypes.data,
+                                                             m.ctypes.data if matrix else None))
+        return (col0, pos, var, m) if matrix else (col0, pos, var)
+
+    def nodes(self, root_index, cut_lists, max_pivots=None, keep_tableaux=False):
+        """Node k = root root_index[k] of the last root pass + cut_lists[k] ((sign, variable, value) each).  max_pivots: None =
+        each root's own, else one budget per node.  Returns (status names, results, pivot counts, heights)."""
+        if self.root_shapes is None:
+            raise NativeError("MilpBatch.nodes: no root pass to build nodes on")
+        ri = np.ascontiguousarray(root_index, np.int32)
+        off, sg, vr, vl = _pack_cuts(cut_lists)
+        n = ri.size
+        assert off.size == n + 1
+        mp = None if max_pivots is None else np.ascontiguousarray(np.broadcast_to(np.asarray(max_pivots, np.float64), (n,)))
+        st, res, piv, hg = np.empty(n, np.int32), np.empty(n, np.float64), np.empty(n, np.int64), np.empty(n, np.int32)
+        self.node_shapes = None
+        milpbatch_check(milpbatch_lib().yalps_milpbatch_nodes(
+            self.handle, n, ri.ctypes.data, off.ctypes.data, sg.ctypes.data, vr.ctypes.data, vl.ctypes.data,
+            mp.ctypes.data if mp is not None else None, int(bool(keep_tableaux)), st.ctypes.data, res.ctypes.data, piv.ctypes.data,
+            hg.ctypes.data))
+        self.node_shapes = (self.root_shapes[0][ri] if n else np.zeros(0, np.int32), hg)
+        return [STATUS[k] for k in st], res, piv, hg
+
+    def _node_shape(self, k):
+        if self.node_shapes is None or not 0 <= k < self.node_shapes[1].size:
+            raise NativeError("MilpBatch: no such node in the last node pass: %r" % (k,))
+        return int(self.node_shapes[0][k]), int(self.node_shapes[1][k])
+
+    def node(self, k):
+        """(col0, positionOfVariable, variableAtPosition) of node k of the last node pass."""
+        w, h = self._node_shape(k)
+        col0, pos, var = np.empty(h, np.float64), np.empty(w + h, np.int32), np.empty(w + h, np.int32)
+        milpbatch_check(milpbatch_lib().yalps_milpbatch_node(self.handle, k, col0.ctypes.data, pos.ctypes.data, var.ctypes.data))
+        return col0, pos, var
+
+    def node_tableau(self, k):
+        """The whole final matrix of node k of the last node pass (nodes(..., keep_tableaux=True)), flat row-major."""
+        w, h = self._node_shape(k)
+        m = np.empty(w * h, np.float64)
+        milpbatch_check(milpbatch_lib().yalps_milpbatch_node_tableau(self.handle, k, m.ctypes.data))
+        return m
+
+    def solve(self, milps, node_batch=8):
+        """milps: a PackedMilps or the sequence it is made from.  Returns (status names, results, nodes used, nodes evaluated,
+        {"rounds", "launches", "gpu_ms"})."""
+        p = milps if isinstance(milps, PackedMilps) else PackedMilps(milps)
+        n, lp = p.count, p.lps
+        st, res, stats, call = np.empty(n, np.int32), np.empty(n, np.float64), np.zeros(2 * n, np.int64), np.zeros(3, np.int64)
+        self.root_shapes = self.node_shapes = self.packed = None
+        milpbatch_check(milpbatch_lib().yalps_milpbatch_solve(
+            self.handle, n, lp.width.ctypes.data, lp.height.ctypes.data, lp.offsets.ctypes.data, lp.row.ctypes.data, lp.col.ctypes.data,
+            lp.val.ctypes.data, p.int_offsets.ctypes.data, p.integers.ctypes.data, p.sign.ctypes.data, lp.precision.ctypes.data,
+            lp.max_pivots.ctypes.data, lp.check_cycles.ctypes.data, p.tolerance.ctypes.data, p.timeout.ctypes.data,
+            p.max_iterations.ctypes.data, int(node_batch), st.ctypes.data, res.ctypes.data, stats.ctypes.data, call.ctypes.data))
+        self.packed = p
+        self.root_shapes = (lp.width.copy(), lp.height.copy())
+        return ([STATUS[k] for k in st], res, stats[0::2].copy(), stats[1::2].copy(),
+                {"rounds": int(call[0]), "launches": int(call[1]), "gpu_ms": call[2] / 1000.0})
+
+    def solution(self, i):
+        """(height, col0, positionOfVariable, variableAtPosition) of the best tableau of model i of the last solve."""
+        p = self.packed
+        if p is None or not 0 <= i < p.count:
+            raise NativeError("MilpBatch: no such model in the last solve: %r" % (i,))
+        w, cap = int(p.lps.width[i]), int(p.lps.height[i]) + 2 * int(p.n_integers[i])
+        col0, pos, var, h = np.empty(cap, np.float64), np.empty(w + cap, np.int32), np.empty(w + cap, np.int32), C.c_int32()
+        milpbatch_check(milpbatch_lib().yalps_milpbatch_solution(self.handle, i, C.byref(h), col0.ctypes.data, pos.ctypes.data,
+                                                                 var.ctypes.data))
+        n = h.value
+        return n, col0[:n].copy(), pos[:w + n].copy(), var[:w + n].copy()
+
+    def info(self):
+        """{"rounds", "launches", "reruns", "gpu_ms", "rerun_nodes": [k | (round, k)], "kernels": [{kernel, class, nodes | lps, grid,
+        lds, pass, round, hist_cap}], "text"}"""
+        buf = C.create_string_buffer(1 << 14)
+        need = milpbatch_check(milpbatch_lib().yalps_milpbatch_info(self.handle, buf, len(buf)))
+        if need >= len(buf):
+            buf = C.create_string_buffer(need + 1)
+            milpbatch_check(milpbatch_lib().yalps_milpbatch_info(self.handle, buf, len(buf)))
+        text = buf.value.decode()
+        lines = text.splitlines()
+        head = dict(kv.split("=", 1) for kv in lines[0].split()) if lines else {}
+        ids = [x for x in head.get("rerun_nodes", "[]").strip("[]").split(",") if x]
+        kernels = []
+        for line in lines[1:]:
+            kv = dict(x.split("=", 1) for x in line.split())
+            kernels.append({k: (v if k == "kernel" else int(v)) for k, v in kv.items()})
+        return {"rounds": int(head.get("rounds", 0)), "launches": int(head.get("launches", 0)), "reruns": int(head.get("reruns", 0)),
+                "gpu_ms": int(head.get("gpu_us", 0)) / 1000.0,
+                "rerun_nodes": [tuple(int(y) for y in x.split(":")) if ":" in x else int(x) for x in ids], "kernels": kernels, "text": text}
+
+    def close(self):
+        if self.handle:
+            milpbatch_lib().yalps_milpbatch_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+
+def milp_search(roots, evaluate, node_batch=8, consumed=None):
+    """The lockstep branch and cut of yalps_milpbatch_solve with `evaluate` as its node evaluator (host only, no device).
+    roots: per model (width, height, status name, result, col0, pos, var, integers, sign, options) -- the root solved.
+    evaluate(nodes) with nodes = [(model index, [(sign, variable, value)])] returns per node (status name, result, col0, pos,
+    var) (the last three are read of optimal nodes only).  consumed(model, eval, cuts), optional, sees every node a tree
+    consumes, in its pop order.  Returns per model (status name, result, height, col0, pos, var, nodes used, nodes evaluated)
+    and the number of rounds."""
+    n = len(roots)
+    i32 = lambda it: np.ascontiguousarray(np.fromiter(it, np.int32, n))
+    f64 = lambda it: np.ascontiguousarray(np.fromiter((float(x) for x in it), np.float64, n))
+    width, height = i32(r[0] for r in roots), i32(r[1] for r in roots)
+    rstatus, rresult = i32(STATUS.index(r[2]) for r in roots), f64(r[3] for r in roots)
+    cat = lambda k, dt: np.ascontiguousarray(np.concatenate([np.asarray(r[k], dt) for r in roots]), dt) if n else np.zeros(0, dt)
+    rcol0, rpos, rvar = cat(4, np.float64), cat(5, np.int32), cat(6, np.int32)
+    nints = np.fromiter((len(r[7]) for r in roots), np.int64, n)
+    ioff = np.zeros(n + 1, np.int64)
+    ioff[1:] = np.cumsum(nints)
+    ints = cat(7, np.int32)
+    sign = f64(r[8] for r in roots)
+    prec, tol = f64(r[9]["precision"] for r in roots), f64(r[9]["tolerance"] for r in roots)
+    tmo, mit = f64(r[9]["timeout"] for r in roots), f64(r[9]["maxIterations"] for r in roots)
+    failure = []
+
+    def c_eval(user, count, model, off, sg, vr, vl, status, result, hout, col0, pos, var):
+        try:
+            nodes = [(model[k], [(sg[c], vr[c], vl[c]) for c in range(off[k], off[k + 1])]) for k in range(count)]
+            at0 = atp = 0
+            for k, ((m, cuts), (st, res, c0, p, v)) in enumerate(zip(nodes, evaluate(nodes))):
+                h, w = int(height[m]) + len(cuts), int(width[m])
+                status[k], result[k], hout[k] = STATUS.index(st), res, h
+                if st == "optimal":
+                    hout[k] = len(c0)  # (a node of another height is refused by the driver)
+                    for j in range(min(h, len(c0))):
+                        col0[at0 + j] = c0[j]
+                    for j in range(min(w + h, len(p), len(v))):
+                        pos[atp + j], var[atp + j] = p[j], v[j]
+                at0, atp = at0 + h, atp + w + h
+            return 0
+        except BaseException as e:  # (no exception may cross the C frames)
+            failure.append(e)
+            return -1
+
+    def c_consumed(user, model, ev, ncuts, sg, vr, vl):
+        try:
+            consumed(model, ev, [(sg[c], vr[c], vl[c]) for c in range(ncuts)])
+        except BaseException as e:
+            failure.append(e)
+
+    caps = height.astype(np.int64) + 2 * nints
+    c0_off, p_off = np.concatenate([[0], np.cumsum(caps)]), np.concatenate([[0], np.cumsum(caps + width)])
+    st, res, hg = np.empty(n, np.int32), np.empty(n, np.float64), np.empty(n, np.int32)
+    col0, pos, var = np.zeros(int(c0_off[-1]), np.float64), np.zeros(int(p_off[-1]), np.int32), np.zeros(int(p_off[-1]), np.int32)
+    stats, rounds = np.zeros(2 * n, np.int64), C.c_int64()
+    rc = milpbatch_lib().yalps_milpbatch_search(
+        n, width.ctypes.data, height.ctypes.data, rstatus.ctypes.data, rresult.ctypes.data, rcol0.ctypes.data, rpos.ctypes.data,
+        rvar.ctypes.data, ioff.ctypes.data, ints.ctypes.data, sign.ctypes.data, prec.ctypes.data, tol.ctypes.data, tmo.ctypes.data,
+        mit.ctypes.data, int(node_batch), MILP_EVAL_FN(c_eval), MILP_CONSUMED_FN(c_consumed) if consumed else MILP_CONSUMED_FN(),
+        None, st.ctypes.data, res.ctypes.data, hg.ctypes.data, col0.ctypes.data, pos.ctypes.data, var.ctypes.data, stats.ctypes.data,
+        C.addressof(rounds))
+    if failure:
+        raise failure[0]
+    milpbatch_check(rc)
+    out = []
+    for i in range(n):
+        h, w = int(hg[i]), int(width[i])
+        out.append((STATUS[st[i]], float(res[i]), h, col0[c0_off[i]:c0_off[i] + h].copy(), pos[p_off[i]:p_off[i] + w + h].copy(),
+                    var[p_off[i]:p_off[i] + w + h].copy(), int(stats[2 * i]), int(stats[2 * i + 1])))
+    return out, rounds.value

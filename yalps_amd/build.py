@@ -2,6 +2,7 @@
 
   yalps_amd/libyalps_hip.so   HIP kernels + C ABI (include/yalps_hip.h)      hipcc
   yalps_amd/libyalps_lpbatch.so   batches of independent LPs (include/yalps_lpbatch.h)   hipcc
+  yalps_amd/libyalps_milpbatch.so batches of independent MILPs (include/yalps_milpbatch.h) hipcc
   yalps_amd/napi/yalps_napi.node  thin N-API shim over the C ABI (optional)  g++
 
 The .so files are git-ignored but travel to the GPU box with the tree.
@@ -20,12 +21,17 @@ HIP_SRC = os.path.join(CSRC, "yalps_hip.hip")  # host side + C ABI + the launch-
 # the persistent kernels' instantiations, one translation unit per group: compiled side by side (the device compile of
 # ~40 register-heavy kernels in one unit took 2.5 minutes)
 HIP_UNITS = [HIP_SRC] + [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.startswith("persistent_") and f.endswith(".hip")]
-HIP_DEPS = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith((".cuh", ".inc", ".h")) and not f.startswith("lp_batch")]
+HIP_DEPS = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith((".cuh", ".inc", ".h")) and not f.startswith(("lp_batch", "milp_node"))]
 # the batch library: one translation unit of its own around the shared workgroup loop, never linked into libyalps_hip.so
 LIB_LPBATCH = os.path.join(HERE, "libyalps_lpbatch.so")
 LPBATCH_SRC = os.path.join(CSRC, "lp_batch.hip")
-LPBATCH_DEPS = [os.path.join(CSRC, f) for f in ("lp_batch_kernel.cuh", "wg_simplex.cuh", "common.cuh")]
+LPBATCH_DEPS = [os.path.join(CSRC, f) for f in ("lp_batch_kernel.cuh", "lp_batch_host.inc", "wg_simplex.cuh", "common.cuh")]
 LPBATCH_HEADER = os.path.join(ROOT, "include", "yalps_lpbatch.h")
+# the MILP batch library: the LP batch's root pass compiled again next to milp_node_kernel and the lockstep driver
+LIB_MILPBATCH = os.path.join(HERE, "libyalps_milpbatch.so")
+MILPBATCH_SRC = os.path.join(CSRC, "milp_batch.hip")
+MILPBATCH_DEPS = LPBATCH_DEPS + [os.path.join(CSRC, f) for f in ("milp_node_kernel.cuh", "milp_search.inc")] + [LPBATCH_HEADER]
+MILPBATCH_HEADER = os.path.join(ROOT, "include", "yalps_milpbatch.h")
 OBJ_DIR = os.path.join(HERE, "build")
 HEADER = os.path.join(ROOT, "include", "yalps_hip.h")
 NAPI_SRC = os.path.join(HERE, "napi", "yalps_napi.cc")
@@ -81,7 +87,7 @@ def kernel_metadata(lib=LIB):
 # scratch and without accumulator registers, or not at all.  (Two instantiations that broke this rule computed wrong
 # rows on the GPU -- DESIGN.md 4.7 -- so the rule is part of the build, not of an optional test.)
 # ("batch_kernel" also matches libyalps_lpbatch.so's lp_batch_kernel.)
-NO_SCRATCH = ("dshard_kernel", "dshard_select_kernel", "dshard_sweep_kernel", "small_kernel", "batch_kernel", "assemble", "resident_kernel", "resident2_kernel", "stream_kernel", "stream2_kernel", "stream3_kernel", "sweep_kernel")
+NO_SCRATCH = ("milp_node_kernel", "dshard_kernel", "dshard_select_kernel", "dshard_sweep_kernel", "small_kernel", "batch_kernel", "assemble", "resident_kernel", "resident2_kernel", "stream_kernel", "stream2_kernel", "stream3_kernel", "sweep_kernel")
 
 
 def check_register_budgets(lib=LIB, min_resident=15):
@@ -97,10 +103,11 @@ def check_register_budgets(lib=LIB, min_resident=15):
             bad.append("%s: vgpr_count %s agpr_count %s" % (name, md["vgpr_count"], md["agpr_count"]))
         if any(tag in name for tag in NO_SCRATCH) and int(md["private_segment_fixed_size"]) != 0:
             bad.append("%s: private_segment_fixed_size %s (scratch)" % (name, md["private_segment_fixed_size"]))
-        if "lp_batch_kernel" in name and int(md["agpr_count"]) != 0:
+        queue = "lp_batch_kernel" in name or "milp_node_kernel" in name
+        if queue and int(md["agpr_count"]) != 0:
             bad.append("%s: agpr_count %s" % (name, md["agpr_count"]))
         # its dynamic LDS block (tableau and pivot row, swept 16 bytes at a time) starts where the static LDS ends
-        if "lp_batch_kernel" in name and int(md["group_segment_fixed_size"]) % 16 != 0:
+        if queue and int(md["group_segment_fixed_size"]) % 16 != 0:
             bad.append("%s: group_segment_fixed_size %s is not a multiple of 16 (misaligned 128-bit LDS accesses)" % (name, md["group_segment_fixed_size"]))
     if bad and os.environ.get("YALPS_BUILD_ALLOW_SCRATCH") == "1":  # (experiments only: a same-box A/B of a form that does not fit yet)
         print("register budget violated (YALPS_BUILD_ALLOW_SCRATCH=1: building anyway):\n  " + "\n  ".join(bad))
@@ -163,6 +170,26 @@ def build_lpbatch(force=False, verbose=False):
     return LIB_LPBATCH
 
 
+def build_milpbatch(force=False, verbose=False):
+    """libyalps_milpbatch.so: milp_batch.hip alone, same flags as the other two libraries."""
+    if not force and not _stale(LIB_MILPBATCH, MILPBATCH_HEADER, MILPBATCH_SRC, *MILPBATCH_DEPS):
+        return LIB_MILPBATCH
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    os.makedirs(OBJ_DIR, exist_ok=True)
+    obj = os.path.join(OBJ_DIR, "milp_batch.o")
+    for cmd in ([hipcc, *HIPCC_FLAGS, "-c", "-o", obj, MILPBATCH_SRC],
+                [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB_MILPBATCH + ".tmp", obj]):
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        subprocess.run(cmd, check=True)
+    ks = check_register_budgets(LIB_MILPBATCH + ".tmp", min_resident=0)
+    for kernel in ("milp_node_kernel", "lp_batch_kernel"):
+        if not any(kernel in k for k in ks):
+            raise RuntimeError("no %s in the code object of %s" % (kernel, LIB_MILPBATCH))
+    os.replace(LIB_MILPBATCH + ".tmp", LIB_MILPBATCH)
+    return LIB_MILPBATCH
+
+
 def build_napi(force=False, verbose=False):
     """The Node addon; skipped (returns None) where node's headers are absent."""
     inc = "/usr/include/node"
@@ -185,4 +212,5 @@ if __name__ == "__main__":
         raise SystemExit(0)
     print(build_hip(force=True, verbose=True))
     print(build_lpbatch(force=True, verbose=True))
+    print(build_milpbatch(force=True, verbose=True))
     print(build_napi(force=True, verbose=True))

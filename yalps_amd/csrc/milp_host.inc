@@ -15,104 +15,9 @@
 // A node's LP depends only on the root and its cuts, so evaluating frontier nodes early (batches) cannot change
 // any result; checkCycles always takes the one-node-at-a-time paths.
 
-namespace {
-
-struct MilpCut {
-    int32_t sign, variable;
-    double value;
-    bool operator<(const MilpCut &o) const {
-        return sign != o.sign ? sign < o.sign : variable != o.variable ? variable < o.variable : value < o.value;
-    }
-};
-using MilpCuts = std::vector<MilpCut>;
-
-struct MilpBranch {
-    double eval;
-    MilpCuts cuts;
-};
-
-// heapq.heappush / heappop (CPython Lib/heapq.py): comparison on eval only
-inline bool milp_lt(const MilpBranch &a, const MilpBranch &b) { return a.eval < b.eval; }
-void milp_siftdown(std::vector<MilpBranch> &heap, size_t startpos, size_t pos) {
-    MilpBranch newitem = std::move(heap[pos]);
-    while (pos > startpos) {
-        const size_t parentpos = (pos - 1) >> 1;
-        if (milp_lt(newitem, heap[parentpos])) {
-            heap[pos] = std::move(heap[parentpos]);
-            pos = parentpos;
-            continue;
-        }
-        break;
-    }
-    heap[pos] = std::move(newitem);
-}
-void milp_siftup(std::vector<MilpBranch> &heap, size_t pos) {
-    const size_t endpos = heap.size(), startpos = pos;
-    MilpBranch newitem = std::move(heap[pos]);
-    size_t childpos = 2 * pos + 1;
-    while (childpos < endpos) {
-        const size_t rightpos = childpos + 1;
-        if (rightpos < endpos && !milp_lt(heap[childpos], heap[rightpos])) childpos = rightpos;
-        heap[pos] = std::move(heap[childpos]);
-        pos = childpos;
-        childpos = 2 * pos + 1;
-    }
-    heap[pos] = std::move(newitem);
-    milp_siftdown(heap, startpos, pos);
-}
-void milp_push(std::vector<MilpBranch> &heap, MilpBranch item) {
-    heap.push_back(std::move(item));
-    milp_siftdown(heap, 0, heap.size() - 1);
-}
-MilpBranch milp_pop(std::vector<MilpBranch> &heap) {
-    MilpBranch last = std::move(heap.back());
-    heap.pop_back();
-    if (heap.empty()) return last;
-    MilpBranch ret = std::move(heap[0]);
-    heap[0] = std::move(last);
-    milp_siftup(heap, 0);
-    return ret;
-}
-
-// what mostFractionalVar / solution() read of a solved tableau
-struct MilpView {
-    int32_t height = 0;
-    std::vector<double> col0;
-    std::vector<int32_t> pos, var;
-};
-
-struct MilpEval {
-    int32_t status = YALPS_CYCLED;
-    double result = NAN;
-    MilpView view; // filled when status == optimal
-};
-
-// src/branchAndCut.ts:64-85
-void milp_most_fractional(const MilpView &v, int32_t width, const int32_t *ints, int32_t nints, int32_t *variable, double *value,
-                          double *frac_out) {
-    double highest = 0.0, val_best = 0.0;
-    int32_t var_best = 0;
-    for (int32_t i = 0; i < nints; i++) {
-        const int32_t row = v.pos[ints[i]] - width;
-        if (row < 0) continue;
-        const double val = v.col0[row];
-        const double frac = std::fabs(val - js_round(val));
-        if (frac > highest) {
-            highest = frac;
-            var_best = ints[i];
-            val_best = val;
-        }
-    }
-    *variable = var_best;
-    *value = val_best;
-    *frac_out = highest;
-}
-
-double milp_now_ms() {
-    return (double)std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::system_clock::now().time_since_epoch()).count();
-}
-
-} // namespace
+// The queue (CPython heapq's sift rules), mostFractionalVar, the children's cut lists and the choice of the nodes of a
+// batch are milp_search.inc: the lockstep driver of libyalps_milpbatch.so (milp_batch.hip) reads the same text.
+#include "milp_search.inc"
 
 extern "C" int32_t yalps_milp_f64(const double *matrix, int32_t width, int32_t height, const int32_t *positionOfVariable,
                        const int32_t *variableAtPosition, const int32_t *integers, int32_t n_integers, double sign,
@@ -269,28 +174,14 @@ extern "C" int32_t yalps_milp_f64(const double *matrix, int32_t width, int32_t h
     };
 
     std::vector<MilpBranch> branches; // :99-103
-    milp_push(branches, {root_result, {{-1, variable, std::ceil(value)}}});
-    milp_push(branches, {root_result, {{1, variable, std::floor(value)}}});
+    milp_push_first(branches, root_result, variable, value);
     std::map<MilpCuts, MilpEval> cache; // batched: results of nodes evaluated ahead of their turn
     std::vector<double> bulk_col0;
     std::vector<int32_t> bulk_pos, bulk_var;
 
     // the popped node together with the next-best frontier nodes, one workgroup per node
     auto evaluate_batch = [&](const MilpCuts &first) -> int32_t {
-        std::vector<const MilpCuts *> todo{&first};
-        std::vector<size_t> order(branches.size());
-        for (size_t i = 0; i < order.size(); i++) order[i] = i;
-        const size_t want = (size_t)node_batch - 1 < order.size() ? (size_t)node_batch - 1 : order.size();
-        std::partial_sort(order.begin(), order.begin() + want, order.end(), [&](size_t a, size_t b2) {
-            return branches[a].eval != branches[b2].eval ? branches[a].eval < branches[b2].eval : a < b2;
-        });
-        std::set<MilpCuts> seen{first};
-        for (size_t k = 0; k < want; k++) {
-            const MilpCuts &cs = branches[order[k]].cuts;
-            if (cache.count(cs) || seen.count(cs)) continue;
-            todo.push_back(&cs);
-            seen.insert(cs);
-        }
+        const std::vector<const MilpCuts *> todo = milp_wanted(branches, first, node_batch, cache);
         const int32_t count = (int32_t)todo.size();
         std::vector<int32_t> off((size_t)count + 1, 0), sg, vr, st((size_t)count);
         std::vector<double> vl, res((size_t)count);
@@ -363,19 +254,7 @@ extern "C" int32_t yalps_milp_f64(const double *matrix, int32_t width, int32_t h
                 best_eval = ev.result;
                 best = std::move(ev.view);
             } else { // :137-158
-                MilpCuts upper, lower;
-                for (const MilpCut &cut : br.cuts) {
-                    if (cut.variable == variable) {
-                        (cut.sign < 0 ? lower : upper).push_back(cut);
-                    } else {
-                        upper.push_back(cut);
-                        lower.push_back(cut);
-                    }
-                }
-                lower.push_back({1, variable, std::floor(value)});
-                upper.push_back({-1, variable, std::ceil(value)});
-                milp_push(branches, {ev.result, std::move(upper)});
-                milp_push(branches, {ev.result, std::move(lower)});
+                milp_push_children(branches, br, variable, value, ev.result);
             }
         }
         timedout = milp_now_ms() >= stop_time;

@@ -207,42 +207,105 @@ def lpbatch_simplex(tableaux, options, stats=None):
     return [(s, float(r)) for s, r in zip(statuses, results)]
 
 
-def _solve_many_with(batch_simplex, solve_one, models, options=None, stats=None):
-    """solve_many with both backends as parameters (tests drive the routing and the marshalling with the CPU oracle):
+_milpbatch = None  # the process's MilpBatch, kept like _lpbatch
+MILP_NODE_BATCH = 8  # nodes a tree asks for per round in solve_many (see milpbatch_solve)
+
+
+def milpbatch_solve(items, stats=None, node_batch=None):
+    """The batched MILP backend of solve_many: items = [(tabmod, options)] (tableaux built with sparse=True) through ONE
+    yalps_milpbatch_solve -- a root pass, then rounds in which the nodes all unfinished trees want share their launches.
+    Returns per model (status, result, height, col0, positionOfVariable, variableAtPosition) of its best tableau.
+
+    node_batch (default MILP_NODE_BATCH): the node a tree popped plus its next-best node_batch - 1 frontier nodes per round.
+    The value rests on the "node_batch_sweep" table of profiles/milp_batch_throughput.json (the mixed workload of 2944
+    trees): throughput rises steeply from 1 to 8 and is flat from 8 to 32, where repeated runs of the table order 8, 16 and
+    32 differently (within 6 % of each other); 8 is the smallest value on the plateau and evaluates the fewest nodes that
+    are never used."""
+    global _milpbatch
+    with _lpbatch_lock:
+        if _milpbatch is None:
+            _milpbatch = _native.MilpBatch(0)
+        batch = _milpbatch
+        packed = _native.PackedMilps([(tm.tableau.width, tm.tableau.height, *tm.tableau.cells, tm.integers, tm.sign, o)
+                                      for tm, o in items])
+        statuses, results, used, evaluated, call = batch.solve(packed, node_batch or MILP_NODE_BATCH)
+        out = [(s, float(r), *batch.solution(i)) for i, (s, r) in enumerate(zip(statuses, results))]
+    if stats is not None:
+        stats.update(node_rounds=call["rounds"], nodes_evaluated=int(evaluated.sum()), nodes_used=int(used.sum()),
+                     milp_launches=call["launches"])
+    return out
+
+
+def milp_batchable(tabmod, opt):
+    """A model with integers joins the MILP batch when its largest possible node (2 cuts per integer variable) is within
+    4 MiB and its timeout is infinite or <= 0: a finite positive timeout keeps solve(), whose clock counts that model alone."""
+    t = tabmod.tableau
+    timeout = opt["timeout"]
+    return (bool(tabmod.integers) and 8 * t.width * (t.height + 2 * len(tabmod.integers)) <= _native.MILPBATCH_MAX_BYTES
+            and (timeout == math.inf or timeout <= 0))
+
+
+def _solve_many_with(batch_simplex, solve_one, models, options=None, stats=None, milp_backend=None):
+    """solve_many with its backends as parameters (tests drive the routing and the marshalling with the CPU oracle):
     batch_simplex(tableaux, options, stats) -> [(status, result)] for the models without integers whose tableau is at most
-    NODE_BATCH_MAX_BYTES, solve_one(model, options) for every other model (integers, larger LPs), results in input order."""
+    NODE_BATCH_MAX_BYTES, solve_one(model, options) for every other model (integers, larger LPs), results in input order.
+    milp_backend(items, stats) (None: no MILP batch, every model with integers goes to solve_one) takes the models with
+    integers that milp_batchable accepts, as [(tabmod, options)], and returns each one's best tableau (milpbatch_solve)."""
+    from .model import Tableau, TableauModel
     models = list(models)
     opts = list(options) if isinstance(options, (list, tuple)) else [options] * len(models)
     if len(opts) != len(models):
         raise ValueError("solve_many: %d models but %d option sets" % (len(models), len(opts)))
     out = [None] * len(models)
     batched = []  # (index, tabmod, merged options)
+    milps = []
     routed = {"batched": 0, "milp": 0, "large": 0}
     for i, (model, o) in enumerate(zip(models, opts)):
         tabmod = tableau_model(model, sparse=True)
         t = tabmod.tableau
+        opt = dict(_DEFAULTS)
+        if o:
+            opt.update({k: v for k, v in o.items() if v is not None})
+        if milp_backend is not None and milp_batchable(tabmod, opt):
+            routed["milp"] += 1
+            milps.append((i, tabmod, opt))
+            continue
         if tabmod.integers or 8 * t.width * t.height > NODE_BATCH_MAX_BYTES:
             routed["milp" if tabmod.integers else "large"] += 1
             out[i] = solve_one(model, o)
             continue
-        opt = dict(_DEFAULTS)
-        if o:
-            opt.update({k: v for k, v in o.items() if v is not None})
         batched.append((i, tabmod, opt))
     routed["batched"] = len(batched)
+    if milp_backend is not None:
+        routed.update(milp_batched=len(milps), node_rounds=0, nodes_evaluated=0, nodes_used=0)
     if stats is not None:
         stats.update(routed)
     if batched:
         results = batch_simplex([b[1].tableau for b in batched], [b[2] for b in batched], stats)
         for (i, tabmod, opt), (status, result) in zip(batched, results):
             out[i] = solution(tabmod, status, result, opt)
+    if milps:
+        results = milp_backend([(m[1], m[2]) for m in milps], stats)
+        for (i, tabmod, opt), (status, result, height, col0, pos, var) in zip(milps, results):
+            view = TableauModel(Tableau(None, tabmod.tableau.width, height, pos, var, col0), tabmod.sign, tabmod.variables,
+                                tabmod.integers)
+            out[i] = solution(view, status, result, opt)
     return out
 
 
 def solve_many(models, options=None, stats=None):
-    """[solve(m, o) for m, o in zip(models, options)] -- same dicts, same order -- with every model that has no integer
-    variables and a tableau of at most 4 MiB solved in ONE batched GPU call (one workgroup per LP, yalps_lpbatch_solve).
-    `options` is one dict for all models or one per model.  Models with integers and larger LPs go through solve() one
-    by one.  stats (a dict, optional) receives how many models went which way ("batched", "milp", "large") and the
-    batch's launches."""
-    return _solve_many_with(lpbatch_simplex, solve, models, options, stats)
+    """[solve(m, o) for m, o in zip(models, options)] -- same dicts, same order -- in at most two batched GPU calls plus
+    solve() for what fits neither.  `options` is one dict for all models or one per model.
+
+    Models without integer variables and a tableau of at most 4 MiB: ONE yalps_lpbatch_solve, one workgroup per LP.
+    Models with integer variables whose largest possible node (8 * width * (height + 2 * n_integers) bytes) is within 4 MiB:
+    ONE yalps_milpbatch_solve -- every root in a root pass, then all branch-and-cut trees advance together, the nodes they
+    want next sharing launches round by round; each tree's node sequence, best tableau and result are what solve() gives
+    for it alone.  The clock: only a timeout of +inf, or <= 0 (timed out before the first node, deterministic), is batched;
+    a model with a finite positive timeout goes through solve(), whose clock counts that model's own work.
+    Everything else (larger LPs, larger MILPs) goes through solve() one by one.
+
+    stats (a dict, optional) receives how many models went which way ("batched" LPs, "milp" = every model with integers,
+    "milp_batched" of them in the MILP batch, "large"), the LP batch's launches, and "node_rounds", "nodes_evaluated",
+    "nodes_used" of the MILP batch."""
+    return _solve_many_with(lpbatch_simplex, solve, models, options, stats, milpbatch_solve)
