@@ -49,6 +49,10 @@ void yalps_lpbatch_destroy(yalps_lpbatch *b);
  * bytes, which yalps_lpbatch_lds_bytes returns), 4 = the HBM form, -1 = above YALPS_LPBATCH_MAX_BYTES or a bad size. */
 int32_t yalps_lpbatch_class(int32_t width, int32_t height);
 int64_t yalps_lpbatch_lds_bytes(int32_t width, int32_t height);
+/* Host only.  1 where a width x height LP is solved in the aux form of the HBM class: its pivot column and pivot row buffers
+ * (even(width - 1) + height doubles) are above 64 KiB, that is even(width - 1) + height > 8192, and live behind the tableau
+ * in the HBM workspace instead of LDS.  0 for every other batchable LP, -1 where yalps_lpbatch_class returns -1. */
+int32_t yalps_lpbatch_aux_hbm(int32_t width, int32_t height);
 /* Host only: what yalps_lpbatch_solve checks before it touches the device.  0, or YALPS_E_ARG with the index of the
  * first offending LP in the error text: width < 1, height < 1, a tableau above YALPS_LPBATCH_MAX_BYTES, cell offsets
  * that decrease, a cell outside the tableau, cells not strictly increasing by (row, col). */

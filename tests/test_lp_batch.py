@@ -132,6 +132,12 @@ def test_class_binning_on_both_sides_of_every_boundary(nat):
             assert nat.lpbatch_lds_bytes(w, h) == B.lds_bytes(w, h) <= bound < B.lds_bytes(w, h + 1)
             assert nat.lpbatch_class(w, h) == k and nat.lpbatch_class(w, h + 1) == k + 1, (w, h, k)
     assert nat.lpbatch_class(1024, 512) == 4 and nat.lpbatch_class(1024, 513) == -1  # 4 MiB exactly | above
+    # the aux form of the HBM class: colbuf + prow (even(w - 1) + h doubles) above 64 KiB, on both sides of the bound
+    for w, h in ((8152, 40), (8153, 40), (31, 8162), (30, 8162), (2, 8190), (1, 8192), (64, 8128)):
+        assert (w & ~1) + h == 8192 and nat.lpbatch_class(w, h) == nat.lpbatch_class(w, h + 1) == 4
+        assert (nat.lpbatch_aux_hbm(w, h), nat.lpbatch_aux_hbm(w, h + 1)) == (0, 1), (w, h)
+    assert nat.lpbatch_aux_hbm(262144, 2) == 1 and nat.lpbatch_aux_hbm(64, 8191) == 1 and nat.lpbatch_aux_hbm(512, 1024) == 0
+    assert nat.lpbatch_aux_hbm(30, 30) == 0 and nat.lpbatch_aux_hbm(1024, 513) == -1 and nat.lpbatch_aux_hbm(0, 5) == -1
     assert nat.lpbatch_class(0, 5) == -1 and nat.lpbatch_class(5, 0) == -1
     for cls, (M, N) in CLASS_SHAPES.items():
         assert nat.lpbatch_class(N + 1, M + 1) == cls

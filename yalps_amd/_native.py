@@ -30,7 +30,7 @@ SYMBOLS = (
 # every symbol include/yalps_lpbatch.h declares (a library of its own, loaded on first use)
 LPBATCH_LIB_PATH = os.environ.get("YALPS_LPBATCH_LIB") or os.path.join(HERE, "libyalps_lpbatch.so")
 SYMBOLS_LPBATCH = (
-    "yalps_lpbatch_last_error", "yalps_lpbatch_create", "yalps_lpbatch_destroy", "yalps_lpbatch_class", "yalps_lpbatch_lds_bytes",
+    "yalps_lpbatch_last_error", "yalps_lpbatch_create", "yalps_lpbatch_destroy", "yalps_lpbatch_class", "yalps_lpbatch_lds_bytes", "yalps_lpbatch_aux_hbm",
     "yalps_lpbatch_validate", "yalps_lpbatch_solve", "yalps_lpbatch_solution", "yalps_lpbatch_tableau", "yalps_lpbatch_info",
 )
 LPBATCH_MAX_BYTES = 4 << 20  # YALPS_LPBATCH_MAX_BYTES
@@ -517,6 +517,8 @@ def lpbatch_lib():
         L.yalps_lpbatch_class.argtypes = [i32, i32]
         L.yalps_lpbatch_lds_bytes.restype = C.c_int64
         L.yalps_lpbatch_lds_bytes.argtypes = [i32, i32]
+        L.yalps_lpbatch_aux_hbm.restype = i32
+        L.yalps_lpbatch_aux_hbm.argtypes = [i32, i32]
         L.yalps_lpbatch_validate.restype = i32
         L.yalps_lpbatch_validate.argtypes = [i32, vp, vp, vp, vp, vp]
         L.yalps_lpbatch_solve.restype = i32
@@ -544,6 +546,11 @@ def lpbatch_class(width, height):
 
 def lpbatch_lds_bytes(width, height):
     return lpbatch_lib().yalps_lpbatch_lds_bytes(int(width), int(height))
+
+
+def lpbatch_aux_hbm(width, height):
+    """1 where a width x height LP takes the aux form of the HBM class (colbuf / prow in HBM), 0 where not, -1 not batchable."""
+    return lpbatch_lib().yalps_lpbatch_aux_hbm(int(width), int(height))
 
 
 class PackedLps:

@@ -36,6 +36,10 @@ int64_t yalps_lpbatch_lds_bytes(int32_t width, int32_t height) {
     return width < 1 || height < 1 ? -1 : (int64_t)small_lds_bytes(width, height);
 }
 
+int32_t yalps_lpbatch_aux_hbm(int32_t width, int32_t height) {
+    return lp_class(width, height) < 0 ? -1 : (lp_class(width, height) == HBM_CLASS && lp_aux_hbm(width, height) ? 1 : 0);
+}
+
 int32_t yalps_lpbatch_validate(int32_t count, const int32_t *width, const int32_t *height, const int64_t *cell_offsets,
                                const int32_t *row, const int32_t *col) {
     return validate(count, width, height, cell_offsets, row, col);

@@ -51,6 +51,9 @@ const KernelForm kForms[] = {
     {lp_batch_kernel<1024, false, true>, 1024, false, true},  {lp_batch_kernel<1024, true, true>, 1024, true, true},
     {lp_batch_kernel<1024, false, false>, 1024, false, false}, {lp_batch_kernel<1024, true, false>, 1024, true, false},
 };
+// HBM form: whether colbuf + prow of a w x h tableau go behind the tableau in the workspace (pcols + h > 8192)
+bool lp_aux_hbm(int64_t w, int64_t h) { return sizeof(double) * ((size_t)small_pcols((int)w - 1) + (size_t)h) > AUX_LDS_MAX; }
+
 const KernelForm *find_form(int lanes, bool check, bool lds) {
     for (const KernelForm &f : kForms)
         if (f.lanes == lanes && f.check == check && f.lds == lds) return &f;
@@ -301,7 +304,7 @@ int solve_impl(yalps_lpbatch *b, int32_t count, const int32_t *width, const int3
         d.tab_off = tab_total;
         d.precision = precision[i];
         d.max_pivots = maxPivots[i];
-        d.aux_hbm = sizeof(double) * ((size_t)small_pcols(d.w - 1) + (size_t)d.h) > AUX_LDS_MAX ? 1 : 0;
+        d.aux_hbm = lp_aux_hbm(d.w, d.h) ? 1 : 0;
         d.pad_ = 0;
         col0_total += (d.h + 1) & ~1; // (even offsets: 16-byte aligned column 0)
         perm_total += d.w + d.h;

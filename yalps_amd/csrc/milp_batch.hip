@@ -437,7 +437,7 @@ int nodes_impl(yalps_milpbatch *b, int32_t count, const int32_t *root, const int
         d.perm_off = perm_total;
         d.tab_off = tab_total;
         d.max_pivots = max_pivots ? max_pivots[k] : r.max_pivots;
-        d.aux_hbm = sizeof(double) * ((size_t)small_pcols(r.w - 1) + (size_t)h) > AUX_LDS_MAX ? 1 : 0;
+        d.aux_hbm = lp_aux_hbm(r.w, h) ? 1 : 0;
         d.pad_ = 0;
         col0_total += (h + 1) & ~1; // (even offsets: 16-byte aligned column 0)
         perm_total += r.w + h;
