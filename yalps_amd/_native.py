@@ -1,5 +1,5 @@
-"""ctypes binding of libyalps_hip.so (include/yalps_hip.h), libyalps_lpbatch.so (include/yalps_lpbatch.h) and
-libyalps_milpbatch.so (include/yalps_milpbatch.h).
+"""ctypes binding of libyalps_hip.so (include/yalps_hip.h), libyalps_lpbatch.so (include/yalps_lpbatch.h),
+libyalps_milpbatch.so (include/yalps_milpbatch.h) and libyalps_lpvar.so (include/yalps_lpvar.h).
 
 There is no CPU path: if the library is missing, or no gfx950 device is usable,
 every call raises.  Nothing here imports the oracle.
@@ -42,6 +42,13 @@ SYMBOLS_MILPBATCH = (
     "yalps_milpbatch_solve", "yalps_milpbatch_validate", "yalps_milpbatch_solution", "yalps_milpbatch_search", "yalps_milpbatch_info",
 )
 MILPBATCH_MAX_BYTES = 4 << 20  # YALPS_MILPBATCH_MAX_BYTES: a node's tableau, root height + cuts rows
+# every symbol include/yalps_lpvar.h declares (a fourth library, loaded on first use)
+LPVAR_LIB_PATH = os.environ.get("YALPS_LPVAR_LIB") or os.path.join(HERE, "libyalps_lpvar.so")
+SYMBOLS_LPVAR = (
+    "yalps_lpvar_last_error", "yalps_lpvar_create", "yalps_lpvar_destroy", "yalps_lpvar_validate", "yalps_lpvar_solve",
+    "yalps_lpvar_solution", "yalps_lpvar_tableau", "yalps_lpvar_info",
+)
+LPVAR_MAX_BYTES = 4 << 20  # YALPS_LPVAR_MAX_BYTES
 LPBATCH_HBM_CLASS = 4        # yalps_lpbatch_class: 0..3 the LDS form, 4 the HBM form
 
 
@@ -646,6 +653,152 @@ class LpBatch:
     def close(self):
         if self.handle:
             lpbatch_lib().yalps_lpbatch_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+
+# ---------------------------------------------------------------------------------------------- libyalps_lpvar.so
+
+_lpvar_lib = None
+
+
+def lpvar_lib():
+    global _lpvar_lib
+    if _lpvar_lib is None:
+        if not os.path.exists(LPVAR_LIB_PATH):
+            raise NativeError(f"{LPVAR_LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
+                              "(there is no CPU fallback)")
+        L = C.CDLL(LPVAR_LIB_PATH)
+        vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
+        L.yalps_lpvar_last_error.restype = C.c_char_p
+        L.yalps_lpvar_create.restype = i32
+        L.yalps_lpvar_create.argtypes = [i32, vp, C.POINTER(vp)]
+        L.yalps_lpvar_destroy.restype = None
+        L.yalps_lpvar_destroy.argtypes = [vp]
+        L.yalps_lpvar_validate.restype = i32
+        L.yalps_lpvar_validate.argtypes = [i32, i32, i64, vp, vp, i32, vp, vp, vp]
+        L.yalps_lpvar_solve.restype = i32
+        L.yalps_lpvar_solve.argtypes = [vp, i32, i32, i64, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp,
+                                        C.POINTER(C.c_float)]
+        L.yalps_lpvar_solution.restype = i32
+        L.yalps_lpvar_solution.argtypes = [vp, i32, vp, vp, vp]
+        L.yalps_lpvar_tableau.restype = i32
+        L.yalps_lpvar_tableau.argtypes = [vp, i32, vp]
+        L.yalps_lpvar_info.restype = i32
+        L.yalps_lpvar_info.argtypes = [vp, C.c_char_p, i32]
+        _lpvar_lib = L
+    return _lpvar_lib
+
+
+def lpvar_check(rc):
+    if rc < 0:
+        raise NativeError("yalps_lpvar error %d: %s" % (rc, lpvar_lib().yalps_lpvar_last_error().decode()))
+    return rc
+
+
+class PackedVariants:
+    """Variants of one LP as yalps_lpvar_solve takes them: the base's cells once, every variant's patch in three arrays."""
+
+    def __init__(self, width, height, row, col, val, patches, options=None, flat=None):
+        """row / col / val: the base's cells.  patches: per variant (row, col, val).  options: per variant (precision,
+        max_pivots, check_cycles); None = the defaults of solve for every variant.
+        flat = (offsets, row, col, val) gives the patches already concatenated (patches is then only counted)."""
+        n = len(patches)
+        self.count, self.width, self.height = n, int(width), int(height)
+        self.row = np.ascontiguousarray(row, np.int32)
+        self.col = np.ascontiguousarray(col, np.int32)
+        self.val = np.ascontiguousarray(val, np.float64)
+        assert self.row.size == self.col.size == self.val.size
+        if flat is not None:
+            off, prow, pcol, pval = flat
+            self.offsets = np.ascontiguousarray(off, np.int64)
+            self.patch_row, self.patch_col = np.ascontiguousarray(prow, np.int32), np.ascontiguousarray(pcol, np.int32)
+            self.patch_val = np.ascontiguousarray(pval, np.float64)
+        else:
+            self.offsets = np.zeros(n + 1, np.int64)
+            self.offsets[1:] = np.cumsum([len(p[0]) for p in patches])
+            cat = lambda k, dt: np.ascontiguousarray(np.concatenate([np.asarray(p[k], dt) for p in patches]), dt) if n else np.zeros(0, dt)
+            self.patch_row, self.patch_col, self.patch_val = cat(0, np.int32), cat(1, np.int32), cat(2, np.float64)
+        assert self.offsets.size == n + 1 and self.patch_row.size == self.patch_col.size == self.patch_val.size
+        if options is None:
+            options = [(1e-8, 8192.0, False)] * n
+        assert len(options) == n
+        self.precision = np.fromiter((o[0] for o in options), np.float64, n)
+        self.max_pivots = np.fromiter((float(o[1]) for o in options), np.float64, n)
+        self.check_cycles = np.fromiter((int(bool(o[2])) for o in options), np.int32, n)
+
+    def validate(self):
+        """The argument checks of yalps_lpvar_solve, on the host (raises NativeError naming the variant)."""
+        lpvar_check(lpvar_lib().yalps_lpvar_validate(
+            self.width, self.height, self.row.size, self.row.ctypes.data, self.col.ctypes.data, self.count,
+            self.offsets.ctypes.data, self.patch_row.ctypes.data, self.patch_col.ctypes.data))
+
+
+class LpVariants:
+    """Many variants of one LP per call, one workgroup per variant (yalps_lpvar_*).  Belongs to one thread at a time."""
+
+    def __init__(self, device=0, stream=None):
+        self.handle = C.c_void_p()
+        lpvar_check(lpvar_lib().yalps_lpvar_create(device, C.c_void_p(stream) if stream is not None else None,
+                                                   C.byref(self.handle)))
+        self.packed = None
+
+    def solve(self, packed, keep_tableaux=False):
+        """packed: a PackedVariants.  Returns (status names, results, pivot counts, gpu_ms)."""
+        p = packed
+        n = p.count
+        st, res, piv, ms = np.empty(n, np.int32), np.empty(n, np.float64), np.empty(n, np.int64), C.c_float()
+        self.packed = None
+        lpvar_check(lpvar_lib().yalps_lpvar_solve(
+            self.handle, p.width, p.height, p.row.size, p.row.ctypes.data, p.col.ctypes.data, p.val.ctypes.data, n,
+            p.offsets.ctypes.data, p.patch_row.ctypes.data, p.patch_col.ctypes.data, p.patch_val.ctypes.data,
+            p.precision.ctypes.data, p.max_pivots.ctypes.data, p.check_cycles.ctypes.data, int(bool(keep_tableaux)),
+            st.ctypes.data, res.ctypes.data, piv.ctypes.data, C.byref(ms)))
+        self.packed = p
+        return [STATUS[k] for k in st], res, piv, ms.value
+
+    def _check(self, i):
+        if self.packed is None or not 0 <= i < self.packed.count:
+            raise NativeError("LpVariants: no such variant in the last solve: %r" % (i,))
+        return self.packed.width, self.packed.height
+
+    def solution(self, i):
+        """(col0, positionOfVariable, variableAtPosition) of variant i of the last solve."""
+        w, h = self._check(i)
+        col0 = np.empty(h, np.float64)
+        pos, var = np.empty(w + h, np.int32), np.empty(w + h, np.int32)
+        lpvar_check(lpvar_lib().yalps_lpvar_solution(self.handle, i, col0.ctypes.data, pos.ctypes.data, var.ctypes.data))
+        return col0, pos, var
+
+    def tableau(self, i):
+        """The whole final matrix of variant i of the last solve (solve(..., keep_tableaux=True)), flat row-major."""
+        w, h = self._check(i)
+        m = np.empty(w * h, np.float64)
+        lpvar_check(lpvar_lib().yalps_lpvar_tableau(self.handle, i, m.ctypes.data))
+        return m
+
+    def info(self):
+        """{"launches", "reruns", "rerun_lps": [...], "base_cells", "patch_cells", "image_bytes",
+        "kernels": [{kernel, class, aux, lps, grid, lds, pass, hist_cap}], "text"}"""
+        buf = C.create_string_buffer(1 << 12)
+        need = lpvar_check(lpvar_lib().yalps_lpvar_info(self.handle, buf, len(buf)))
+        if need >= len(buf):  # (the text names every rerun variant: as long as the call makes it)
+            buf = C.create_string_buffer(need + 1)
+            lpvar_check(lpvar_lib().yalps_lpvar_info(self.handle, buf, len(buf)))
+        text = buf.value.decode()
+        lines = text.splitlines()
+        head = dict(kv.split("=", 1) for kv in lines[0].split()) if lines else {}
+        ids = head.get("rerun_lps", "[]").strip("[]")
+        kernels = []
+        for line in lines[1:]:
+            kv = dict(x.split("=", 1) for x in line.split())
+            kernels.append({k: (v if k == "kernel" else int(v)) for k, v in kv.items()})
+        out = {k: int(head.get(k, 0)) for k in ("launches", "reruns", "base_cells", "patch_cells", "image_bytes")}
+        out.update(rerun_lps=[int(x) for x in ids.split(",") if x], kernels=kernels, text=text)
+        return out
+
+    def close(self):
+        if self.handle:
+            lpvar_lib().yalps_lpvar_destroy(self.handle)
             self.handle = C.c_void_p()
 
 

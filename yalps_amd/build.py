@@ -3,6 +3,7 @@
   yalps_amd/libyalps_hip.so   HIP kernels + C ABI (include/yalps_hip.h)      hipcc
   yalps_amd/libyalps_lpbatch.so   batches of independent LPs (include/yalps_lpbatch.h)   hipcc
   yalps_amd/libyalps_milpbatch.so batches of independent MILPs (include/yalps_milpbatch.h) hipcc
+  yalps_amd/libyalps_lpvar.so     many variants of one LP (include/yalps_lpvar.h)        hipcc
   yalps_amd/napi/yalps_napi.node  thin N-API shim over the C ABI (optional)  g++
 
 The .so files are git-ignored but travel to the GPU box with the tree.
@@ -21,7 +22,7 @@ HIP_SRC = os.path.join(CSRC, "yalps_hip.hip")  # host side + C ABI + the launch-
 # the persistent kernels' instantiations, one translation unit per group: compiled side by side (the device compile of
 # ~40 register-heavy kernels in one unit took 2.5 minutes)
 HIP_UNITS = [HIP_SRC] + [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.startswith("persistent_") and f.endswith(".hip")]
-HIP_DEPS = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith((".cuh", ".inc", ".h")) and not f.startswith(("lp_batch", "milp_node"))]
+HIP_DEPS = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith((".cuh", ".inc", ".h")) and not f.startswith(("lp_batch", "lp_variants", "milp_node"))]
 # the batch library: one translation unit of its own around the shared workgroup loop, never linked into libyalps_hip.so
 LIB_LPBATCH = os.path.join(HERE, "libyalps_lpbatch.so")
 LPBATCH_SRC = os.path.join(CSRC, "lp_batch.hip")
@@ -32,6 +33,11 @@ LIB_MILPBATCH = os.path.join(HERE, "libyalps_milpbatch.so")
 MILPBATCH_SRC = os.path.join(CSRC, "milp_batch.hip")
 MILPBATCH_DEPS = LPBATCH_DEPS + [os.path.join(CSRC, f) for f in ("milp_node_kernel.cuh", "milp_search.inc")] + [LPBATCH_HEADER]
 MILPBATCH_HEADER = os.path.join(ROOT, "include", "yalps_milpbatch.h")
+# the variants library: a shared base image plus per-variant patches, one translation unit around the same workgroup loop
+LIB_LPVAR = os.path.join(HERE, "libyalps_lpvar.so")
+LPVAR_SRC = os.path.join(CSRC, "lp_variants.hip")
+LPVAR_DEPS = [os.path.join(CSRC, f) for f in ("lp_variants_kernel.cuh", "wg_simplex.cuh", "common.cuh")]
+LPVAR_HEADER = os.path.join(ROOT, "include", "yalps_lpvar.h")
 OBJ_DIR = os.path.join(HERE, "build")
 HEADER = os.path.join(ROOT, "include", "yalps_hip.h")
 NAPI_SRC = os.path.join(HERE, "napi", "yalps_napi.cc")
@@ -87,7 +93,7 @@ def kernel_metadata(lib=LIB):
 # scratch and without accumulator registers, or not at all.  (Two instantiations that broke this rule computed wrong
 # rows on the GPU -- DESIGN.md 4.7 -- so the rule is part of the build, not of an optional test.)
 # ("batch_kernel" also matches libyalps_lpbatch.so's lp_batch_kernel.)
-NO_SCRATCH = ("milp_node_kernel", "dshard_kernel", "dshard_select_kernel", "dshard_sweep_kernel", "small_kernel", "batch_kernel", "assemble", "resident_kernel", "resident2_kernel", "stream_kernel", "stream2_kernel", "stream3_kernel", "sweep_kernel")
+NO_SCRATCH = ("lp_variants", "milp_node_kernel", "dshard_kernel", "dshard_select_kernel", "dshard_sweep_kernel", "small_kernel", "batch_kernel", "assemble", "resident_kernel", "resident2_kernel", "stream_kernel", "stream2_kernel", "stream3_kernel", "sweep_kernel")
 
 
 def check_register_budgets(lib=LIB, min_resident=15):
@@ -103,7 +109,7 @@ def check_register_budgets(lib=LIB, min_resident=15):
             bad.append("%s: vgpr_count %s agpr_count %s" % (name, md["vgpr_count"], md["agpr_count"]))
         if any(tag in name for tag in NO_SCRATCH) and int(md["private_segment_fixed_size"]) != 0:
             bad.append("%s: private_segment_fixed_size %s (scratch)" % (name, md["private_segment_fixed_size"]))
-        queue = "lp_batch_kernel" in name or "milp_node_kernel" in name
+        queue = "lp_batch_kernel" in name or "milp_node_kernel" in name or "lp_variants_kernel" in name
         if queue and int(md["agpr_count"]) != 0:
             bad.append("%s: agpr_count %s" % (name, md["agpr_count"]))
         # its dynamic LDS block (tableau and pivot row, swept 16 bytes at a time) starts where the static LDS ends
@@ -190,6 +196,26 @@ def build_milpbatch(force=False, verbose=False):
     return LIB_MILPBATCH
 
 
+def build_lpvar(force=False, verbose=False):
+    """libyalps_lpvar.so: lp_variants.hip alone, same flags as the other libraries."""
+    if not force and not _stale(LIB_LPVAR, LPVAR_HEADER, LPVAR_SRC, *LPVAR_DEPS):
+        return LIB_LPVAR
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    os.makedirs(OBJ_DIR, exist_ok=True)
+    obj = os.path.join(OBJ_DIR, "lp_variants.o")
+    for cmd in ([hipcc, *HIPCC_FLAGS, "-c", "-o", obj, LPVAR_SRC],
+                [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB_LPVAR + ".tmp", obj]):
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        subprocess.run(cmd, check=True)
+    ks = check_register_budgets(LIB_LPVAR + ".tmp", min_resident=0)
+    for kernel in ("lp_variants_kernel", "lp_variants_base_kernel"):
+        if not any(kernel in k for k in ks):
+            raise RuntimeError("no %s in the code object of %s" % (kernel, LIB_LPVAR))
+    os.replace(LIB_LPVAR + ".tmp", LIB_LPVAR)
+    return LIB_LPVAR
+
+
 def build_napi(force=False, verbose=False):
     """The Node addon; skipped (returns None) where node's headers are absent."""
     inc = "/usr/include/node"
@@ -213,4 +239,5 @@ if __name__ == "__main__":
     print(build_hip(force=True, verbose=True))
     print(build_lpbatch(force=True, verbose=True))
     print(build_milpbatch(force=True, verbose=True))
+    print(build_lpvar(force=True, verbose=True))
     print(build_napi(force=True, verbose=True))

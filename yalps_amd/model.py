@@ -96,6 +96,13 @@ class _Cells(dict):
 def tableau_model(model, sparse=False):
     """src/tableau.ts:47-137, line for line in behaviour.  sparse=True keeps only the cells the
     reference writes into its zeroed matrix (Tableau.cells; for yalps_tableau_assemble)."""
+    return tableau_model_with_bounds(model, sparse)[0]
+
+
+def tableau_model_with_bounds(model, sparse=False):
+    """(tableau_model(model, sparse), bounds_info): what tableau_model builds, and next to it what variant_patch needs to
+    patch that tableau without walking the model again -- {"bounds": {constraint key: {"row", "lower", "upper"}} (the merged
+    bounds with their rows), "objective": the objective key, "columns": {variable key: [its columns]}}."""
     sign = -1.0 if model.get("direction") == "minimize" else 1.0  # :51
     objective = model.get("objective")
     integers, binaries = model.get("integers"), model.get("binaries")
@@ -165,9 +172,139 @@ def tableau_model(model, sparse=False):
         m[row * width] = 1.0
         m[row * width + col] = 1.0
 
+    columns = {}
+    for c in range(1, width):
+        columns.setdefault(variables[c - 1][0], []).append(c)
+    info = {"bounds": bounds, "objective": objective, "columns": columns}
     if sparse:
-        return TableauModel(Tableau(None, width, height, pos, var, cells=m.arrays(width)), sign, variables, ints)
-    return TableauModel(Tableau(m, width, height, pos, var), sign, variables, ints)
+        return TableauModel(Tableau(None, width, height, pos, var, cells=m.arrays(width)), sign, variables, ints), info
+    return TableauModel(Tableau(m, width, height, pos, var), sign, variables, ints), info
+
+
+# ---- variants of one model: the same model under other bounds and coefficients (solve.solve_variants) ----
+# A variant is {"constraints": {key: constraint}, "variables": {variable key: {constraint key: coef}}}, both optional.
+
+def _merged(constraint):
+    """The [lower, upper] of one constraint alone (src/tableau.ts:73-80 on a fresh entry)."""
+    eq, mn, mx = _get(constraint, "equal"), _get(constraint, "min"), _get(constraint, "max")
+    return (max(-math.inf, eq if eq is not None else (mn if mn is not None else -math.inf)),
+            min(math.inf, eq if eq is not None else (mx if mx is not None else math.inf)))
+
+
+def apply_variant(model, variant):
+    """The full model a variant stands for: `model` with
+      variant["constraints"][key]  in place of EVERY entry of constraint `key`, at the position of the first one;
+      variant["variables"][key]    coefficients written over (or added to) those of every variable entry `key`, the
+                                   objective key included -- a later coefficient overwrites an earlier one, as in tableau_model.
+    A constraint key or a variable key the model does not have is a ValueError (a new variable would change the width).
+    Nothing the variant leaves alone is copied: unchanged constraints and coefficient sets are the model's own objects."""
+    out = dict(model)
+    new_constraints = variant.get("constraints") or {}
+    if new_constraints:
+        cons = model.get("constraints", {})
+        if isinstance(cons, dict):
+            missing = [k for k in new_constraints if k not in cons]
+            replaced = dict(cons)
+            replaced.update(new_constraints)  # (an existing key keeps its place)
+        else:
+            replaced, seen = [], set()
+            for key, constraint in cons:
+                if key in new_constraints:
+                    if key not in seen:
+                        replaced.append((key, new_constraints[key]))
+                    seen.add(key)
+                else:
+                    replaced.append((key, constraint))
+            missing = [k for k in new_constraints if k not in seen]
+        if missing:
+            raise ValueError("apply_variant: the model has no constraint %r" % (missing[0],))
+        out["constraints"] = replaced
+    new_coefs = variant.get("variables") or {}
+    if new_coefs:
+        vars_ = model.get("variables", {})
+
+        def patched(coefs, over):
+            if isinstance(coefs, dict):
+                merged = dict(coefs)
+                merged.update(over)
+                return merged
+            return list(coefs) + entries(over)
+
+        if isinstance(vars_, dict):
+            missing = [k for k in new_coefs if k not in vars_]
+            replaced = dict(vars_)
+            for key in new_coefs:
+                if key in vars_:
+                    replaced[key] = patched(vars_[key], new_coefs[key])
+        else:
+            replaced, seen = [], set()
+            for key, coefs in vars_:
+                if key in new_coefs:
+                    seen.add(key)
+                    coefs = patched(coefs, new_coefs[key])
+                replaced.append((key, coefs))
+            missing = [k for k in new_coefs if k not in seen]
+        if missing:
+            raise ValueError("apply_variant: the model has no variable %r" % (missing[0],))
+        out["variables"] = replaced
+    return out
+
+
+def variant_patch_cells(tabmod, bounds_info, variant):
+    """variant_patch as one list [(flat index, value)] sorted by index (what solve_variants concatenates), or None."""
+    width, sign = tabmod.tableau.width, tabmod.sign
+    bounds, objective, columns = bounds_info["bounds"], bounds_info["objective"], bounds_info["columns"]
+    m = {}
+    replaced = {}
+    for key, constraint in (variant.get("constraints") or {}).items():
+        b = bounds.get(key)
+        if b is None:
+            raise ValueError("variant_patch: the model has no constraint %r" % (key,))
+        lower, upper = _merged(constraint)
+        if math.isfinite(lower) != math.isfinite(b["lower"]) or math.isfinite(upper) != math.isfinite(b["upper"]):
+            return None  # other rows: the height or the row order changes
+        replaced[key] = {"row": b["row"], "lower": lower, "upper": upper}
+    for key, over in (variant.get("variables") or {}).items():
+        cols = columns.get(key)
+        if cols is None:
+            raise ValueError("variant_patch: the model has no variable %r" % (key,))
+        for constraint, coef in entries(over):  # src/tableau.ts:100-118 for these coefficients alone
+            coef = float(coef)
+            b = replaced.get(constraint) or bounds.get(constraint)
+            for c in cols:
+                if constraint == objective and objective is not None:
+                    m[c] = sign * coef
+                if b is not None:
+                    if math.isfinite(b["upper"]):
+                        m[b["row"] * width + c] = coef
+                        if math.isfinite(b["lower"]):
+                            m[(b["row"] + 1) * width + c] = -coef
+                    elif math.isfinite(b["lower"]):
+                        m[b["row"] * width + c] = -coef
+    for b in replaced.values():  # src/tableau.ts:120-128 for the replaced bounds alone
+        if math.isfinite(b["upper"]):
+            m[b["row"] * width] = b["upper"]
+            if math.isfinite(b["lower"]):
+                m[(b["row"] + 1) * width] = -b["lower"]
+        elif math.isfinite(b["lower"]):
+            m[b["row"] * width] = -b["lower"]
+    return sorted(m.items())
+
+
+def variant_patch(tabmod, bounds_info, variant):
+    """The cells in which the tableau of apply_variant(model, variant) differs from tabmod's (built from `model`, with
+    bounds_info from tableau_model_with_bounds): (row, col, val) sorted strictly by (row, col), every value computed by the
+    expression tableau_model uses for that cell (sign * coef, coef, -coef, upper, -lower: a lower bound of 0 is -0.0 here as
+    there).  Cells the variant names are in the patch whether or not their value changes.
+    None where the variant changes the tableau's STRUCTURE: a replaced constraint whose finite sides (upper finite? lower
+    finite?) differ from the base's merged bound, so that rows would appear, vanish or move.  Unknown keys: ValueError."""
+    cells = variant_patch_cells(tabmod, bounds_info, variant)
+    if cells is None:
+        return None
+    width = tabmod.tableau.width
+    idx = np.fromiter((k for k, _ in cells), np.int64, len(cells))
+    val = np.fromiter((v for _, v in cells), np.float64, len(cells))
+    return (idx // width).astype(np.int32), (idx % width).astype(np.int32), val
 
 
 # src/constraint.ts:7-25

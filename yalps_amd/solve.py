@@ -10,7 +10,7 @@ import threading
 
 from . import _native
 from .branch_and_cut import branch_and_cut
-from .model import tableau_model
+from .model import apply_variant, tableau_model, tableau_model_with_bounds, variant_patch_cells
 
 # src/YALPS.ts:52-60
 _DEFAULTS = {
@@ -309,3 +309,92 @@ def solve_many(models, options=None, stats=None):
     "milp_batched" of them in the MILP batch, "large"), the LP batch's launches, and "node_rounds", "nodes_evaluated",
     "nodes_used" of the MILP batch."""
     return _solve_many_with(lpbatch_simplex, solve, models, options, stats, milpbatch_solve)
+
+
+_lpvariants = None  # the process's LpVariants, kept like _lpbatch
+
+
+def lpvariants_simplex(tableau, patches, options, stats=None):
+    """The patched backend of solve_variants: the base tableau (built with sparse=True) and every variant's patch -- sorted
+    [(flat index, value)] -- through ONE yalps_lpvar_solve.  Returns per variant (status, result, col0, positionOfVariable,
+    variableAtPosition)."""
+    import numpy as np
+    global _lpvariants
+    w = tableau.width
+    offsets = np.zeros(len(patches) + 1, np.int64)
+    np.cumsum([len(p) for p in patches], out=offsets[1:])
+    total = int(offsets[-1])
+    idx = np.fromiter((k for p in patches for k, _ in p), np.int64, total)
+    val = np.fromiter((v for p in patches for _, v in p), np.float64, total)
+    packed = _native.PackedVariants(w, tableau.height, *tableau.cells, patches,
+                                    [(o["precision"], o["maxPivots"], o["checkCycles"]) for o in options],
+                                    flat=(offsets, idx // w, idx % w, val))
+    with _lpbatch_lock:
+        if _lpvariants is None:
+            _lpvariants = _native.LpVariants(0)
+        lv = _lpvariants
+        statuses, results, _, _ = lv.solve(packed)
+        out = [(s, float(r), *lv.solution(i)) for i, (s, r) in enumerate(zip(statuses, results))]
+        if stats is not None:
+            info = lv.info()
+            stats.update(launches=info["launches"], reruns=info["reruns"], kernels=info["kernels"])
+    return out
+
+
+def _solve_variants_with(variants_backend, solve_many_fn, model, variants, options=None, stats=None):
+    """solve_variants with its backends as parameters (tests drive the routing and the marshalling with the CPU oracle):
+    variants_backend(tableau, patches, options, stats) -> per variant (status, result, col0, pos, var) for the variants that
+    only patch the base tableau, solve_many_fn(models, options, stats) for the variants materialised with apply_variant
+    (a base with integers or above NODE_BATCH_MAX_BYTES, a variant that changes the structure); results in input order."""
+    from .model import Tableau, TableauModel
+    variants = list(variants)
+    opts = list(options) if isinstance(options, (list, tuple)) else [options] * len(variants)
+    if len(opts) != len(variants):
+        raise ValueError("solve_variants: %d variants but %d option sets" % (len(variants), len(opts)))
+    tabmod, bounds_info = tableau_model_with_bounds(model, sparse=True)
+    t = tabmod.tableau
+    patchable = not tabmod.integers and 8 * t.width * t.height <= NODE_BATCH_MAX_BYTES
+    out = [None] * len(variants)
+    patched, materialised = [], []  # (index, patch, merged options) | (index, model, options as given)
+    for i, (v, o) in enumerate(zip(variants, opts)):
+        patch = variant_patch_cells(tabmod, bounds_info, v) if patchable else None
+        if patch is None:
+            materialised.append((i, apply_variant(model, v), o))
+            continue
+        opt = dict(_DEFAULTS)
+        if o:
+            opt.update({k: x for k, x in o.items() if x is not None})
+        patched.append((i, patch, opt))
+    if stats is not None:
+        stats.update(patched=len(patched), materialised=len(materialised), base_cells=int(t.cells[0].size),
+                     patch_cells=sum(len(p[1]) for p in patched), launches=0, reruns=0, kernels=[])
+    if patched:
+        results = variants_backend(t, [p[1] for p in patched], [p[2] for p in patched], stats)
+        for (i, _, opt), (status, result, col0, pos, var) in zip(patched, results):
+            view = TableauModel(Tableau(None, t.width, t.height, pos, var, col0), tabmod.sign, tabmod.variables, tabmod.integers)
+            out[i] = solution(view, status, result, opt)
+    if materialised:
+        sub = {} if stats is not None else None
+        results = solve_many_fn([m[1] for m in materialised], [m[2] for m in materialised], sub)
+        for (i, _, _), r in zip(materialised, results):
+            out[i] = r
+        if stats is not None:
+            stats["solve_many"] = sub
+    return out
+
+
+def solve_variants(model, variants, options=None, stats=None):
+    """[solve(apply_variant(model, v), o) for v, o in zip(variants, options)] -- same dicts, same order -- for many variants
+    of ONE model: other bounds, other objective and constraint coefficients of existing variables (yalps_amd.model.apply_variant
+    says what a variant is).  `options` is one dict for all variants or one per variant.
+
+    The model is walked once.  Where it has no integer variables and its tableau is at most 4 MiB, a variant that keeps the
+    tableau's structure costs only its patch -- the handful of cells it changes -- on the host and over PCIe, and all such
+    variants go through ONE yalps_lpvar_solve: the base is assembled once on the device and every variant starts from a copy
+    of it.  Every other variant (a base with integers, a larger base, a replaced constraint with other finite sides) is
+    materialised with apply_variant and handed to solve_many in one call; nothing is refused that solve would accept.
+
+    stats (a dict, optional) receives "patched" and "materialised" (variants that went each way), "base_cells",
+    "patch_cells" (all patches together), "launches", "reruns" and "kernels" of the native call, and under "solve_many" the
+    stats of the materialised variants' call."""
+    return _solve_variants_with(lpvariants_simplex, solve_many, model, variants, options, stats)
