@@ -1,5 +1,6 @@
 """ctypes binding of libyalps_hip.so (include/yalps_hip.h), libyalps_lpbatch.so (include/yalps_lpbatch.h),
-libyalps_milpbatch.so (include/yalps_milpbatch.h) and libyalps_lpvar.so (include/yalps_lpvar.h).
+libyalps_milpbatch.so (include/yalps_milpbatch.h), libyalps_lpvar.so (include/yalps_lpvar.h) and libyalps_lpsens.so
+(include/yalps_lpsens.h).
 
 There is no CPU path: if the library is missing, or no gfx950 device is usable,
 every call raises.  Nothing here imports the oracle.
@@ -49,6 +50,13 @@ SYMBOLS_LPVAR = (
     "yalps_lpvar_solution", "yalps_lpvar_tableau", "yalps_lpvar_info",
 )
 LPVAR_MAX_BYTES = 4 << 20  # YALPS_LPVAR_MAX_BYTES
+# every symbol include/yalps_lpsens.h declares (a fifth library, loaded on first use)
+LPSENS_LIB_PATH = os.environ.get("YALPS_LPSENS_LIB") or os.path.join(HERE, "libyalps_lpsens.so")
+SYMBOLS_LPSENS = (
+    "yalps_lpsens_last_error", "yalps_lpsens_create", "yalps_lpsens_destroy", "yalps_lpsens_validate", "yalps_lpsens_solve",
+    "yalps_lpsens_solution", "yalps_lpsens_tableau", "yalps_lpsens_ranges", "yalps_lpsens_info",
+)
+LPSENS_MAX_BYTES = 4 << 20  # YALPS_LPSENS_MAX_BYTES
 LPBATCH_HBM_CLASS = 4        # yalps_lpbatch_class: 0..3 the LDS form, 4 the HBM form
 
 
@@ -654,6 +662,133 @@ class LpBatch:
         if self.handle:
             lpbatch_lib().yalps_lpbatch_destroy(self.handle)
             self.handle = C.c_void_p()
+
+
+# ---------------------------------------------------------------------------------------------- libyalps_lpsens.so
+
+_lpsens_lib = None
+
+
+def lpsens_lib():
+    global _lpsens_lib
+    if _lpsens_lib is None:
+        if not os.path.exists(LPSENS_LIB_PATH):
+            raise NativeError(f"{LPSENS_LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
+                              "(there is no CPU fallback)")
+        L = C.CDLL(LPSENS_LIB_PATH)
+        vp, i32 = C.c_void_p, C.c_int32
+        L.yalps_lpsens_last_error.restype = C.c_char_p
+        L.yalps_lpsens_create.restype = i32
+        L.yalps_lpsens_create.argtypes = [i32, vp, C.POINTER(vp)]
+        L.yalps_lpsens_destroy.restype = None
+        L.yalps_lpsens_destroy.argtypes = [vp]
+        L.yalps_lpsens_validate.restype = i32
+        L.yalps_lpsens_validate.argtypes = [i32, vp, vp, vp, vp, vp]
+        L.yalps_lpsens_solve.restype = i32
+        L.yalps_lpsens_solve.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, C.POINTER(C.c_float)]
+        L.yalps_lpsens_solution.restype = i32
+        L.yalps_lpsens_solution.argtypes = [vp, i32, vp, vp, vp]
+        L.yalps_lpsens_tableau.restype = i32
+        L.yalps_lpsens_tableau.argtypes = [vp, i32, vp]
+        L.yalps_lpsens_ranges.restype = i32
+        L.yalps_lpsens_ranges.argtypes = [vp, i32, vp, vp, vp, vp, vp]
+        L.yalps_lpsens_info.restype = i32
+        L.yalps_lpsens_info.argtypes = [vp, C.c_char_p, i32]
+        _lpsens_lib = L
+    return _lpsens_lib
+
+
+def lpsens_check(rc):
+    if rc < 0:
+        raise NativeError("yalps_lpsens error %d: %s" % (rc, lpsens_lib().yalps_lpsens_last_error().decode()))
+    return rc
+
+
+def lpsens_validate(packed):
+    """The argument checks of yalps_lpsens_solve on a PackedLps, on the host (raises NativeError naming the LP)."""
+    lpsens_check(lpsens_lib().yalps_lpsens_validate(packed.count, packed.width.ctypes.data, packed.height.ctypes.data,
+                                                    packed.offsets.ctypes.data, packed.row.ctypes.data, packed.col.ctypes.data))
+
+
+class LpSens:
+    """LpBatch's interface over yalps_lpsens_*, plus ranges(i): many independent LPs per call, one workgroup per LP, and for
+    every LP that ends optimal the five ranging arrays of its final tableau.  Belongs to one thread at a time."""
+
+    def __init__(self, device=0, stream=None):
+        self.handle = C.c_void_p()
+        lpsens_check(lpsens_lib().yalps_lpsens_create(device, C.c_void_p(stream) if stream is not None else None,
+                                                      C.byref(self.handle)))
+        self.packed = None
+
+    def solve(self, lps, keep_tableaux=False):
+        """lps: a PackedLps or the sequence it is made from.  Returns (status names, results, pivot counts, gpu_ms)."""
+        p = lps if isinstance(lps, PackedLps) else PackedLps(lps)
+        n = p.count
+        st, res, piv, ms = np.empty(n, np.int32), np.empty(n, np.float64), np.empty(n, np.int64), C.c_float()
+        self.packed = None
+        lpsens_check(lpsens_lib().yalps_lpsens_solve(
+            self.handle, n, p.width.ctypes.data, p.height.ctypes.data, p.offsets.ctypes.data, p.row.ctypes.data,
+            p.col.ctypes.data, p.val.ctypes.data, p.precision.ctypes.data, p.max_pivots.ctypes.data, p.check_cycles.ctypes.data,
+            int(bool(keep_tableaux)), st.ctypes.data, res.ctypes.data, piv.ctypes.data, C.byref(ms)))
+        self.packed = p
+        return [STATUS[k] for k in st], res, piv, ms.value
+
+    def _shape(self, i):
+        if self.packed is None or not 0 <= i < self.packed.count:
+            raise NativeError("LpSens: no such LP in the last solve: %r" % (i,))
+        return int(self.packed.width[i]), int(self.packed.height[i])
+
+    def solution(self, i):
+        """(col0, positionOfVariable, variableAtPosition) of LP i of the last solve."""
+        w, h = self._shape(i)
+        col0 = np.empty(h, np.float64)
+        pos, var = np.empty(w + h, np.int32), np.empty(w + h, np.int32)
+        lpsens_check(lpsens_lib().yalps_lpsens_solution(self.handle, i, col0.ctypes.data, pos.ctypes.data, var.ctypes.data))
+        return col0, pos, var
+
+    def tableau(self, i):
+        """The whole final matrix of LP i of the last solve (solve(..., keep_tableaux=True)), flat row-major."""
+        w, h = self._shape(i)
+        m = np.empty(w * h, np.float64)
+        lpsens_check(lpsens_lib().yalps_lpsens_tableau(self.handle, i, m.ctypes.data))
+        return m
+
+    def ranges(self, i):
+        """(row0, col_up, col_dn, row_lo, row_hi) of LP i of the last solve, which must have ended optimal (NativeError
+        otherwise): include/yalps_lpsens.h says what they hold."""
+        w, h = self._shape(i)
+        row0, col_up, col_dn = np.empty(w, np.float64), np.empty(w, np.float64), np.empty(w, np.float64)
+        row_lo, row_hi = np.empty(h, np.float64), np.empty(h, np.float64)
+        lpsens_check(lpsens_lib().yalps_lpsens_ranges(self.handle, i, row0.ctypes.data, col_up.ctypes.data, col_dn.ctypes.data,
+                                                      row_lo.ctypes.data, row_hi.ctypes.data))
+        return row0, col_up, col_dn, row_lo, row_hi
+
+    def info(self):
+        """LpBatch.info()'s dict; the kernels are spelled lp_sens_kernel<T[,check][,lds]>."""
+        buf = C.create_string_buffer(1 << 12)
+        need = lpsens_check(lpsens_lib().yalps_lpsens_info(self.handle, buf, len(buf)))
+        if need >= len(buf):
+            buf = C.create_string_buffer(need + 1)
+            lpsens_check(lpsens_lib().yalps_lpsens_info(self.handle, buf, len(buf)))
+        return _batch_info(buf.value.decode())
+
+    def close(self):
+        if self.handle:
+            lpsens_lib().yalps_lpsens_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+
+def _batch_info(text):
+    """The text of yalps_lpsens_info (yalps_lpbatch_info's format) as LpBatch.info()'s dict."""
+    lines = text.splitlines()
+    head = dict(kv.split("=", 1) for kv in lines[0].split()) if lines else {}
+    ids = head.get("rerun_lps", "[]").strip("[]")
+    kernels = []
+    for line in lines[1:]:
+        kv = dict(x.split("=", 1) for x in line.split())
+        kernels.append({k: (v if k == "kernel" else int(v)) for k, v in kv.items()})
+    return {"launches": int(head.get("launches", 0)), "reruns": int(head.get("reruns", 0)),
+            "rerun_lps": [int(x) for x in ids.split(",") if x], "kernels": kernels, "text": text}
 
 
 # ---------------------------------------------------------------------------------------------- libyalps_lpvar.so

@@ -1,6 +1,14 @@
 // lp_batch_host.inc -- host side of a batch of independent LPs: size classes, device buffers, the launches of a pass, the
 // checkCycles history rerun.  Included by lp_batch.hip (libyalps_lpbatch.so) and by milp_batch.hip (libyalps_milpbatch.so, whose
 // root pass is this code with kept tableaux) after common.cuh, wg_simplex.cuh and lp_batch_kernel.cuh: one text, two libraries.
+// lp_sens.hip (libyalps_lpsens.so) includes it a third time around lp_sens_kernel: it sets the names below and LPB_SENS, which
+// adds the buffer of the ranges; without them the text is what the two libraries above have always compiled.
+#ifndef LPB_KERNEL
+#define LPB_KERNEL lp_batch_kernel
+#define LPB_KERNEL_NAME "lp_batch_kernel"
+#define LPB_NAME "yalps_lpbatch"   // in messages
+#define LPB_ENV "YALPS_LPBATCH"    // prefix of the environment switches
+#endif
 namespace {
 thread_local std::string g_err;
 
@@ -47,9 +55,9 @@ struct KernelForm {
     bool check, lds;
 };
 const KernelForm kForms[] = {
-    {lp_batch_kernel<256, false, true>, 256, false, true},    {lp_batch_kernel<256, true, true>, 256, true, true},
-    {lp_batch_kernel<1024, false, true>, 1024, false, true},  {lp_batch_kernel<1024, true, true>, 1024, true, true},
-    {lp_batch_kernel<1024, false, false>, 1024, false, false}, {lp_batch_kernel<1024, true, false>, 1024, true, false},
+    {LPB_KERNEL<256, false, true>, 256, false, true},    {LPB_KERNEL<256, true, true>, 256, true, true},
+    {LPB_KERNEL<1024, false, true>, 1024, false, true},  {LPB_KERNEL<1024, true, true>, 1024, true, true},
+    {LPB_KERNEL<1024, false, false>, 1024, false, false}, {LPB_KERNEL<1024, true, false>, 1024, true, false},
 };
 // HBM form: whether colbuf + prow of a w x h tableau go behind the tableau in the workspace (pcols + h > 8192)
 bool lp_aux_hbm(int64_t w, int64_t h) { return sizeof(double) * ((size_t)small_pcols((int)w - 1) + (size_t)h) > AUX_LDS_MAX; }
@@ -60,7 +68,7 @@ const KernelForm *find_form(int lanes, bool check, bool lds) {
     return nullptr;
 }
 std::string form_name(const KernelForm &f) {
-    return "lp_batch_kernel<" + std::to_string(f.lanes) + (f.check ? ",check" : "") + (f.lds ? ",lds" : "") + ">";
+    return LPB_KERNEL_NAME "<" + std::to_string(f.lanes) + (f.check ? ",check" : "") + (f.lds ? ",lds" : "") + ">";
 }
 
 struct DevBuf {
@@ -97,6 +105,10 @@ struct yalps_lpbatch {
     std::vector<int32_t> h_pos, h_var, h_status;
     bool keep = false;
     std::string info;
+#ifdef LPB_SENS
+    DevBuf sens;                 // per LP 3 * (w + h) doubles at 3 * perm_off: row0[w] col_up[w] col_dn[w] row_lo[h] row_hi[h]
+    std::vector<double> h_sens;
+#endif
 };
 
 namespace {
@@ -113,12 +125,12 @@ int ensure(DevBuf &b, size_t bytes) {
 
 int validate(int32_t count, const int32_t *width, const int32_t *height, const int64_t *off, const int32_t *row,
              const int32_t *col) {
-    if (count < 0) return fail(YALPS_E_ARG, "yalps_lpbatch: count < 0");
+    if (count < 0) return fail(YALPS_E_ARG, LPB_NAME ": count < 0");
     if (count == 0) return 0;
-    if (!width || !height || !off) return fail(YALPS_E_ARG, "yalps_lpbatch: width / height / cell_offsets is NULL");
-    if (off[0] < 0) return fail(YALPS_E_ARG, "yalps_lpbatch: LP 0: negative cell offset");
+    if (!width || !height || !off) return fail(YALPS_E_ARG, LPB_NAME ": width / height / cell_offsets is NULL");
+    if (off[0] < 0) return fail(YALPS_E_ARG, LPB_NAME ": LP 0: negative cell offset");
     for (int32_t i = 0; i < count; i++) {
-        const std::string who = "yalps_lpbatch: LP " + std::to_string(i) + ": ";
+        const std::string who = LPB_NAME ": LP " + std::to_string(i) + ": ";
         const int64_t w = width[i], h = height[i];
         if (w < 1 || h < 1) return fail(YALPS_E_ARG, who + "width and height must be at least 1");
         if (8 * w * h > YALPS_LPBATCH_MAX_BYTES)
@@ -169,7 +181,7 @@ int run_pass(yalps_lpbatch *b, const std::vector<int32_t> &todo, const int32_t *
     for (Launch &L : launches) {
         const bool lds = L.cls != HBM_CLASS;
         L.form = find_form(lds ? b->lanes[L.cls] : 1024, L.check, lds);
-        if (!L.form) return fail(YALPS_E_ARG, "yalps_lpbatch: no kernel of " + std::to_string(b->lanes[L.cls]) + " lanes");
+        if (!L.form) return fail(YALPS_E_ARG, LPB_NAME ": no kernel of " + std::to_string(b->lanes[L.cls]) + " lanes");
         L.grid = (int)std::min<size_t>(L.lps.size(), (size_t)b->num_cus * (size_t)std::max(1, b->per_cu[L.cls]));
         for (int32_t i : L.lps) {
             if (lds) {
@@ -217,6 +229,9 @@ int run_pass(yalps_lpbatch *b, const std::vector<int32_t> &todo, const int32_t *
         a.ws_stride = (long long)L.stride;
         a.hist = static_cast<int32_t *>(b->hist.p);
         a.hist_cap = hist_cap;
+#ifdef LPB_SENS
+        a.sens = static_cast<double *>(b->sens.p);
+#endif
         const KernelFn fn = L.form->fn;
         fn<<<dim3(L.grid), dim3(L.form->lanes), L.shmem, s>>>(a);
         HIP_TRY(hipGetLastError());
@@ -254,18 +269,18 @@ int create_impl(int32_t device, void *hip_stream, yalps_lpbatch **out) {
     }
     HIP_TRY(hipEventCreate(&b->ev0));
     HIP_TRY(hipEventCreate(&b->ev1));
-    b->hist_first = std::max(1, env_int("YALPS_LPBATCH_HIST", (int)HIST_FIRST)); // (test hook: forces the rerun)
+    b->hist_first = std::max(1, env_int(LPB_ENV "_HIST", (int)HIST_FIRST)); // (test hook: forces the rerun)
     for (int k = 0; k < NCLASS; k++) {
         b->lanes[k] = kClasses[k].lanes;
         b->per_cu[k] = kClasses[k].per_cu;
     }
-    env_list("YALPS_LPBATCH_LANES", b->lanes, HBM_CLASS);
-    env_list("YALPS_LPBATCH_PER_CU", b->per_cu, NCLASS);
+    env_list(LPB_ENV "_LANES", b->lanes, HBM_CLASS);
+    env_list(LPB_ENV "_PER_CU", b->per_cu, NCLASS);
     for (int k = 0; k < NCLASS; k++) {
         if (!find_form(b->lanes[k], false, k != HBM_CLASS))
-            return fail(YALPS_E_ARG, "YALPS_LPBATCH_LANES: class " + std::to_string(k) + " has no kernel of " + std::to_string(b->lanes[k]) + " lanes (256 or 1024)");
+            return fail(YALPS_E_ARG, LPB_ENV "_LANES: class " + std::to_string(k) + " has no kernel of " + std::to_string(b->lanes[k]) + " lanes (256 or 1024)");
         if (b->per_cu[k] < 1 || b->per_cu[k] > 8) // (32 waves per CU: at most eight workgroups of 256 lanes)
-            return fail(YALPS_E_ARG, "YALPS_LPBATCH_PER_CU: class " + std::to_string(k) + ": " + std::to_string(b->per_cu[k]) + " is outside 1..8");
+            return fail(YALPS_E_ARG, LPB_ENV "_PER_CU: class " + std::to_string(k) + ": " + std::to_string(b->per_cu[k]) + " is outside 1..8");
     }
     // (dynamic LDS beyond 48 KB: the attribute belongs to the function, raised once to the most a launch can ask for)
     for (const KernelForm &f : kForms)
@@ -280,7 +295,7 @@ int solve_impl(yalps_lpbatch *b, int32_t count, const int32_t *width, const int3
                float *gpu_ms_out) {
     if (int rc = validate(count, width, height, off, row, col)) return rc;
     if (count > 0 && (!precision || !maxPivots || !checkCycles || (off[count] > off[0] && !val)))
-        return fail(YALPS_E_ARG, "yalps_lpbatch_solve: val / precision / maxPivots / checkCycles is NULL");
+        return fail(YALPS_E_ARG, LPB_NAME "_solve: val / precision / maxPivots / checkCycles is NULL");
     b->descs.clear();
     b->keep = keep != 0;
     b->info = "launches=0 reruns=0\n";
@@ -323,6 +338,9 @@ int solve_impl(yalps_lpbatch *b, int32_t count, const int32_t *width, const int3
     if (int rc = ensure(b->var, sizeof(int32_t) * (size_t)perm_total)) return rc;
     if (b->keep)
         if (int rc = ensure(b->tab, sizeof(double) * (size_t)tab_total)) return rc;
+#ifdef LPB_SENS
+    if (int rc = ensure(b->sens, sizeof(double) * 3 * (size_t)perm_total)) return rc;
+#endif
     HIP_TRY(hipMemcpyAsync(b->desc.p, D.data(), sizeof(LpDesc) * n, hipMemcpyHostToDevice, s));
     if (ncells) {
         HIP_TRY(hipMemcpyAsync(b->row.p, row + base, sizeof(int32_t) * ncells, hipMemcpyHostToDevice, s));
@@ -353,13 +371,13 @@ int solve_impl(yalps_lpbatch *b, int32_t count, const int32_t *width, const int3
             if (b->h_status[i] == WG_HISTORY_FULL)
                 again.push_back(i);
             else if (b->h_status[i] < 0 || b->h_status[i] > YALPS_CYCLED)
-                return fail(YALPS_E_DEVICE, "lp_batch_kernel did not report a result for LP " + std::to_string(i));
+                return fail(YALPS_E_DEVICE, LPB_KERNEL_NAME " did not report a result for LP " + std::to_string(i));
         }
         rerun_all.insert(rerun_all.end(), again.begin(), again.end());
         todo.swap(again);
         hist_cap *= 4;
         passes++;
-        if (!todo.empty() && hist_cap > (1ll << 28)) return fail(YALPS_E_NOMEM, "yalps_lpbatch_solve: checkCycles history beyond 2^28 pivots");
+        if (!todo.empty() && hist_cap > (1ll << 28)) return fail(YALPS_E_NOMEM, LPB_NAME "_solve: checkCycles history beyond 2^28 pivots");
     }
     std::string ids;
     for (int32_t i : rerun_all) ids += (ids.empty() ? "" : ",") + std::to_string(i);
@@ -371,6 +389,10 @@ int solve_impl(yalps_lpbatch *b, int32_t count, const int32_t *width, const int3
     HIP_TRY(hipMemcpyAsync(b->h_col0.data(), b->col0.p, sizeof(double) * (size_t)col0_total, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(b->h_pos.data(), b->pos.p, sizeof(int32_t) * (size_t)perm_total, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(b->h_var.data(), b->var.p, sizeof(int32_t) * (size_t)perm_total, hipMemcpyDeviceToHost, s));
+#ifdef LPB_SENS
+    b->h_sens.resize(3 * (size_t)perm_total);
+    HIP_TRY(hipMemcpyAsync(b->h_sens.data(), b->sens.p, sizeof(double) * 3 * (size_t)perm_total, hipMemcpyDeviceToHost, s));
+#endif
     if (result_out) HIP_TRY(hipMemcpyAsync(result_out, b->result.p, sizeof(double) * n, hipMemcpyDeviceToHost, s));
     if (pivots_out) HIP_TRY(hipMemcpyAsync(pivots_out, b->pivots.p, sizeof(int64_t) * n, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -386,6 +408,9 @@ void lpbatch_destroy_impl(yalps_lpbatch *b) {
     for (DevBuf *d : {&b->desc, &b->order, &b->counters, &b->row, &b->col, &b->val, &b->status, &b->result, &b->pivots, &b->col0,
                       &b->pos, &b->var, &b->tab, &b->ws, &b->hist})
         if (d->p) (void)hipFree(d->p);
+#ifdef LPB_SENS
+    if (b->sens.p) (void)hipFree(b->sens.p);
+#endif
     if (b->ev0) (void)hipEventDestroy(b->ev0);
     if (b->ev1) (void)hipEventDestroy(b->ev1);
     if (b->own_stream && b->stream) (void)hipStreamDestroy(b->stream);

@@ -398,3 +398,7 @@ def solve_variants(model, variants, options=None, stats=None):
     "patch_cells" (all patches together), "launches", "reruns" and "kernels" of the native call, and under "solve_many" the
     stats of the materialised variants' call."""
     return _solve_variants_with(lpvariants_simplex, solve_many, model, variants, options, stats)
+
+
+# sensitivity(model, options) / sensitivity_many(models, options, stats): solve()'s answer plus duals, reduced costs and ranges
+from .sensitivity import _sensitivity_many_with, sensitivity, sensitivity_many  # noqa: E402,F401
