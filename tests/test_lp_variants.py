@@ -6,7 +6,11 @@ both permutations, column 0 and (with keep_tableaux) every word of the final mat
 always the C oracle's on the dense tableau of tableau_model(apply_variant(model, variant)).
 
 KERNELS holds one row per compiled instantiation of the solving kernel: the size class whose launch uses it, checkCycles,
-and the (M, N) of a tests/_lp_variants.py::dense_model of that class; lp_variants_base_kernel builds the image."""
+and the (M, N) of a tests/_lp_variants.py::dense_model of that class; lp_variants_base_kernel builds the image.
+
+tests/test_variant_shapes.py takes the kernel through what these tests do not reach: patches longer than a workgroup, a base
+without cells, patch_offsets[0] > 0, both sides of every class bound, tests/_batch_shapes.py::shape_table and the edge families
+of tests/_edges.py as variants, queue reuse in the HBM and the aux form with history reruns, a caller's stream."""
 import math
 import os
 import re
