@@ -174,7 +174,8 @@ int32_t yalps_tableau_bench_sweep(yalps_tableau *t, int32_t row, int32_t col, in
 /* ---- row-sharded solve of ONE tableau across GPUs (BASELINE config 5) ------------
  * One process per GPU.  Each rank uploads a local tableau = objective row + its contiguous block
  * of rows, declares the partition with yalps_tableau_set_shard (bounds[r]..bounds[r+1] = global
- * rows of rank r, bounds[0] = 1, bounds[nranks] = global height; pos/var are the GLOBAL
+ * rows of rank r, bounds[0] = 1, bounds[nranks] = global height, never decreasing -- bounds[r] ==
+ * bounds[r+1] is a rank without rows, anything else is YALPS_E_ARG; pos/var are the GLOBAL
  * permutations, width + global height entries), then runs per pivot:
  *     yalps_shard_select(t, send)            -- this rank's candidates + candidate rows
  *     all-gather of yalps_shard_slot_doubles() doubles per rank   (caller: RCCL / torch.distributed)

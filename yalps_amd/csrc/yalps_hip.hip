@@ -2055,7 +2055,13 @@ int32_t yalps_tableau_set_shard(yalps_tableau *t, int32_t rank, int32_t nranks, 
                                 int32_t global_height, const int32_t *pos, const int32_t *var) {
     if (!t || !bounds || !pos || !var || nranks < 1 || nranks > MAX_SHARDS || rank < 0 || rank >= nranks)
         return fail(YALPS_E_ARG, "yalps_tableau_set_shard: bad argument");
-    if (t->height != 1 + bounds[rank + 1] - bounds[rank] || bounds[0] != 1 || bounds[nranks] != global_height)
+    // (the kernels' owner lookup takes the last k with row >= bounds[k]: that is the owner only if the bounds never decrease;
+    // bounds[k] == bounds[k + 1], a rank without rows, is fine)
+    for (int k = 1; k <= nranks; k++)
+        if (bounds[k] < bounds[k - 1])
+            return fail(YALPS_E_ARG, "yalps_tableau_set_shard: bounds must not decrease, but bounds[" + std::to_string(k) + "] = " + std::to_string(bounds[k]) +
+                                         " < bounds[" + std::to_string(k - 1) + "] = " + std::to_string(bounds[k - 1]));
+    if (t->height !=1 + bounds[rank + 1] - bounds[rank] || bounds[0] != 1 || bounds[nranks] != global_height)
         return fail(YALPS_E_ARG, "yalps_tableau_set_shard: uploaded rows do not match bounds (objective row + own rows)");
     if (t->generic) return fail(YALPS_E_ARG, "yalps_tableau_set_shard: row shards wider than 16385 columns are not supported");
     HIP_TRY(hipSetDevice(t->ctx->device));
