@@ -22,7 +22,7 @@ from tests import _lp_batch as LB
 from tests import _milp_batch as MB
 from tests import _milps as ML
 
-AUX_LDS_MAX = 64 * 1024  # lp_batch_host.inc: colbuf + prow of the HBM form stay in LDS up to this many bytes
+AUX_LDS_MAX = 64 * 1024  # wg_queue_host.inc: colbuf + prow of the HBM form stay in LDS up to this many bytes
 INF = math.inf
 
 
@@ -32,7 +32,7 @@ def pcols(w):
 
 
 def aux_hbm(w, h):
-    """The aux form of the HBM class (lp_batch_host.inc, milp_batch.hip), restated: pcols + h > 8192."""
+    """The aux form of the HBM class (wg_queue_host.inc::lp_aux_hbm), restated: pcols + h > 8192."""
     return 8 * (pcols(w) + h) > AUX_LDS_MAX
 
 

@@ -9,7 +9,7 @@ import numpy as np
 from tests import _census
 from yalps_amd.model import apply_variant, entries, tableau_model, tableau_model_with_bounds, variant_patch
 
-KERNEL_LANES = {0: 256, 1: 256, 2: 256, 3: 1024, 4: 1024}  # the class table of lp_batch_host.inc, which lp_variants.hip restates
+KERNEL_LANES = {0: 256, 1: 256, 2: 256, 3: 1024, 4: 1024}  # the class table of wg_queue_host.inc, which lp_variants.hip includes
 
 
 def kernel_of(cls, check):

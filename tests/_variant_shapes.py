@@ -33,7 +33,7 @@ def even(h):
 
 def pitch(w, h):
     """The row pitch of the image and of the tableau a variant starts from: small_lds_pitch(n) in the LDS classes,
-    small_pcols(n) in the HBM form (lp_variants.hip::shape_of)."""
+    small_pcols(n) in the HBM form (lp_variants.hip::solve_impl)."""
     return BS.pcols(w) | 2 if LB.size_class(w, h) < 4 else BS.pcols(w)
 
 
@@ -383,7 +383,7 @@ def must_rerun(targets, refs, hist=QUEUE_HIST):
 # ------------------------------------------------------------------------------------------------ wrong starts
 
 def launch_order(group):
-    """[variants] per launch of pass 0: checkCycles off, then on, each in the call's order (lp_variants.hip::run_pass)."""
+    """[variants] per launch of pass 0: checkCycles off, then on, each in the call's order (wg_queue_host.inc::plan_launches)."""
     return [[i for i, c in enumerate(group.checks()) if c == check] for check in (False, True)]
 
 

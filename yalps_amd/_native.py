@@ -512,46 +512,85 @@ def round_to_precision(x, precision):
     return lib().yalps_round_to_precision(x, precision)
 
 
-_lpbatch_lib = None
+_VP, _I32, _I64 = C.c_void_p, C.c_int32, C.c_int64
+_BATCH_LIBS = {}    # prefix -> (path, {name behind the prefix: (restype, argtypes)}); every library also has _COMMON_SIGS
+_loaded = {}        # prefix -> CDLL
+_COMMON_SIGS = {"last_error": (C.c_char_p, None), "create": (_I32, [_I32, _VP, C.POINTER(_VP)]), "destroy": (None, [_VP]),
+                "info": (_I32, [_VP, C.c_char_p, _I32])}
+
+
+def _load_lib(prefix):
+    """The library of _BATCH_LIBS[prefix], loaded once, its functions given their signatures."""
+    L = _loaded.get(prefix)
+    if L is None:
+        path, sigs = _BATCH_LIBS[prefix]
+        if not os.path.exists(path):
+            raise NativeError(f"{path} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
+                              "(there is no CPU fallback)")
+        L = C.CDLL(path)
+        for name, (restype, argtypes) in {**_COMMON_SIGS, **sigs}.items():
+            fn = getattr(L, "%s_%s" % (prefix, name))
+            fn.restype = restype
+            if argtypes is not None:
+                fn.argtypes = argtypes
+        _loaded[prefix] = L
+    return L
+
+
+def _check(prefix, rc):
+    if rc < 0:
+        raise NativeError("%s error %d: %s" % (prefix, rc, getattr(_load_lib(prefix), prefix + "_last_error")().decode()))
+    return rc
+
+
+def _info_text(prefix, handle, first=1 << 12):
+    """The text of <prefix>_info, the buffer grown to what the library says it needs (it names every rerun item)."""
+    info = getattr(_load_lib(prefix), prefix + "_info")
+    buf = C.create_string_buffer(first)
+    need = _check(prefix, info(handle, buf, len(buf)))
+    if need >= len(buf):
+        buf = C.create_string_buffer(need + 1)
+        _check(prefix, info(handle, buf, len(buf)))
+    return buf.value.decode()
+
+
+def _info_lines(text):
+    """(head, kernels) of an info text: the key=value pairs of its first line, and of every further line as a dict."""
+    lines = text.splitlines()
+    head = dict(kv.split("=", 1) for kv in lines[0].split()) if lines else {}
+    kernels = []
+    for line in lines[1:]:
+        kv = dict(x.split("=", 1) for x in line.split())
+        kernels.append({k: (v if k == "kernel" else int(v)) for k, v in kv.items()})
+    return head, kernels
+
+
+def _batch_info(text, more=()):
+    """The text of yalps_lpbatch_info / yalps_lpsens_info / yalps_lpvar_info as LpBatch.info()'s dict; `more`: further integer
+    keys of the first line."""
+    head, kernels = _info_lines(text)
+    ids = head.get("rerun_lps", "[]").strip("[]")
+    out = {k: int(head.get(k, 0)) for k in ("launches", "reruns", *more)}
+    out.update(rerun_lps=[int(x) for x in ids.split(",") if x], kernels=kernels, text=text)
+    return out
+
+
+# yalps_lpbatch_* and yalps_lpsens_*: validate, solve, solution, tableau
+_LP_SIGS = {"validate": (_I32, [_I32, _VP, _VP, _VP, _VP, _VP]),
+            "solve": (_I32, [_VP, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I32, _VP, _VP, _VP, C.POINTER(C.c_float)]),
+            "solution": (_I32, [_VP, _I32, _VP, _VP, _VP]), "tableau": (_I32, [_VP, _I32, _VP])}
+
+
+_BATCH_LIBS["yalps_lpbatch"] = (LPBATCH_LIB_PATH, {
+    **_LP_SIGS, "class": (_I32, [_I32, _I32]), "lds_bytes": (_I64, [_I32, _I32]), "aux_hbm": (_I32, [_I32, _I32])})
 
 
 def lpbatch_lib():
-    global _lpbatch_lib
-    if _lpbatch_lib is None:
-        if not os.path.exists(LPBATCH_LIB_PATH):
-            raise NativeError(f"{LPBATCH_LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
-                              "(there is no CPU fallback)")
-        L = C.CDLL(LPBATCH_LIB_PATH)
-        vp, i32, f64p = C.c_void_p, C.c_int32, C.POINTER(C.c_double)
-        L.yalps_lpbatch_last_error.restype = C.c_char_p
-        L.yalps_lpbatch_create.restype = i32
-        L.yalps_lpbatch_create.argtypes = [i32, vp, C.POINTER(vp)]
-        L.yalps_lpbatch_destroy.restype = None
-        L.yalps_lpbatch_destroy.argtypes = [vp]
-        L.yalps_lpbatch_class.restype = i32
-        L.yalps_lpbatch_class.argtypes = [i32, i32]
-        L.yalps_lpbatch_lds_bytes.restype = C.c_int64
-        L.yalps_lpbatch_lds_bytes.argtypes = [i32, i32]
-        L.yalps_lpbatch_aux_hbm.restype = i32
-        L.yalps_lpbatch_aux_hbm.argtypes = [i32, i32]
-        L.yalps_lpbatch_validate.restype = i32
-        L.yalps_lpbatch_validate.argtypes = [i32, vp, vp, vp, vp, vp]
-        L.yalps_lpbatch_solve.restype = i32
-        L.yalps_lpbatch_solve.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, C.POINTER(C.c_float)]
-        L.yalps_lpbatch_solution.restype = i32
-        L.yalps_lpbatch_solution.argtypes = [vp, i32, vp, vp, vp]
-        L.yalps_lpbatch_tableau.restype = i32
-        L.yalps_lpbatch_tableau.argtypes = [vp, i32, vp]
-        L.yalps_lpbatch_info.restype = i32
-        L.yalps_lpbatch_info.argtypes = [vp, C.c_char_p, i32]
-        _lpbatch_lib = L
-    return _lpbatch_lib
+    return _load_lib("yalps_lpbatch")
 
 
 def lpbatch_check(rc):
-    if rc < 0:
-        raise NativeError("yalps_lpbatch error %d: %s" % (rc, lpbatch_lib().yalps_lpbatch_last_error().decode()))
-    return rc
+    return _check("yalps_lpbatch", rc)
 
 
 def lpbatch_class(width, height):
@@ -600,11 +639,14 @@ def dense_cells(matrix, width, height):
 
 class LpBatch:
     """Many independent LPs per call, one workgroup per LP (yalps_lpbatch_*).  Belongs to one thread at a time."""
+    _prefix = "yalps_lpbatch"
+
+    def _call(self, name, *args):
+        return _check(self._prefix, getattr(_load_lib(self._prefix), "%s_%s" % (self._prefix, name))(*args))
 
     def __init__(self, device=0, stream=None):
         self.handle = C.c_void_p()
-        lpbatch_check(lpbatch_lib().yalps_lpbatch_create(device, C.c_void_p(stream) if stream is not None else None,
-                                                         C.byref(self.handle)))
+        self._call("create", device, C.c_void_p(stream) if stream is not None else None, C.byref(self.handle))
         self.packed = None
 
     def solve(self, lps, keep_tableaux=False):
@@ -613,16 +655,15 @@ class LpBatch:
         n = p.count
         st, res, piv, ms = np.empty(n, np.int32), np.empty(n, np.float64), np.empty(n, np.int64), C.c_float()
         self.packed = None
-        lpbatch_check(lpbatch_lib().yalps_lpbatch_solve(
-            self.handle, n, p.width.ctypes.data, p.height.ctypes.data, p.offsets.ctypes.data, p.row.ctypes.data,
-            p.col.ctypes.data, p.val.ctypes.data, p.precision.ctypes.data, p.max_pivots.ctypes.data, p.check_cycles.ctypes.data,
-            int(bool(keep_tableaux)), st.ctypes.data, res.ctypes.data, piv.ctypes.data, C.byref(ms)))
+        self._call("solve", self.handle, n, p.width.ctypes.data, p.height.ctypes.data, p.offsets.ctypes.data, p.row.ctypes.data,
+                   p.col.ctypes.data, p.val.ctypes.data, p.precision.ctypes.data, p.max_pivots.ctypes.data, p.check_cycles.ctypes.data,
+                   int(bool(keep_tableaux)), st.ctypes.data, res.ctypes.data, piv.ctypes.data, C.byref(ms))
         self.packed = p
         return [STATUS[k] for k in st], res, piv, ms.value
 
     def _shape(self, i):
         if self.packed is None or not 0 <= i < self.packed.count:
-            raise NativeError("LpBatch: no such LP in the last solve: %r" % (i,))
+            raise NativeError("%s: no such LP in the last solve: %r" % (type(self).__name__, i))
         return int(self.packed.width[i]), int(self.packed.height[i])
 
     def solution(self, i):
@@ -630,78 +671,37 @@ class LpBatch:
         w, h = self._shape(i)
         col0 = np.empty(h, np.float64)
         pos, var = np.empty(w + h, np.int32), np.empty(w + h, np.int32)
-        lpbatch_check(lpbatch_lib().yalps_lpbatch_solution(self.handle, i, col0.ctypes.data, pos.ctypes.data, var.ctypes.data))
+        self._call("solution", self.handle, i, col0.ctypes.data, pos.ctypes.data, var.ctypes.data)
         return col0, pos, var
 
     def tableau(self, i):
         """The whole final matrix of LP i of the last solve (solve(..., keep_tableaux=True)), flat row-major."""
         w, h = self._shape(i)
         m = np.empty(w * h, np.float64)
-        lpbatch_check(lpbatch_lib().yalps_lpbatch_tableau(self.handle, i, m.ctypes.data))
+        self._call("tableau", self.handle, i, m.ctypes.data)
         return m
 
     def info(self):
         """{"launches": n, "reruns": n, "rerun_lps": [...], "kernels": [{kernel, class, lps, grid, lds, pass, hist_cap}], "text"}"""
-        buf = C.create_string_buffer(1 << 12)
-        need = lpbatch_check(lpbatch_lib().yalps_lpbatch_info(self.handle, buf, len(buf)))
-        if need >= len(buf):  # (the text names every rerun LP: as long as the batch makes it)
-            buf = C.create_string_buffer(need + 1)
-            lpbatch_check(lpbatch_lib().yalps_lpbatch_info(self.handle, buf, len(buf)))
-        text = buf.value.decode()
-        lines = text.splitlines()
-        head = dict(kv.split("=", 1) for kv in lines[0].split()) if lines else {}
-        ids = head.get("rerun_lps", "[]").strip("[]")
-        kernels = []
-        for line in lines[1:]:
-            kv = dict(x.split("=", 1) for x in line.split())
-            kernels.append({k: (v if k == "kernel" else int(v)) for k, v in kv.items()})
-        return {"launches": int(head.get("launches", 0)), "reruns": int(head.get("reruns", 0)),
-                "rerun_lps": [int(x) for x in ids.split(",") if x], "kernels": kernels, "text": text}
+        return _batch_info(_info_text(self._prefix, self.handle))
 
     def close(self):
         if self.handle:
-            lpbatch_lib().yalps_lpbatch_destroy(self.handle)
+            getattr(_load_lib(self._prefix), self._prefix + "_destroy")(self.handle)
             self.handle = C.c_void_p()
 
 
 # ---------------------------------------------------------------------------------------------- libyalps_lpsens.so
 
-_lpsens_lib = None
+_BATCH_LIBS["yalps_lpsens"] = (LPSENS_LIB_PATH, {**_LP_SIGS, "ranges": (_I32, [_VP, _I32, _VP, _VP, _VP, _VP, _VP])})
 
 
 def lpsens_lib():
-    global _lpsens_lib
-    if _lpsens_lib is None:
-        if not os.path.exists(LPSENS_LIB_PATH):
-            raise NativeError(f"{LPSENS_LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
-                              "(there is no CPU fallback)")
-        L = C.CDLL(LPSENS_LIB_PATH)
-        vp, i32 = C.c_void_p, C.c_int32
-        L.yalps_lpsens_last_error.restype = C.c_char_p
-        L.yalps_lpsens_create.restype = i32
-        L.yalps_lpsens_create.argtypes = [i32, vp, C.POINTER(vp)]
-        L.yalps_lpsens_destroy.restype = None
-        L.yalps_lpsens_destroy.argtypes = [vp]
-        L.yalps_lpsens_validate.restype = i32
-        L.yalps_lpsens_validate.argtypes = [i32, vp, vp, vp, vp, vp]
-        L.yalps_lpsens_solve.restype = i32
-        L.yalps_lpsens_solve.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, C.POINTER(C.c_float)]
-        L.yalps_lpsens_solution.restype = i32
-        L.yalps_lpsens_solution.argtypes = [vp, i32, vp, vp, vp]
-        L.yalps_lpsens_tableau.restype = i32
-        L.yalps_lpsens_tableau.argtypes = [vp, i32, vp]
-        L.yalps_lpsens_ranges.restype = i32
-        L.yalps_lpsens_ranges.argtypes = [vp, i32, vp, vp, vp, vp, vp]
-        L.yalps_lpsens_info.restype = i32
-        L.yalps_lpsens_info.argtypes = [vp, C.c_char_p, i32]
-        _lpsens_lib = L
-    return _lpsens_lib
+    return _load_lib("yalps_lpsens")
 
 
 def lpsens_check(rc):
-    if rc < 0:
-        raise NativeError("yalps_lpsens error %d: %s" % (rc, lpsens_lib().yalps_lpsens_last_error().decode()))
-    return rc
+    return _check("yalps_lpsens", rc)
 
 
 def lpsens_validate(packed):
@@ -710,48 +710,11 @@ def lpsens_validate(packed):
                                                     packed.offsets.ctypes.data, packed.row.ctypes.data, packed.col.ctypes.data))
 
 
-class LpSens:
+class LpSens(LpBatch):
     """LpBatch's interface over yalps_lpsens_*, plus ranges(i): many independent LPs per call, one workgroup per LP, and for
-    every LP that ends optimal the five ranging arrays of its final tableau.  Belongs to one thread at a time."""
-
-    def __init__(self, device=0, stream=None):
-        self.handle = C.c_void_p()
-        lpsens_check(lpsens_lib().yalps_lpsens_create(device, C.c_void_p(stream) if stream is not None else None,
-                                                      C.byref(self.handle)))
-        self.packed = None
-
-    def solve(self, lps, keep_tableaux=False):
-        """lps: a PackedLps or the sequence it is made from.  Returns (status names, results, pivot counts, gpu_ms)."""
-        p = lps if isinstance(lps, PackedLps) else PackedLps(lps)
-        n = p.count
-        st, res, piv, ms = np.empty(n, np.int32), np.empty(n, np.float64), np.empty(n, np.int64), C.c_float()
-        self.packed = None
-        lpsens_check(lpsens_lib().yalps_lpsens_solve(
-            self.handle, n, p.width.ctypes.data, p.height.ctypes.data, p.offsets.ctypes.data, p.row.ctypes.data,
-            p.col.ctypes.data, p.val.ctypes.data, p.precision.ctypes.data, p.max_pivots.ctypes.data, p.check_cycles.ctypes.data,
-            int(bool(keep_tableaux)), st.ctypes.data, res.ctypes.data, piv.ctypes.data, C.byref(ms)))
-        self.packed = p
-        return [STATUS[k] for k in st], res, piv, ms.value
-
-    def _shape(self, i):
-        if self.packed is None or not 0 <= i < self.packed.count:
-            raise NativeError("LpSens: no such LP in the last solve: %r" % (i,))
-        return int(self.packed.width[i]), int(self.packed.height[i])
-
-    def solution(self, i):
-        """(col0, positionOfVariable, variableAtPosition) of LP i of the last solve."""
-        w, h = self._shape(i)
-        col0 = np.empty(h, np.float64)
-        pos, var = np.empty(w + h, np.int32), np.empty(w + h, np.int32)
-        lpsens_check(lpsens_lib().yalps_lpsens_solution(self.handle, i, col0.ctypes.data, pos.ctypes.data, var.ctypes.data))
-        return col0, pos, var
-
-    def tableau(self, i):
-        """The whole final matrix of LP i of the last solve (solve(..., keep_tableaux=True)), flat row-major."""
-        w, h = self._shape(i)
-        m = np.empty(w * h, np.float64)
-        lpsens_check(lpsens_lib().yalps_lpsens_tableau(self.handle, i, m.ctypes.data))
-        return m
+    every LP that ends optimal the five ranging arrays of its final tableau.  Belongs to one thread at a time.
+    info() spells the kernels lp_sens_kernel<T[,check][,lds]>."""
+    _prefix = "yalps_lpsens"
 
     def ranges(self, i):
         """(row0, col_up, col_dn, row_lo, row_hi) of LP i of the last solve, which must have ended optimal (NativeError
@@ -759,75 +722,26 @@ class LpSens:
         w, h = self._shape(i)
         row0, col_up, col_dn = np.empty(w, np.float64), np.empty(w, np.float64), np.empty(w, np.float64)
         row_lo, row_hi = np.empty(h, np.float64), np.empty(h, np.float64)
-        lpsens_check(lpsens_lib().yalps_lpsens_ranges(self.handle, i, row0.ctypes.data, col_up.ctypes.data, col_dn.ctypes.data,
-                                                      row_lo.ctypes.data, row_hi.ctypes.data))
+        self._call("ranges", self.handle, i, row0.ctypes.data, col_up.ctypes.data, col_dn.ctypes.data, row_lo.ctypes.data,
+                   row_hi.ctypes.data)
         return row0, col_up, col_dn, row_lo, row_hi
-
-    def info(self):
-        """LpBatch.info()'s dict; the kernels are spelled lp_sens_kernel<T[,check][,lds]>."""
-        buf = C.create_string_buffer(1 << 12)
-        need = lpsens_check(lpsens_lib().yalps_lpsens_info(self.handle, buf, len(buf)))
-        if need >= len(buf):
-            buf = C.create_string_buffer(need + 1)
-            lpsens_check(lpsens_lib().yalps_lpsens_info(self.handle, buf, len(buf)))
-        return _batch_info(buf.value.decode())
-
-    def close(self):
-        if self.handle:
-            lpsens_lib().yalps_lpsens_destroy(self.handle)
-            self.handle = C.c_void_p()
-
-
-def _batch_info(text):
-    """The text of yalps_lpsens_info (yalps_lpbatch_info's format) as LpBatch.info()'s dict."""
-    lines = text.splitlines()
-    head = dict(kv.split("=", 1) for kv in lines[0].split()) if lines else {}
-    ids = head.get("rerun_lps", "[]").strip("[]")
-    kernels = []
-    for line in lines[1:]:
-        kv = dict(x.split("=", 1) for x in line.split())
-        kernels.append({k: (v if k == "kernel" else int(v)) for k, v in kv.items()})
-    return {"launches": int(head.get("launches", 0)), "reruns": int(head.get("reruns", 0)),
-            "rerun_lps": [int(x) for x in ids.split(",") if x], "kernels": kernels, "text": text}
 
 
 # ---------------------------------------------------------------------------------------------- libyalps_lpvar.so
 
-_lpvar_lib = None
+_BATCH_LIBS["yalps_lpvar"] = (LPVAR_LIB_PATH, {
+        "validate": (_I32, [_I32, _I32, _I64, _VP, _VP, _I32, _VP, _VP, _VP]),
+        "solve": (_I32, [_VP, _I32, _I32, _I64, _VP, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I32, _VP, _VP, _VP,
+                         C.POINTER(C.c_float)]),
+        "solution": (_I32, [_VP, _I32, _VP, _VP, _VP]), "tableau": (_I32, [_VP, _I32, _VP])})
 
 
 def lpvar_lib():
-    global _lpvar_lib
-    if _lpvar_lib is None:
-        if not os.path.exists(LPVAR_LIB_PATH):
-            raise NativeError(f"{LPVAR_LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
-                              "(there is no CPU fallback)")
-        L = C.CDLL(LPVAR_LIB_PATH)
-        vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
-        L.yalps_lpvar_last_error.restype = C.c_char_p
-        L.yalps_lpvar_create.restype = i32
-        L.yalps_lpvar_create.argtypes = [i32, vp, C.POINTER(vp)]
-        L.yalps_lpvar_destroy.restype = None
-        L.yalps_lpvar_destroy.argtypes = [vp]
-        L.yalps_lpvar_validate.restype = i32
-        L.yalps_lpvar_validate.argtypes = [i32, i32, i64, vp, vp, i32, vp, vp, vp]
-        L.yalps_lpvar_solve.restype = i32
-        L.yalps_lpvar_solve.argtypes = [vp, i32, i32, i64, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp,
-                                        C.POINTER(C.c_float)]
-        L.yalps_lpvar_solution.restype = i32
-        L.yalps_lpvar_solution.argtypes = [vp, i32, vp, vp, vp]
-        L.yalps_lpvar_tableau.restype = i32
-        L.yalps_lpvar_tableau.argtypes = [vp, i32, vp]
-        L.yalps_lpvar_info.restype = i32
-        L.yalps_lpvar_info.argtypes = [vp, C.c_char_p, i32]
-        _lpvar_lib = L
-    return _lpvar_lib
+    return _load_lib("yalps_lpvar")
 
 
 def lpvar_check(rc):
-    if rc < 0:
-        raise NativeError("yalps_lpvar error %d: %s" % (rc, lpvar_lib().yalps_lpvar_last_error().decode()))
-    return rc
+    return _check("yalps_lpvar", rc)
 
 
 class PackedVariants:
@@ -914,22 +828,7 @@ class LpVariants:
     def info(self):
         """{"launches", "reruns", "rerun_lps": [...], "base_cells", "patch_cells", "image_bytes",
         "kernels": [{kernel, class, aux, lps, grid, lds, pass, hist_cap}], "text"}"""
-        buf = C.create_string_buffer(1 << 12)
-        need = lpvar_check(lpvar_lib().yalps_lpvar_info(self.handle, buf, len(buf)))
-        if need >= len(buf):  # (the text names every rerun variant: as long as the call makes it)
-            buf = C.create_string_buffer(need + 1)
-            lpvar_check(lpvar_lib().yalps_lpvar_info(self.handle, buf, len(buf)))
-        text = buf.value.decode()
-        lines = text.splitlines()
-        head = dict(kv.split("=", 1) for kv in lines[0].split()) if lines else {}
-        ids = head.get("rerun_lps", "[]").strip("[]")
-        kernels = []
-        for line in lines[1:]:
-            kv = dict(x.split("=", 1) for x in line.split())
-            kernels.append({k: (v if k == "kernel" else int(v)) for k, v in kv.items()})
-        out = {k: int(head.get(k, 0)) for k in ("launches", "reruns", "base_cells", "patch_cells", "image_bytes")}
-        out.update(rerun_lps=[int(x) for x in ids.split(",") if x], kernels=kernels, text=text)
-        return out
+        return _batch_info(_info_text("yalps_lpvar", self.handle), more=("base_cells", "patch_cells", "image_bytes"))
 
     def close(self):
         if self.handle:
@@ -939,8 +838,6 @@ class LpVariants:
 
 # ---------------------------------------------------------------------------------------------- libyalps_milpbatch.so
 
-_milpbatch_lib = None
-
 # yalps_milpbatch_eval_fn / yalps_milpbatch_consumed_fn
 MILP_EVAL_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int32),
                            C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_double),
@@ -949,49 +846,21 @@ MILP_CONSUMED_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int32, C.c_double, C.c_int3
                                C.POINTER(C.c_double))
 
 
+_BATCH_LIBS["yalps_milpbatch"] = (MILPBATCH_LIB_PATH, {
+        "roots": (_I32, [_VP, _I32] + [_VP] * 12), "root": (_I32, [_VP, _I32, _VP, _VP, _VP, _VP]),
+        "nodes": (_I32, [_VP, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _I32, _VP, _VP, _VP, _VP]),
+        "validate_nodes": (_I32, [_I32, _VP, _VP, _I32, _VP, _VP, _VP]), "node": (_I32, [_VP, _I32, _VP, _VP, _VP]),
+        "node_tableau": (_I32, [_VP, _I32, _VP]), "solve": (_I32, [_VP, _I32] + [_VP] * 15 + [_I32, _VP, _VP, _VP, _VP]),
+        "validate": (_I32, [_I32, _VP, _VP, _VP, _VP, _I32]), "solution": (_I32, [_VP, _I32, C.POINTER(_I32), _VP, _VP, _VP]),
+        "search": (_I32, [_I32] + [_VP] * 14 + [_I32, MILP_EVAL_FN, MILP_CONSUMED_FN, _VP] + [_VP] * 8)})
+
+
 def milpbatch_lib():
-    global _milpbatch_lib
-    if _milpbatch_lib is None:
-        if not os.path.exists(MILPBATCH_LIB_PATH):
-            raise NativeError(f"{MILPBATCH_LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
-                              "(there is no CPU fallback)")
-        L = C.CDLL(MILPBATCH_LIB_PATH)
-        vp, i32 = C.c_void_p, C.c_int32
-        L.yalps_milpbatch_last_error.restype = C.c_char_p
-        L.yalps_milpbatch_create.restype = i32
-        L.yalps_milpbatch_create.argtypes = [i32, vp, C.POINTER(vp)]
-        L.yalps_milpbatch_destroy.restype = None
-        L.yalps_milpbatch_destroy.argtypes = [vp]
-        L.yalps_milpbatch_roots.restype = i32
-        L.yalps_milpbatch_roots.argtypes = [vp, i32] + [vp] * 12
-        L.yalps_milpbatch_root.restype = i32
-        L.yalps_milpbatch_root.argtypes = [vp, i32, vp, vp, vp, vp]
-        L.yalps_milpbatch_nodes.restype = i32
-        L.yalps_milpbatch_nodes.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
-        L.yalps_milpbatch_validate_nodes.restype = i32
-        L.yalps_milpbatch_validate_nodes.argtypes = [i32, vp, vp, i32, vp, vp, vp]
-        L.yalps_milpbatch_node.restype = i32
-        L.yalps_milpbatch_node.argtypes = [vp, i32, vp, vp, vp]
-        L.yalps_milpbatch_node_tableau.restype = i32
-        L.yalps_milpbatch_node_tableau.argtypes = [vp, i32, vp]
-        L.yalps_milpbatch_solve.restype = i32
-        L.yalps_milpbatch_solve.argtypes = [vp, i32] + [vp] * 15 + [i32, vp, vp, vp, vp]
-        L.yalps_milpbatch_validate.restype = i32
-        L.yalps_milpbatch_validate.argtypes = [i32, vp, vp, vp, vp, i32]
-        L.yalps_milpbatch_solution.restype = i32
-        L.yalps_milpbatch_solution.argtypes = [vp, i32, C.POINTER(i32), vp, vp, vp]
-        L.yalps_milpbatch_search.restype = i32
-        L.yalps_milpbatch_search.argtypes = [i32] + [vp] * 14 + [i32, MILP_EVAL_FN, MILP_CONSUMED_FN, vp] + [vp] * 8
-        L.yalps_milpbatch_info.restype = i32
-        L.yalps_milpbatch_info.argtypes = [vp, C.c_char_p, i32]
-        _milpbatch_lib = L
-    return _milpbatch_lib
+    return _load_lib("yalps_milpbatch")
 
 
 def milpbatch_check(rc):
-    if rc < 0:
-        raise NativeError("yalps_milpbatch error %d: %s" % (rc, milpbatch_lib().yalps_milpbatch_last_error().decode()))
-    return rc
+    return _check("yalps_milpbatch", rc)
 
 
 class PackedMilps:
@@ -1141,19 +1010,9 @@ class MilpBatch:
     def info(self):
         """{"rounds", "launches", "reruns", "gpu_ms", "rerun_nodes": [k | (round, k)], "kernels": [{kernel, class, nodes | lps, grid,
         lds, pass, round, hist_cap}], "text"}"""
-        buf = C.create_string_buffer(1 << 14)
-        need = milpbatch_check(milpbatch_lib().yalps_milpbatch_info(self.handle, buf, len(buf)))
-        if need >= len(buf):
-            buf = C.create_string_buffer(need + 1)
-            milpbatch_check(milpbatch_lib().yalps_milpbatch_info(self.handle, buf, len(buf)))
-        text = buf.value.decode()
-        lines = text.splitlines()
-        head = dict(kv.split("=", 1) for kv in lines[0].split()) if lines else {}
+        text = _info_text("yalps_milpbatch", self.handle, first=1 << 14)
+        head, kernels = _info_lines(text)
         ids = [x for x in head.get("rerun_nodes", "[]").strip("[]").split(",") if x]
-        kernels = []
-        for line in lines[1:]:
-            kv = dict(x.split("=", 1) for x in line.split())
-            kernels.append({k: (v if k == "kernel" else int(v)) for k, v in kv.items()})
         return {"rounds": int(head.get("rounds", 0)), "launches": int(head.get("launches", 0)), "reruns": int(head.get("reruns", 0)),
                 "gpu_ms": int(head.get("gpu_us", 0)) / 1000.0,
                 "rerun_nodes": [tuple(int(y) for y in x.split(":")) if ":" in x else int(x) for x in ids], "kernels": kernels, "text": text}

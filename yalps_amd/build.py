@@ -23,11 +23,12 @@ HIP_SRC = os.path.join(CSRC, "yalps_hip.hip")  # host side + C ABI + the launch-
 # the persistent kernels' instantiations, one translation unit per group: compiled side by side (the device compile of
 # ~40 register-heavy kernels in one unit took 2.5 minutes)
 HIP_UNITS = [HIP_SRC] + [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.startswith("persistent_") and f.endswith(".hip")]
-HIP_DEPS = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith((".cuh", ".inc", ".h")) and not f.startswith(("lp_batch", "lp_variants", "lp_sens", "milp_node"))]
+HIP_DEPS = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith((".cuh", ".inc", ".h")) and not f.startswith(("lp_batch", "lp_variants", "lp_sens", "milp_node", "wg_queue"))]
 # the batch library: one translation unit of its own around the shared workgroup loop, never linked into libyalps_hip.so
 LIB_LPBATCH = os.path.join(HERE, "libyalps_lpbatch.so")
 LPBATCH_SRC = os.path.join(CSRC, "lp_batch.hip")
-LPBATCH_DEPS = [os.path.join(CSRC, f) for f in ("lp_batch_kernel.cuh", "lp_batch_host.inc", "wg_simplex.cuh", "common.cuh")]
+QUEUE_DEPS = [os.path.join(CSRC, f) for f in ("wg_queue.cuh", "wg_queue_host.inc", "wg_simplex.cuh", "common.cuh")]  # the queue body and the host pass of all four
+LPBATCH_DEPS = [os.path.join(CSRC, f) for f in ("lp_batch_kernel.cuh", "lp_batch_host.inc", "lp_batch_lib.inc")] + QUEUE_DEPS
 LPBATCH_HEADER = os.path.join(ROOT, "include", "yalps_lpbatch.h")
 # the MILP batch library: the LP batch's root pass compiled again next to milp_node_kernel and the lockstep driver
 LIB_MILPBATCH = os.path.join(HERE, "libyalps_milpbatch.so")
@@ -37,12 +38,12 @@ MILPBATCH_HEADER = os.path.join(ROOT, "include", "yalps_milpbatch.h")
 # the variants library: a shared base image plus per-variant patches, one translation unit around the same workgroup loop
 LIB_LPVAR = os.path.join(HERE, "libyalps_lpvar.so")
 LPVAR_SRC = os.path.join(CSRC, "lp_variants.hip")
-LPVAR_DEPS = [os.path.join(CSRC, f) for f in ("lp_variants_kernel.cuh", "wg_simplex.cuh", "common.cuh")]
+LPVAR_DEPS = [os.path.join(CSRC, "lp_variants_kernel.cuh")] + QUEUE_DEPS
 LPVAR_HEADER = os.path.join(ROOT, "include", "yalps_lpvar.h")
-# the sensitivity library: the LP batch's host code compiled again around lp_sens_kernel (lp_batch_kernel plus a ranging epilogue)
+# the sensitivity library: the LP batch's host code around lp_sens_kernel (lp_batch_kernel's job plus a ranging epilogue)
 LIB_LPSENS = os.path.join(HERE, "libyalps_lpsens.so")
 LPSENS_SRC = os.path.join(CSRC, "lp_sens.hip")
-LPSENS_DEPS = [os.path.join(CSRC, f) for f in ("lp_sens_kernel.cuh", "lp_batch_host.inc", "wg_simplex.cuh", "common.cuh")]
+LPSENS_DEPS = [os.path.join(CSRC, "lp_sens_kernel.cuh")] + LPBATCH_DEPS
 LPSENS_HEADER = os.path.join(ROOT, "include", "yalps_lpsens.h")
 OBJ_DIR = os.path.join(HERE, "build")
 HEADER = os.path.join(ROOT, "include", "yalps_hip.h")
@@ -163,82 +164,49 @@ def build_hip(force=False, verbose=False, stamps=False):
     return lib_out
 
 
-def build_lpbatch(force=False, verbose=False):
-    """libyalps_lpbatch.so: lp_batch.hip alone (it includes common.cuh / wg_simplex.cuh itself), same flags as the main library."""
-    if not force and not _stale(LIB_LPBATCH, LPBATCH_HEADER, LPBATCH_SRC, *LPBATCH_DEPS):
-        return LIB_LPBATCH
+def build_single_unit(src, out, deps, header, kernels, force=False, verbose=False):
+    """A library of one translation unit (it includes common.cuh / wg_simplex.cuh itself), same flags as the main library;
+    `kernels`: the kernel names its code object must hold."""
+    if not force and not _stale(out, header, src, *deps):
+        return out
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     os.makedirs(OBJ_DIR, exist_ok=True)
-    obj = os.path.join(OBJ_DIR, "lp_batch.o")
-    for cmd in ([hipcc, *HIPCC_FLAGS, "-c", "-o", obj, LPBATCH_SRC],
-                [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB_LPBATCH + ".tmp", obj]):
+    obj = os.path.join(OBJ_DIR, os.path.basename(src)[:-4] + ".o")
+    for cmd in ([hipcc, *HIPCC_FLAGS, "-c", "-o", obj, src],
+                [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out + ".tmp", obj]):
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.run(cmd, check=True)
-    ks = check_register_budgets(LIB_LPBATCH + ".tmp", min_resident=0)
-    if not any("lp_batch_kernel" in k for k in ks):
-        raise RuntimeError("no lp_batch_kernel in the code object of %s" % LIB_LPBATCH)
-    os.replace(LIB_LPBATCH + ".tmp", LIB_LPBATCH)
-    return LIB_LPBATCH
+    ks = check_register_budgets(out + ".tmp", min_resident=0)
+    for kernel in kernels:
+        if not any(kernel in k for k in ks):
+            raise RuntimeError("no %s in the code object of %s" % (kernel, out))
+    os.replace(out + ".tmp", out)
+    return out
+
+
+def build_lpbatch(force=False, verbose=False):
+    """libyalps_lpbatch.so: lp_batch.hip alone."""
+    return build_single_unit(LPBATCH_SRC, LIB_LPBATCH, LPBATCH_DEPS, LPBATCH_HEADER,
+                             ("lp_batch_kernel",), force, verbose)
 
 
 def build_milpbatch(force=False, verbose=False):
-    """libyalps_milpbatch.so: milp_batch.hip alone, same flags as the other two libraries."""
-    if not force and not _stale(LIB_MILPBATCH, MILPBATCH_HEADER, MILPBATCH_SRC, *MILPBATCH_DEPS):
-        return LIB_MILPBATCH
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    os.makedirs(OBJ_DIR, exist_ok=True)
-    obj = os.path.join(OBJ_DIR, "milp_batch.o")
-    for cmd in ([hipcc, *HIPCC_FLAGS, "-c", "-o", obj, MILPBATCH_SRC],
-                [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB_MILPBATCH + ".tmp", obj]):
-        if verbose:
-            print(" ".join(cmd), flush=True)
-        subprocess.run(cmd, check=True)
-    ks = check_register_budgets(LIB_MILPBATCH + ".tmp", min_resident=0)
-    for kernel in ("milp_node_kernel", "lp_batch_kernel"):
-        if not any(kernel in k for k in ks):
-            raise RuntimeError("no %s in the code object of %s" % (kernel, LIB_MILPBATCH))
-    os.replace(LIB_MILPBATCH + ".tmp", LIB_MILPBATCH)
-    return LIB_MILPBATCH
+    """libyalps_milpbatch.so: milp_batch.hip alone."""
+    return build_single_unit(MILPBATCH_SRC, LIB_MILPBATCH, MILPBATCH_DEPS, MILPBATCH_HEADER,
+                             ("milp_node_kernel", "lp_batch_kernel"), force, verbose)
 
 
 def build_lpvar(force=False, verbose=False):
-    """libyalps_lpvar.so: lp_variants.hip alone, same flags as the other libraries."""
-    if not force and not _stale(LIB_LPVAR, LPVAR_HEADER, LPVAR_SRC, *LPVAR_DEPS):
-        return LIB_LPVAR
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    os.makedirs(OBJ_DIR, exist_ok=True)
-    obj = os.path.join(OBJ_DIR, "lp_variants.o")
-    for cmd in ([hipcc, *HIPCC_FLAGS, "-c", "-o", obj, LPVAR_SRC],
-                [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB_LPVAR + ".tmp", obj]):
-        if verbose:
-            print(" ".join(cmd), flush=True)
-        subprocess.run(cmd, check=True)
-    ks = check_register_budgets(LIB_LPVAR + ".tmp", min_resident=0)
-    for kernel in ("lp_variants_kernel", "lp_variants_base_kernel"):
-        if not any(kernel in k for k in ks):
-            raise RuntimeError("no %s in the code object of %s" % (kernel, LIB_LPVAR))
-    os.replace(LIB_LPVAR + ".tmp", LIB_LPVAR)
-    return LIB_LPVAR
+    """libyalps_lpvar.so: lp_variants.hip alone."""
+    return build_single_unit(LPVAR_SRC, LIB_LPVAR, LPVAR_DEPS, LPVAR_HEADER,
+                             ("lp_variants_kernel", "lp_variants_base_kernel"), force, verbose)
 
 
 def build_lpsens(force=False, verbose=False):
-    """libyalps_lpsens.so: lp_sens.hip alone, same flags as the other libraries."""
-    if not force and not _stale(LIB_LPSENS, LPSENS_HEADER, LPSENS_SRC, *LPSENS_DEPS):
-        return LIB_LPSENS
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    os.makedirs(OBJ_DIR, exist_ok=True)
-    obj = os.path.join(OBJ_DIR, "lp_sens.o")
-    for cmd in ([hipcc, *HIPCC_FLAGS, "-c", "-o", obj, LPSENS_SRC],
-                [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB_LPSENS + ".tmp", obj]):
-        if verbose:
-            print(" ".join(cmd), flush=True)
-        subprocess.run(cmd, check=True)
-    ks = check_register_budgets(LIB_LPSENS + ".tmp", min_resident=0)
-    if not any("lp_sens_kernel" in k for k in ks):
-        raise RuntimeError("no lp_sens_kernel in the code object of %s" % LIB_LPSENS)
-    os.replace(LIB_LPSENS + ".tmp", LIB_LPSENS)
-    return LIB_LPSENS
+    """libyalps_lpsens.so: lp_sens.hip alone."""
+    return build_single_unit(LPSENS_SRC, LIB_LPSENS, LPSENS_DEPS, LPSENS_HEADER,
+                             ("lp_sens_kernel",), force, verbose)
 
 
 def build_napi(force=False, verbose=False):

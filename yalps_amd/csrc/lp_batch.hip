@@ -1,6 +1,7 @@
 // lp_batch.hip -- libyalps_lpbatch.so: a batch of independent LPs in one call (include/yalps_lpbatch.h)
-// C ABI + the lp_batch_kernel instantiations; the host side is lp_batch_host.inc (shared with milp_batch.hip).  A library of its own: nothing here is linked into
-// libyalps_hip.so, and the pivot loop is that library's wg_simplex.cuh, included unchanged.
+// C ABI + the lp_batch_kernel instantiations; the host side is lp_batch_host.inc on wg_queue_host.inc (shared with milp_batch.hip
+// and lp_sens.hip).  A library of its own: nothing here is linked into libyalps_hip.so, and the pivot loop is that library's
+// wg_simplex.cuh, included unchanged.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -22,9 +23,11 @@ namespace {
 
 #include "wg_simplex.cuh"
 #include "lp_batch_kernel.cuh"
+#include "wg_queue_host.inc"
+#include "lp_batch_host.inc"
 } // namespace
 
-#include "lp_batch_host.inc"
+#include "lp_batch_lib.inc"
 
 extern "C" {
 
@@ -42,57 +45,37 @@ int32_t yalps_lpbatch_aux_hbm(int32_t width, int32_t height) {
 
 int32_t yalps_lpbatch_validate(int32_t count, const int32_t *width, const int32_t *height, const int64_t *cell_offsets,
                                const int32_t *row, const int32_t *col) {
-    return validate(count, width, height, cell_offsets, row, col);
+    return lp_validate<LpBatchLib>(count, width, height, cell_offsets, row, col);
 }
 
 int32_t yalps_lpbatch_create(int32_t device, void *hip_stream, yalps_lpbatch **out) {
     if (!out) return fail(YALPS_E_ARG, "yalps_lpbatch_create: out is NULL");
-    return lpbatch_create(device, hip_stream, out);
+    return lp_create(device, hip_stream, out);
 }
 
-void yalps_lpbatch_destroy(yalps_lpbatch *b) { lpbatch_destroy_impl(b); }
+void yalps_lpbatch_destroy(yalps_lpbatch *b) { lp_destroy(b); }
 
 int32_t yalps_lpbatch_solve(yalps_lpbatch *b, int32_t count, const int32_t *width, const int32_t *height,
                             const int64_t *cell_offsets, const int32_t *row, const int32_t *col, const double *val,
                             const double *precision, const double *maxPivots, const int32_t *checkCycles,
                             int32_t keep_tableaux, int32_t *status_out, double *result_out, int64_t *pivots_out,
                             float *gpu_ms_out) {
-    if (!b) return fail(YALPS_E_ARG, "yalps_lpbatch_solve: handle is NULL");
-    const int32_t rc = solve_impl(b, count, width, height, cell_offsets, row, col, val, precision, maxPivots, checkCycles,
-                                  keep_tableaux, status_out, result_out, pivots_out, gpu_ms_out);
-    if (rc) b->descs.clear(); // (no last solve to read from)
-    return rc;
+    return lp_solve<LpBatchLib>(b, "yalps_lpbatch_solve", count, width, height, cell_offsets, row, col, val, precision, maxPivots,
+                                checkCycles, keep_tableaux, status_out, result_out, pivots_out, gpu_ms_out);
 }
 
 int32_t yalps_lpbatch_solution(yalps_lpbatch *b, int32_t i, double *col0, int32_t *positionOfVariable,
                                int32_t *variableAtPosition) {
-    if (!b || i < 0 || (size_t)i >= b->descs.size()) return fail(YALPS_E_ARG, "yalps_lpbatch_solution: no such LP in the last solve");
-    const LpDesc &d = b->descs[(size_t)i];
-    const size_t np = (size_t)d.w + (size_t)d.h;
-    if (col0) std::memcpy(col0, b->h_col0.data() + d.col0_off, sizeof(double) * (size_t)d.h);
-    if (positionOfVariable) std::memcpy(positionOfVariable, b->h_pos.data() + d.perm_off, sizeof(int32_t) * np);
-    if (variableAtPosition) std::memcpy(variableAtPosition, b->h_var.data() + d.perm_off, sizeof(int32_t) * np);
-    return 0;
+    return lp_solution<LpBatchLib>(b, "yalps_lpbatch_solution", i, col0, positionOfVariable, variableAtPosition);
 }
 
 int32_t yalps_lpbatch_tableau(yalps_lpbatch *b, int32_t i, double *matrix) {
-    if (!b || i < 0 || (size_t)i >= b->descs.size() || !matrix)
-        return fail(YALPS_E_ARG, "yalps_lpbatch_tableau: no such LP in the last solve");
-    if (!b->keep) return fail(YALPS_E_ARG, "yalps_lpbatch_tableau: the last solve did not keep its tableaux (keep_tableaux)");
-    const LpDesc &d = b->descs[(size_t)i];
-    HIP_TRY(hipSetDevice(b->device));
-    HIP_TRY(hipMemcpyAsync(matrix, static_cast<const double *>(b->tab.p) + d.tab_off, sizeof(double) * (size_t)d.w * (size_t)d.h,
-                           hipMemcpyDeviceToHost, b->stream));
-    HIP_TRY(hipStreamSynchronize(b->stream));
-    return 0;
+    return lp_tableau<LpBatchLib>(b, "yalps_lpbatch_tableau", i, matrix);
 }
 
 int32_t yalps_lpbatch_info(const yalps_lpbatch *b, char *buf, int32_t len) {
     if (!b || !buf || len < 1) return fail(YALPS_E_ARG, "yalps_lpbatch_info: bad argument");
-    const size_t n = std::min(b->info.size(), (size_t)len - 1);
-    std::memcpy(buf, b->info.data(), n);
-    buf[n] = 0;
-    return (int32_t)std::min<size_t>(b->info.size(), INT32_MAX); // (the whole text's length: >= len means it was cut)
+    return info_out(b->info, buf, len);
 }
 
 } // extern "C"

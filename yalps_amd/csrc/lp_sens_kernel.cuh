@@ -1,10 +1,11 @@
 // lp_sens_kernel.cuh -- lp_batch_kernel plus a ranging epilogue over the final tableau of every LP that ended optimal
 // Part of libyalps_lpsens.so; included by lp_sens.hip inside its anonymous namespace (gfx950 only).
 #pragma once
+#include "lp_batch_kernel.cuh"
 
 // ------------------------------------------------------------------------------------------
-// lp_sens_kernel: lp_batch_kernel's body (lp_batch_kernel.cuh: the work queue, the barriers, the assembly from cells,
-// wg_simplex unchanged), and between wg_simplex and the last barrier of an LP that ended "optimal" two passes over the
+// lp_sens_kernel: lp_batch_kernel's job on wg_queue (lp_batch_kernel.cuh: the assembly from cells; wg_queue.cuh: the work
+// queue, the barriers, wg_simplex unchanged), and between wg_simplex and the last barrier of an LP that ended "optimal" two passes over the
 // final matrix M where it lies (LDS in the LDS form, the workgroup's HBM workspace in the HBM form), p = the LP's precision:
 //   row0[c]   = M[0,c]                                                        c = 0 .. w-1
 //   col_up[c] = min{ M[r,0] /  M[r,c] : 1 <= r < h, M[r,c] >  p }             c = 1 .. w-1   (+inf where empty)
@@ -18,34 +19,7 @@
 // straight to the LP's slice of the output.  Columns 1 .. w-1 only: the padding column of an odd n is never read.
 // The LP's slice: sens[3 * perm_off ..) = row0[w] col_up[w] col_dn[w] row_lo[h] row_hi[h].
 // ------------------------------------------------------------------------------------------
-struct LpDesc {
-    int32_t w, h;
-    long long cell_lo, cell_hi;   // the LP's cells in the packed row / col / val arrays
-    long long col0_off;           // column 0 at col0[col0_off .. + h)
-    long long perm_off;           // the permutations at pos / var[perm_off .. + w + h); the ranges at sens[3 * perm_off ..)
-    long long tab_off;            // keep_tableaux: the final matrix, row-major w * h, at tab[tab_off ..)
-    double precision, max_pivots;
-    int32_t aux_hbm;              // HBM form: colbuf / prow behind the tableau in the workspace (too long for the LDS block)
-    int32_t pad_;
-};
-
-struct LpLaunch {
-    const LpDesc *desc;           // [LPs of the batch]
-    const int32_t *order;         // [count] LP indices of this launch, largest first
-    int32_t count;
-    unsigned int *counter;        // next entry of `order` to hand out (zeroed before the launch)
-    const int32_t *row, *col;
-    const double *val;
-    int32_t *status;              // per LP of the batch
-    double *result;
-    long long *pivots;
-    double *col0;
-    int32_t *pos, *var;
-    double *tab;                  // nullptr unless keep_tableaux
-    double *ws;                   // HBM form: [grid][ws_stride]
-    long long ws_stride;
-    int32_t *hist;                // checkCycles: [grid][2][hist_cap] pivot history of the LP a workgroup is solving
-    long long hist_cap;
+struct SensLaunch : LpLaunch {
     double *sens;                 // the ranges of every LP that ends optimal
 };
 
@@ -125,104 +99,17 @@ __device__ __attribute__((noinline)) void sens_epilogue(const double *mat, const
     }
 }
 
-// The dynamic LDS block holds the tableau and prow, which wg_simplex sweeps 16 bytes at a time: it must start on a 16-byte
-// boundary, so the static objects in front of it add up to a multiple of 16 (the queue slot is padded to 16 bytes;
-// build.build_lpsens refuses a library whose kernels' static LDS is not).
-template <int T, bool CHECK, bool LDS>
-__global__ __launch_bounds__(T) void lp_sens_kernel(LpLaunch L) {
-    __shared__ double sk[2][16];
-    __shared__ int si[2][16];
-    __shared__ __attribute__((aligned(16))) unsigned int s_next[4]; // [0]: the queue index this workgroup works on next
-    extern __shared__ __attribute__((aligned(16))) double sh_dyn[];
-    const int tid = threadIdx.x;
-    if (tid == 0) s_next[0] = atomicAdd(L.counter, 1u);
-    __syncthreads();
-    // The loop's top only READS the index; the one lane that fetches the next one does so in the middle of the body, between
-    // two barriers, and the body ends with a barrier.  No per-lane block touches the back edge, so the loop stays uniform
-    // however the compiler threads branches (lp_batch_kernel.cuh tells what happened when one did).  The epilogue keeps to
-    // that: it sits between the outputs and the last barrier, under a condition every lane shares.
-    for (;;) {
-        const unsigned int k = __builtin_amdgcn_readfirstlane(s_next[0]);
-        if (k >= (unsigned int)L.count) return;
-        const int i = L.order[k];
-        const LpDesc *d = L.desc + i;
-        const int w = d->w, h = d->h, n = w - 1;
-        const int pcols = small_pcols(n), lp = LDS ? small_lds_pitch(n) : pcols;
-        const long long cell_lo = d->cell_lo, cell_hi = d->cell_hi, col0_off = d->col0_off, perm_off = d->perm_off;
-        double *mat, *rhs, *colbuf, *prow;
-        int32_t *pos, *var;
-        if (LDS) {
-            mat = sh_dyn;
-            rhs = mat + (size_t)h * lp;
-            colbuf = rhs + h;
-            prow = colbuf + h;
-            pos = reinterpret_cast<int32_t *>(prow + lp);
-            var = pos + ((w + h + 1) & ~1);
-        } else {
-            mat = L.ws + (size_t)blockIdx.x * L.ws_stride;
-            rhs = L.col0 + col0_off;
-            pos = L.pos + perm_off;
-            var = L.var + perm_off;
-            prow = d->aux_hbm ? mat + (size_t)h * lp : sh_dyn;
-            colbuf = prow + lp;
-        }
-        // ---- the initial tableau (src/tableau.ts:87-134): zeros, the written cells, identity permutations ----
-        {
-            double2 *m2 = reinterpret_cast<double2 *>(mat);
-            const size_t units = (size_t)h * lp / 2; // lp is even
-            for (size_t u = tid; u < units; u += T) m2[u] = make_double2(0.0, 0.0);
-            for (int r = tid; r < h; r += T) rhs[r] = 0.0;
-            for (int p = tid; p < w + h; p += T) {
-                pos[p] = p;
-                var[p] = p;
-            }
-        }
-        __syncthreads();
-        for (long long c = cell_lo + tid; c < cell_hi; c += T) {
-            const int r = L.row[c], cc = L.col[c];
-            if ((unsigned)r >= (unsigned)h || (unsigned)cc >= (unsigned)w) continue; // (the host has refused such cells)
-            if (cc == 0)
-                rhs[r] = L.val[c];
-            else
-                mat[(size_t)r * lp + cc - 1] = L.val[c];
-        }
-        __syncthreads();
-        if (tid == 0) s_next[0] = atomicAdd(L.counter, 1u); // (everybody read the slot two barriers ago; read again after the last one)
-
-        int32_t *hist_l = CHECK ? L.hist + (size_t)blockIdx.x * 2 * L.hist_cap : nullptr;
-        const WgResult out = wg_simplex<T, CHECK>(mat, rhs, pos, var, colbuf, prow, sk, si, w, n, lp, pcols, h,
-                                                  wg_unit_lanes(pcols / 2, T), d->precision, d->max_pivots, hist_l,
-                                                  CHECK ? hist_l + L.hist_cap : nullptr, CHECK ? L.hist_cap : 0);
-        __syncthreads();
-        // (checkCycles, history full: no output but the status -- the host grows the history and reruns this LP)
-        const bool done = !(CHECK && out.status == WG_HISTORY_FULL);
-        if (LDS && done) {
-            double *col0 = L.col0 + col0_off;
-            for (int r = tid; r < h; r += T) col0[r] = rhs[r];
-            int32_t *opos = L.pos + perm_off, *ovar = L.var + perm_off;
-            for (int p = tid; p < w + h; p += T) {
-                opos[p] = pos[p];
-                ovar[p] = var[p];
-            }
-        }
-        if (L.tab && done) { // the whole final matrix in the reference's layout (src/tableau.ts:9-21)
-            double *tab = L.tab + d->tab_off;
-            const int Uc = wg_unit_lanes(w, T), cu0 = tid % Uc, cg0 = tid / Uc, CG = T / Uc;
-            for (int r = cg0; r < h; r += CG) {
-                const double *src = mat + (size_t)r * lp;
-                double *dst = tab + (size_t)r * w;
-                for (int c = cu0; c < w; c += Uc) dst[c] = c == 0 ? rhs[r] : src[c - 1];
-            }
-        }
-        if (tid == T - 1) {
-            L.status[i] = out.status;
-            if (done) {
-                L.result[i] = out.result;
-                L.pivots[i] = out.pivots;
-            }
-        }
-        // (last: by now only the tableau itself is still needed, which keeps the epilogue's registers off the solve's)
-        if (out.status == YALPS_OPTIMAL) sens_epilogue<T>(mat, rhs, w, h, lp, d->precision, L.sens + 3 * perm_off);
-        __syncthreads(); // everybody is done with this LP's tableau, and the next index is in its slot
+// lp_batch_kernel's job with the epilogue between the outputs and the last barrier, under a condition every lane shares
+struct SensJob : LpJob {
+    const SensLaunch &S;
+    __device__ __forceinline__ explicit SensJob(const SensLaunch &launch) : LpJob(launch), S(launch) {}
+    template <int T>
+    __device__ __forceinline__ void after(const QueueItem &it, int status, const double *mat, const double *rhs, int lp) const {
+        if (status == YALPS_OPTIMAL) sens_epilogue<T>(mat, rhs, it.w, it.h, lp, d->precision, S.sens + 3 * it.perm_off);
     }
+};
+
+template <int T, bool CHECK, bool LDS>
+__global__ __launch_bounds__(T) void lp_sens_kernel(SensLaunch L) {
+    wg_queue<T, CHECK, LDS>(L, SensJob(L));
 }

@@ -1,6 +1,7 @@
 // lp_variants_kernel.cuh -- many variants of ONE LP: a shared base tableau plus a small patch per variant, one workgroup per variant at a time
 // Part of libyalps_lpvar.so; included by lp_variants.hip inside its anonymous namespace (gfx950 only).
 #pragma once
+#include "wg_queue.cuh"
 
 // ------------------------------------------------------------------------------------------
 // All variants of a call have one shape, so the call has one size class and one *image*: the base tableau, dense, in the
@@ -9,7 +10,7 @@
 // one zero where h is odd, so that the image is a whole number of 16-byte units).
 // lp_variants_base_kernel builds the image once per call; lp_variants_kernel starts every variant from it: a 16-byte copy
 // per lane per step instead of lp_batch_kernel's zero pass plus the scatter of the whole cell list, then the variant's few
-// patch cells on top.  From there on it is lp_batch_kernel: the same work queue, wg_simplex unchanged, the same outputs.
+// patch cells on top.  From there on it is lp_batch_kernel: the same work queue (wg_queue.cuh), wg_simplex unchanged, the same outputs.
 // ------------------------------------------------------------------------------------------
 
 // scatter == 0: zero the image; scatter != 0: write the base cells into it.  Two launches of one kernel, ordered by the
@@ -38,69 +39,34 @@ struct VarDesc {
     double precision, max_pivots;
 };
 
-struct VarLaunch {
-    const VarDesc *desc;          // [variants of the call]
-    const int32_t *order;         // [count] variant indices of this launch
-    int32_t count;
-    unsigned int *counter;        // next entry of `order` to hand out (zeroed before the launch)
-    int32_t w, h;                 // the one shape of the call
+struct VarLaunch : QueueLaunch {
+    const VarDesc *desc;          // [variants of the call]; variant i has column 0 at col0[i * even(h)], the permutations
+    int32_t w, h;                 // at pos / var[i * (w + h)], with keep_tableaux the final matrix at tab[i * w * h]
     int32_t aux_hbm;              // HBM form: colbuf / prow behind the tableau in the workspace (too long for the LDS block)
     const double *image;          // [h * pitch + even(h)] the base tableau in this form's layout
     const int32_t *prow, *pcol;   // the patches
     const double *pval;
-    int32_t *status;              // per variant; variant i has column 0 at col0[i * even(h)], the permutations at
-    double *result;               // pos / var[i * (w + h)], with keep_tableaux the final matrix at tab[i * w * h]
-    long long *pivots;
-    double *col0;
-    int32_t *pos, *var;
-    double *tab;                  // nullptr unless keep_tableaux
-    double *ws;                   // HBM form: [grid][ws_stride]
-    long long ws_stride;
-    int32_t *hist;                // checkCycles: [grid][2][hist_cap] pivot history of the variant a workgroup is solving
-    long long hist_cap;
 };
 
-// Static LDS in front of the dynamic block adds up to a multiple of 16 bytes, as in lp_batch_kernel (the dynamic block holds
-// the tableau and prow, swept 16 bytes at a time; build.build_lpvar refuses a library whose kernels' static LDS is not).
-template <int T, bool CHECK, bool LDS>
-__global__ __launch_bounds__(T) void lp_variants_kernel(VarLaunch L) {
-    __shared__ double sk[2][16];
-    __shared__ int si[2][16];
-    __shared__ __attribute__((aligned(16))) unsigned int s_next[4]; // [0]: the queue index this workgroup works on next
-    extern __shared__ __attribute__((aligned(16))) double sh_dyn[];
-    const int tid = threadIdx.x;
-    const int w = L.w, h = L.h, n = w - 1;
-    const int pcols = small_pcols(n), lp = LDS ? small_lds_pitch(n) : pcols;
-    const int heven = (h + 1) & ~1;
-    if (tid == 0) s_next[0] = atomicAdd(L.counter, 1u);
-    __syncthreads();
-    // The loop's shape is lp_batch_kernel's (see the comment there): the top only READS the index, one lane fetches the next
-    // one in the middle of the body between two barriers, and the body ends with a barrier -- nothing per-lane at the back edge.
-    for (;;) {
-        const unsigned int k = __builtin_amdgcn_readfirstlane(s_next[0]);
-        if (k >= (unsigned int)L.count) return;
-        const int i = L.order[k];
-        const VarDesc *d = L.desc + i;
-        const long long patch_lo = d->patch_lo, patch_hi = d->patch_hi;
-        const size_t col0_off = (size_t)i * heven, perm_off = (size_t)i * ((size_t)w + h);
-        double *mat, *rhs, *colbuf, *prow;
-        int32_t *pos, *var;
-        if (LDS) {
-            mat = sh_dyn;
-            rhs = mat + (size_t)h * lp;
-            colbuf = rhs + h;
-            prow = colbuf + h;
-            pos = reinterpret_cast<int32_t *>(prow + lp);
-            var = pos + ((w + h + 1) & ~1);
-        } else {
-            mat = L.ws + (size_t)blockIdx.x * L.ws_stride;
-            rhs = L.col0 + col0_off;
-            pos = L.pos + perm_off;
-            var = L.var + perm_off;
-            prow = L.aux_hbm ? mat + (size_t)h * lp : sh_dyn;
-            colbuf = prow + lp;
-        }
-        // ---- the initial tableau: the base image, identity permutations (src/tableau.ts:95-98), then the patch ----
+// the initial tableau: the base image, identity permutations (src/tableau.ts:95-98), then the patch
+struct VarJob : QueueJobBase {
+    const VarLaunch &L;
+    const VarDesc *d;
+    long long patch_lo, patch_hi;
+    __device__ __forceinline__ explicit VarJob(const VarLaunch &launch) : L(launch) {}
+    __device__ __forceinline__ QueueItem item(int i) {
+        d = L.desc + i;
+        patch_lo = d->patch_lo;
+        patch_hi = d->patch_hi;
+        const int w = L.w, h = L.h, heven = (h + 1) & ~1;
+        return QueueItem{w, h, (long long)((size_t)i * heven), (long long)((size_t)i * ((size_t)w + h)), L.aux_hbm};
+    }
+    __device__ __forceinline__ double precision() const { return d->precision; }
+    __device__ __forceinline__ double max_pivots() const { return d->max_pivots; }
+    __device__ __forceinline__ long long tab_off(int i, const QueueItem &it) const { return (long long)((size_t)i * it.w * it.h); }
+    template <int T, bool LDS>
+    __device__ __forceinline__ void fill(const QueueItem &it, double *mat, double *rhs, int32_t *pos, int32_t *var, int lp) const {
+        const int tid = threadIdx.x, w = it.w, h = it.h, heven = (h + 1) & ~1;
         {
             const double2 *im2 = reinterpret_cast<const double2 *>(L.image);
             double2 *m2 = reinterpret_cast<double2 *>(mat);
@@ -129,41 +95,10 @@ __global__ __launch_bounds__(T) void lp_variants_kernel(VarLaunch L) {
             else
                 mat[(size_t)r * lp + cc - 1] = L.pval[c];
         }
-        __syncthreads();
-        if (tid == 0) s_next[0] = atomicAdd(L.counter, 1u); // (everybody read the slot two barriers ago; read again after the last one)
-
-        int32_t *hist_l = CHECK ? L.hist + (size_t)blockIdx.x * 2 * L.hist_cap : nullptr;
-        const WgResult out = wg_simplex<T, CHECK>(mat, rhs, pos, var, colbuf, prow, sk, si, w, n, lp, pcols, h,
-                                                  wg_unit_lanes(pcols / 2, T), d->precision, d->max_pivots, hist_l,
-                                                  CHECK ? hist_l + L.hist_cap : nullptr, CHECK ? L.hist_cap : 0);
-        __syncthreads();
-        // (checkCycles, history full: no output but the status -- the host grows the history and reruns this variant from the image)
-        const bool done = !(CHECK && out.status == WG_HISTORY_FULL);
-        if (LDS && done) {
-            double *col0 = L.col0 + col0_off;
-            for (int r = tid; r < h; r += T) col0[r] = rhs[r];
-            int32_t *opos = L.pos + perm_off, *ovar = L.var + perm_off;
-            for (int p = tid; p < w + h; p += T) {
-                opos[p] = pos[p];
-                ovar[p] = var[p];
-            }
-        }
-        if (L.tab && done) { // the whole final matrix in the reference's layout (src/tableau.ts:9-21)
-            double *tab = L.tab + (size_t)i * w * h;
-            const int Uc = wg_unit_lanes(w, T), cu0 = tid % Uc, cg0 = tid / Uc, CG = T / Uc;
-            for (int r = cg0; r < h; r += CG) {
-                const double *src = mat + (size_t)r * lp;
-                double *dst = tab + (size_t)r * w;
-                for (int c = cu0; c < w; c += Uc) dst[c] = c == 0 ? rhs[r] : src[c - 1];
-            }
-        }
-        if (tid == T - 1) {
-            L.status[i] = out.status;
-            if (done) {
-                L.result[i] = out.result;
-                L.pivots[i] = out.pivots;
-            }
-        }
-        __syncthreads(); // everybody is done with this variant's tableau, and the next index is in its slot
     }
+};
+
+template <int T, bool CHECK, bool LDS>
+__global__ __launch_bounds__(T) void lp_variants_kernel(VarLaunch L) {
+    wg_queue<T, CHECK, LDS>(L, VarJob(L));
 }

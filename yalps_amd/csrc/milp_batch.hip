@@ -1,6 +1,7 @@
 // milp_batch.hip -- libyalps_milpbatch.so: a batch of independent MILPs in one call (include/yalps_milpbatch.h)
 // The root pass is libyalps_lpbatch.so's host code and kernels (lp_batch_host.inc, lp_batch_kernel.cuh) with kept tableaux,
-// compiled again here; the node pass is milp_node_kernel; the search rules are milp_search.inc, shared with yalps_milp_f64.
+// compiled again here; the node pass is milp_node_kernel on the same passes (wg_queue_host.inc); the search rules are
+// milp_search.inc, shared with yalps_milp_f64.
 // A library of its own: nothing here is linked into libyalps_hip.so or libyalps_lpbatch.so.
 #include <hip/hip_runtime.h>
 
@@ -27,43 +28,18 @@ namespace {
 #include "common.cuh"
 
 #include "wg_simplex.cuh"
-#include "lp_batch_kernel.cuh"
 #include "milp_node_kernel.cuh"
+#include "wg_queue_host.inc"
+#include "lp_batch_host.inc"
+
+static_assert(YALPS_MILPBATCH_MAX_BYTES == QUEUE_MAX_BYTES, "include/yalps_milpbatch.h");
+const KernelTable<NodeLaunch> kNodeKernels = QUEUE_KERNEL_TABLE(milp_node_kernel);
 } // namespace
 
-#include "lp_batch_host.inc"
+#include "lp_batch_lib.inc"
 #include "milp_search.inc"
 
 namespace {
-using NodeFn = void (*)(NodeLaunch);
-struct NodeForm {
-    NodeFn fn;
-    int lanes;
-    bool check, lds;
-};
-const NodeForm kNodeForms[] = {
-    {milp_node_kernel<256, false, true>, 256, false, true},    {milp_node_kernel<256, true, true>, 256, true, true},
-    {milp_node_kernel<1024, false, true>, 1024, false, true},  {milp_node_kernel<1024, true, true>, 1024, true, true},
-    {milp_node_kernel<1024, false, false>, 1024, false, false}, {milp_node_kernel<1024, true, false>, 1024, true, false},
-};
-const NodeForm *find_node_form(int lanes, bool check, bool lds) {
-    for (const NodeForm &f : kNodeForms)
-        if (f.lanes == lanes && f.check == check && f.lds == lds) return &f;
-    return nullptr;
-}
-std::string node_form_name(const NodeForm &f) {
-    return "milp_node_kernel<" + std::to_string(f.lanes) + (f.check ? ",check" : "") + (f.lds ? ",lds" : "") + ">";
-}
-
-struct NodeLaunchPlan {
-    int cls;
-    bool check;
-    std::vector<int32_t> nodes; // largest first
-    const NodeForm *form;
-    int grid;
-    size_t shmem, stride;
-};
-
 // one model of the whole solve / of the host-only search
 struct Tree {
     int32_t w = 0, h = 0, nints = 0;
@@ -239,15 +215,15 @@ int validate_nodes(int32_t n_roots, const int32_t *rw, const int32_t *rh, int32_
 
 struct yalps_milpbatch {
     yalps_lpbatch *lp = nullptr; // the root pass: device, stream, events, the kept root tableaux
-    long long hist_first = HIST_FIRST;
     std::vector<int32_t> root_check;
-    DevBuf ndesc, order, counters, csign, cvar, cval, status, height, result, pivots, col0, pos, var, tab, ws, hist;
+    QueueBufs q;
+    DevBuf ndesc, csign, cvar, cval, height;
     // the last node pass
     std::vector<NodeDesc> nodes;
-    std::vector<int32_t> h_status, h_height, h_pos, h_var;
+    std::vector<int32_t> h_height, h_pos, h_var;
     std::vector<double> h_result, h_col0;
     std::vector<long long> h_pivots;
-    bool keep = false, in_solve = false;
+    bool in_solve = false;
     // the last solve
     std::vector<Tree> trees;
     std::vector<int32_t> ints;
@@ -289,7 +265,7 @@ int roots_impl(yalps_milpbatch *b, int32_t count, const int32_t *width, const in
     b->nodes.clear();
     b->root_check.clear();
     float ms = 0.f;
-    if (int rc = solve_impl(b->lp, count, width, height, off, row, col, val, precision, maxPivots, checkCycles, 1, status_out,
+    if (int rc = lp_solve_impl(b->lp, count, width, height, off, row, col, val, precision, maxPivots, checkCycles, 1, status_out,
                             result_out, pivots_out, &ms)) {
         b->lp->descs.clear();
         return rc;
@@ -297,111 +273,6 @@ int roots_impl(yalps_milpbatch *b, int32_t count, const int32_t *width, const in
     b->root_check.assign(checkCycles, checkCycles + count);
     b->gpu_ms += ms;
     info_roots(b);
-    return 0;
-}
-
-// One pass over `todo` (node indices): every launch enqueued, then every output on its way back, one wait.
-int node_pass(yalps_milpbatch *b, const std::vector<int32_t> &todo, long long hist_cap, int pass, size_t col0_total,
-              size_t perm_total) {
-    yalps_lpbatch *lp = b->lp;
-    hipStream_t s = lp->stream;
-    const std::vector<LpDesc> &R = lp->descs;
-    const std::vector<NodeDesc> &N = b->nodes;
-    auto hgt = [&](int32_t k) { return R[(size_t)N[k].root].h + N[k].ncuts; };
-    auto wid = [&](int32_t k) { return R[(size_t)N[k].root].w; };
-    std::vector<NodeLaunchPlan> plans;
-    for (int c = 0; c < 2; c++)
-        for (int k = 0; k < NCLASS; k++) {
-            NodeLaunchPlan L{k, c != 0, {}, nullptr, 0, 0, 0};
-            for (int32_t i : todo)
-                if ((b->root_check[(size_t)N[i].root] != 0) == L.check && lp_class(wid(i), hgt(i)) == k) L.nodes.push_back(i);
-            if (L.nodes.empty()) continue;
-            std::stable_sort(L.nodes.begin(), L.nodes.end(),
-                             [&](int32_t x, int32_t y) { return (int64_t)wid(x) * hgt(x) > (int64_t)wid(y) * hgt(y); });
-            plans.push_back(std::move(L));
-        }
-    size_t order_total = 0, ws_doubles = 0, hist_wgs = 0;
-    for (NodeLaunchPlan &L : plans) {
-        const bool lds = L.cls != HBM_CLASS;
-        L.form = find_node_form(lds ? lp->lanes[L.cls] : 1024, L.check, lds);
-        if (!L.form) return fail(YALPS_E_ARG, "yalps_milpbatch: no kernel of " + std::to_string(lp->lanes[L.cls]) + " lanes");
-        L.grid = (int)std::min<size_t>(L.nodes.size(), (size_t)lp->num_cus * (size_t)std::max(1, lp->per_cu[L.cls]));
-        for (int32_t i : L.nodes) {
-            const int w = wid(i), h = hgt(i);
-            if (lds) {
-                L.shmem = std::max(L.shmem, small_lds_bytes(w, h));
-            } else {
-                const size_t pc = (size_t)small_pcols(w - 1), aux = pc + (size_t)h;
-                if (!N[i].aux_hbm) L.shmem = std::max(L.shmem, sizeof(double) * aux);
-                L.stride = std::max(L.stride, (size_t)h * pc + ((aux + 1) & ~(size_t)1));
-            }
-        }
-        L.shmem = std::max<size_t>((L.shmem + 15) & ~(size_t)15, 16);
-        ws_doubles = std::max(ws_doubles, L.stride * (size_t)L.grid);
-        if (L.check) hist_wgs = std::max(hist_wgs, (size_t)L.grid);
-        order_total += L.nodes.size();
-    }
-    if (plans.empty()) return 0;
-    if (int rc = ensure(b->order, sizeof(int32_t) * order_total)) return rc;
-    if (int rc = ensure(b->counters, sizeof(unsigned int) * plans.size())) return rc;
-    if (int rc = ensure(b->ws, sizeof(double) * ws_doubles)) return rc;
-    if (int rc = ensure(b->hist, sizeof(int32_t) * 2 * hist_wgs * (size_t)hist_cap)) return rc;
-    std::vector<int32_t> order;
-    order.reserve(order_total);
-    for (const NodeLaunchPlan &L : plans) order.insert(order.end(), L.nodes.begin(), L.nodes.end());
-    HIP_TRY(hipMemcpyAsync(b->order.p, order.data(), sizeof(int32_t) * order_total, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemsetAsync(b->counters.p, 0, sizeof(unsigned int) * plans.size(), s));
-    HIP_TRY(hipEventRecord(lp->ev0, s));
-    size_t at = 0, nl = 0;
-    for (const NodeLaunchPlan &L : plans) {
-        NodeLaunch a{};
-        a.roots = static_cast<const LpDesc *>(lp->desc.p);
-        a.root_tab = static_cast<const double *>(lp->tab.p);
-        a.root_pos = static_cast<const int32_t *>(lp->pos.p);
-        a.root_var = static_cast<const int32_t *>(lp->var.p);
-        a.node = static_cast<const NodeDesc *>(b->ndesc.p);
-        a.order = static_cast<const int32_t *>(b->order.p) + at;
-        a.count = (int32_t)L.nodes.size();
-        a.counter = static_cast<unsigned int *>(b->counters.p) + nl;
-        a.cut_sign = static_cast<const int32_t *>(b->csign.p);
-        a.cut_var = static_cast<const int32_t *>(b->cvar.p);
-        a.cut_val = static_cast<const double *>(b->cval.p);
-        a.status = static_cast<int32_t *>(b->status.p);
-        a.height = static_cast<int32_t *>(b->height.p);
-        a.result = static_cast<double *>(b->result.p);
-        a.pivots = static_cast<long long *>(b->pivots.p);
-        a.col0 = static_cast<double *>(b->col0.p);
-        a.pos = static_cast<int32_t *>(b->pos.p);
-        a.var = static_cast<int32_t *>(b->var.p);
-        a.tab = b->keep ? static_cast<double *>(b->tab.p) : nullptr;
-        a.ws = static_cast<double *>(b->ws.p);
-        a.ws_stride = (long long)L.stride;
-        a.hist = static_cast<int32_t *>(b->hist.p);
-        a.hist_cap = hist_cap;
-        const NodeFn fn = L.form->fn;
-        fn<<<dim3(L.grid), dim3(L.form->lanes), L.shmem, s>>>(a);
-        HIP_TRY(hipGetLastError());
-        char line[256];
-        std::snprintf(line, sizeof line, "launch=%lld round=%lld pass=%d kernel=%s class=%d nodes=%zu grid=%d lds=%zu hist_cap=%lld\n",
-                      (long long)b->launches++, (long long)b->rounds, pass, node_form_name(*L.form).c_str(), L.cls, L.nodes.size(), L.grid,
-                      L.shmem, L.check ? hist_cap : 0ll);
-        if (b->lines.size() < ((size_t)1 << 20)) b->lines += line; // (a long solve: the text stops growing, the counts do not)
-        at += L.nodes.size();
-        nl++;
-    }
-    HIP_TRY(hipEventRecord(lp->ev1, s));
-    const size_t n = N.size();
-    HIP_TRY(hipMemcpyAsync(b->h_status.data(), b->status.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(b->h_height.data(), b->height.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(b->h_result.data(), b->result.p, sizeof(double) * n, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(b->h_pivots.data(), b->pivots.p, sizeof(long long) * n, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(b->h_col0.data(), b->col0.p, sizeof(double) * col0_total, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(b->h_pos.data(), b->pos.p, sizeof(int32_t) * perm_total, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(b->h_var.data(), b->var.p, sizeof(int32_t) * perm_total, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, lp->ev0, lp->ev1));
-    b->gpu_ms += ms;
     return 0;
 }
 
@@ -417,7 +288,7 @@ int nodes_impl(yalps_milpbatch *b, int32_t count, const int32_t *root, const int
         if (int rc = validate_nodes((int32_t)R.size(), rw.data(), rh.data(), count, root, off, cvar)) return rc;
     }
     if (count > 0 && off[count] > off[0] && (!csign || !cval)) return fail(YALPS_E_ARG, "yalps_milpbatch_nodes: cut_sign / cut_val is NULL");
-    b->keep = keep != 0;
+    b->q.keep = keep != 0;
     if (count == 0) return 0;
     HIP_TRY(hipSetDevice(lp->device));
     hipStream_t s = lp->stream;
@@ -448,23 +319,15 @@ int nodes_impl(yalps_milpbatch *b, int32_t count, const int32_t *root, const int
     if (int rc = ensure(b->csign, sizeof(int32_t) * ncuts)) return rc;
     if (int rc = ensure(b->cvar, sizeof(int32_t) * ncuts)) return rc;
     if (int rc = ensure(b->cval, sizeof(double) * ncuts)) return rc;
-    if (int rc = ensure(b->status, sizeof(int32_t) * n)) return rc;
     if (int rc = ensure(b->height, sizeof(int32_t) * n)) return rc;
-    if (int rc = ensure(b->result, sizeof(double) * n)) return rc;
-    if (int rc = ensure(b->pivots, sizeof(long long) * n)) return rc;
-    if (int rc = ensure(b->col0, sizeof(double) * (size_t)col0_total)) return rc;
-    if (int rc = ensure(b->pos, sizeof(int32_t) * (size_t)perm_total)) return rc;
-    if (int rc = ensure(b->var, sizeof(int32_t) * (size_t)perm_total)) return rc;
-    if (b->keep)
-        if (int rc = ensure(b->tab, sizeof(double) * (size_t)tab_total)) return rc;
+    if (int rc = ensure_outputs(b->q, n, (size_t)col0_total, (size_t)perm_total, (size_t)tab_total)) return rc;
     HIP_TRY(hipMemcpyAsync(b->ndesc.p, N.data(), sizeof(NodeDesc) * n, hipMemcpyHostToDevice, s));
     if (ncuts) {
         HIP_TRY(hipMemcpyAsync(b->csign.p, csign + base, sizeof(int32_t) * ncuts, hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemcpyAsync(b->cvar.p, cvar + base, sizeof(int32_t) * ncuts, hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemcpyAsync(b->cval.p, cval + base, sizeof(double) * ncuts, hipMemcpyHostToDevice, s));
     }
-    HIP_TRY(hipMemsetAsync(b->status.p, 0x80, sizeof(int32_t) * n, s)); // (a status no kernel writes)
-    b->h_status.assign(n, 0);
+    if (int rc = reset_status(b->q, s, n)) return rc;
     b->h_height.assign(n, 0);
     b->h_result.assign(n, NAN);
     b->h_pivots.assign(n, 0);
@@ -472,33 +335,51 @@ int nodes_impl(yalps_milpbatch *b, int32_t count, const int32_t *root, const int
     b->h_pos.resize((size_t)perm_total);
     b->h_var.resize((size_t)perm_total);
 
-    std::vector<int32_t> todo(n);
-    for (size_t k = 0; k < n; k++) todo[k] = (int32_t)k;
-    long long hist_cap = b->hist_first;
-    int pass = 0;
-    while (!todo.empty()) {
-        if (int rc = node_pass(b, todo, hist_cap, pass, (size_t)col0_total, (size_t)perm_total)) return rc;
-        // a node whose phase outran the history left no output: grow the pool and rerun only those
-        std::vector<int32_t> again;
-        for (int32_t k : todo) {
-            if (b->h_status[k] == WG_HISTORY_FULL)
-                again.push_back(k);
-            else if (b->h_status[k] < 0 || b->h_status[k] > YALPS_CYCLED)
-                return fail(YALPS_E_DEVICE, "milp_node_kernel did not report a result for node " + std::to_string(k));
-        }
-        for (int32_t k : again) b->rerun_ids.push_back((b->in_solve ? std::to_string(b->rounds) + ":" : "") + std::to_string(k)); // (a solve: round:node)
-        todo.swap(again);
-        hist_cap *= 4;
-        pass++;
-        if (!todo.empty() && hist_cap > (1ll << 28)) return fail(YALPS_E_NOMEM, "yalps_milpbatch_nodes: checkCycles history beyond 2^28 pivots");
-    }
+    // every launch of a pass enqueued, then every output on its way back, one wait
+    QueueRun run;
+    const int rc = run_queue(
+        *lp, b->q, kNodeKernels, QueueText{"yalps_milpbatch", false, "yalps_milpbatch_nodes", "node"}, n,
+        [&](int32_t k, int *w, int *h) {
+            const LpDesc &r = R[(size_t)N[k].root];
+            return *w = r.w, *h = r.h + N[k].ncuts, b->root_check[(size_t)N[k].root] != 0;
+        },
+        [&](NodeLaunch &a) {
+            a.roots = lp->desc.as<const LpDesc>();
+            a.root_tab = lp->q.tab.as<const double>();
+            a.root_pos = lp->q.pos.as<const int32_t>();
+            a.root_var = lp->q.var.as<const int32_t>();
+            a.node = b->ndesc.as<const NodeDesc>();
+            a.cut_sign = b->csign.as<const int32_t>();
+            a.cut_var = b->cvar.as<const int32_t>();
+            a.cut_val = b->cval.as<const double>();
+            a.height = b->height.as<int32_t>();
+        },
+        [&]() -> int {
+            HIP_TRY(hipMemcpyAsync(b->h_height.data(), b->height.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipMemcpyAsync(b->h_result.data(), b->q.result.p, sizeof(double) * n, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipMemcpyAsync(b->h_pivots.data(), b->q.pivots.p, sizeof(long long) * n, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipMemcpyAsync(b->h_col0.data(), b->q.col0.p, sizeof(double) * (size_t)col0_total, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipMemcpyAsync(b->h_pos.data(), b->q.pos.p, sizeof(int32_t) * (size_t)perm_total, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipMemcpyAsync(b->h_var.data(), b->q.var.p, sizeof(int32_t) * (size_t)perm_total, hipMemcpyDeviceToHost, s));
+            return 0;
+        },
+        [&](const Launch &L, const std::string &kernel, int pass, int, long long hist_cap) {
+            char line[256];
+            std::snprintf(line, sizeof line, "launch=%lld round=%lld pass=%d kernel=%s class=%d nodes=%zu grid=%d lds=%zu hist_cap=%lld\n",
+                          (long long)b->launches++, (long long)b->rounds, pass, kernel.c_str(), L.cls, L.items.size(), L.grid, L.shmem, hist_cap);
+            if (b->lines.size() < ((size_t)1 << 20)) b->lines += line; // (a long solve: the text stops growing, the counts do not)
+        },
+        run);
+    if (rc) return rc;
+    b->gpu_ms += run.ms;
+    for (int32_t k : run.reruns) b->rerun_ids.push_back((b->in_solve ? std::to_string(b->rounds) + ":" : "") + std::to_string(k)); // (a solve: round:node)
     return 0;
 }
 
 void eval_from_node(const yalps_milpbatch *b, size_t k, MilpEval &ev) {
     const NodeDesc &d = b->nodes[k];
     const int32_t w = b->lp->descs[(size_t)d.root].w, h = b->h_height[k];
-    ev.status = b->h_status[k];
+    ev.status = b->q.h_status[k];
     ev.result = b->h_result[k];
     if (ev.status != YALPS_OPTIMAL) return;
     ev.view.height = h;
@@ -574,18 +455,18 @@ int32_t yalps_milpbatch_create(int32_t device, void *hip_stream, yalps_milpbatch
     if (!out) return fail(YALPS_E_ARG, "yalps_milpbatch_create: out is NULL");
     *out = nullptr;
     yalps_lpbatch *lp = nullptr;
-    if (int rc = lpbatch_create(device, hip_stream, &lp)) return rc;
-    for (const NodeForm &f : kNodeForms) {
+    if (int rc = lp_create(device, hip_stream, &lp)) return rc;
+    for (const KernelForm<NodeLaunch> &f : kNodeKernels.forms) {
         const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(f.fn), hipFuncAttributeMaxDynamicSharedMemorySize,
                                                  (int)SMALL_LDS_MAX);
         if (e != hipSuccess) {
-            lpbatch_destroy_impl(lp);
+            lp_destroy(lp);
             return fail(YALPS_E_DEVICE, std::string("hipFuncSetAttribute: ") + hipGetErrorString(e));
         }
     }
     yalps_milpbatch *b = new yalps_milpbatch();
     b->lp = lp;
-    b->hist_first = std::max(1, env_int("YALPS_MILPBATCH_HIST", (int)HIST_FIRST)); // (test hook: forces the node rerun)
+    b->q.hist_first = std::max(1, env_int("YALPS_MILPBATCH_HIST", (int)HIST_FIRST)); // (test hook: forces the node rerun)
     b->info = "rounds=0 launches=0 reruns=0 gpu_us=0 rerun_nodes=[]\n";
     *out = b;
     return 0;
@@ -595,10 +476,9 @@ void yalps_milpbatch_destroy(yalps_milpbatch *b) {
     if (!b) return;
     (void)hipSetDevice(b->lp->device);
     if (b->lp->stream) (void)hipStreamSynchronize(b->lp->stream);
-    for (DevBuf *d : {&b->ndesc, &b->order, &b->counters, &b->csign, &b->cvar, &b->cval, &b->status, &b->height, &b->result, &b->pivots,
-                      &b->col0, &b->pos, &b->var, &b->tab, &b->ws, &b->hist})
-        if (d->p) (void)hipFree(d->p);
-    lpbatch_destroy_impl(b->lp);
+    release(b->q);
+    release({&b->ndesc, &b->csign, &b->cvar, &b->cval, &b->height});
+    lp_destroy(b->lp);
     delete b;
 }
 
@@ -625,7 +505,7 @@ int32_t yalps_milpbatch_root(yalps_milpbatch *b, int32_t i, double *col0, int32_
     if (variableAtPosition) std::memcpy(variableAtPosition, b->lp->h_var.data() + d.perm_off, sizeof(int32_t) * np);
     if (matrix) {
         HIP_TRY(hipSetDevice(b->lp->device));
-        HIP_TRY(hipMemcpyAsync(matrix, static_cast<const double *>(b->lp->tab.p) + d.tab_off, sizeof(double) * (size_t)d.w * (size_t)d.h,
+        HIP_TRY(hipMemcpyAsync(matrix, b->lp->q.tab.as<const double>() + d.tab_off, sizeof(double) * (size_t)d.w * (size_t)d.h,
                                hipMemcpyDeviceToHost, b->lp->stream));
         HIP_TRY(hipStreamSynchronize(b->lp->stream));
     }
@@ -651,7 +531,7 @@ int32_t yalps_milpbatch_nodes(yalps_milpbatch *b, int32_t count, const int32_t *
         return rc;
     }
     const size_t n = (size_t)count;
-    if (status_out) std::memcpy(status_out, b->h_status.data(), sizeof(int32_t) * n);
+    if (status_out) std::memcpy(status_out, b->q.h_status.data(), sizeof(int32_t) * n);
     if (height_out) std::memcpy(height_out, b->h_height.data(), sizeof(int32_t) * n);
     if (result_out) std::memcpy(result_out, b->h_result.data(), sizeof(double) * n);
     if (pivots_out)
@@ -673,11 +553,11 @@ int32_t yalps_milpbatch_node(yalps_milpbatch *b, int32_t k, double *col0, int32_
 int32_t yalps_milpbatch_node_tableau(yalps_milpbatch *b, int32_t k, double *matrix) {
     if (!b || k < 0 || (size_t)k >= b->nodes.size() || !matrix)
         return fail(YALPS_E_ARG, "yalps_milpbatch_node_tableau: no such node in the last node pass");
-    if (!b->keep) return fail(YALPS_E_ARG, "yalps_milpbatch_node_tableau: the last node pass did not keep its tableaux (keep_tableaux)");
+    if (!b->q.keep) return fail(YALPS_E_ARG, "yalps_milpbatch_node_tableau: the last node pass did not keep its tableaux (keep_tableaux)");
     const NodeDesc &d = b->nodes[(size_t)k];
     const size_t w = (size_t)b->lp->descs[(size_t)d.root].w, h = (size_t)b->h_height[(size_t)k];
     HIP_TRY(hipSetDevice(b->lp->device));
-    HIP_TRY(hipMemcpyAsync(matrix, static_cast<const double *>(b->tab.p) + d.tab_off, sizeof(double) * w * h, hipMemcpyDeviceToHost,
+    HIP_TRY(hipMemcpyAsync(matrix, b->q.tab.as<const double>() + d.tab_off, sizeof(double) * w * h, hipMemcpyDeviceToHost,
                            b->lp->stream));
     HIP_TRY(hipStreamSynchronize(b->lp->stream));
     return 0;
@@ -799,10 +679,7 @@ int32_t yalps_milpbatch_search(int32_t count, const int32_t *width, const int32_
 
 int32_t yalps_milpbatch_info(const yalps_milpbatch *b, char *buf, int32_t len) {
     if (!b || !buf || len < 1) return fail(YALPS_E_ARG, "yalps_milpbatch_info: bad argument");
-    const size_t n = std::min(b->info.size(), (size_t)len - 1);
-    std::memcpy(buf, b->info.data(), n);
-    buf[n] = 0;
-    return (int32_t)std::min<size_t>(b->info.size(), INT32_MAX);
+    return info_out(b->info, buf, len);
 }
 
 } // extern "C"
