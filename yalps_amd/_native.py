@@ -57,6 +57,13 @@ SYMBOLS_LPSENS = (
     "yalps_lpsens_solution", "yalps_lpsens_tableau", "yalps_lpsens_ranges", "yalps_lpsens_info",
 )
 LPSENS_MAX_BYTES = 4 << 20  # YALPS_LPSENS_MAX_BYTES
+# every symbol include/yalps_lpwarm.h declares (a sixth library, loaded on first use)
+LPWARM_LIB_PATH = os.environ.get("YALPS_LPWARM_LIB") or os.path.join(HERE, "libyalps_lpwarm.so")
+SYMBOLS_LPWARM = (
+    "yalps_lpwarm_last_error", "yalps_lpwarm_create", "yalps_lpwarm_destroy", "yalps_lpwarm_validate", "yalps_lpwarm_solve",
+    "yalps_lpwarm_solution", "yalps_lpwarm_tableau", "yalps_lpwarm_info",
+)
+LPWARM_MAX_BYTES = 4 << 20  # YALPS_LPWARM_MAX_BYTES
 LPBATCH_HBM_CLASS = 4        # yalps_lpbatch_class: 0..3 the LDS form, 4 the HBM form
 
 
@@ -833,6 +840,102 @@ class LpVariants:
     def close(self):
         if self.handle:
             lpvar_lib().yalps_lpvar_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+
+# ---------------------------------------------------------------------------------------------- libyalps_lpwarm.so
+
+_BATCH_LIBS["yalps_lpwarm"] = (LPWARM_LIB_PATH, {
+        "validate": (_I32, [_I32, _I32, _I64, _VP, _VP, _I32, _VP, _VP, _VP]),
+        "solve": (_I32, [_VP, _I32, _I32, _I64, _VP, _VP, _VP, C.c_double, C.c_double, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
+                         _I32, _VP, _VP, _VP, _VP, _VP, _VP, C.POINTER(C.c_float)]),
+        "solution": (_I32, [_VP, _I32, _VP, _VP, _VP]), "tableau": (_I32, [_VP, _I32, _VP])})
+
+
+def lpwarm_lib():
+    return _load_lib("yalps_lpwarm")
+
+
+def lpwarm_check(rc):
+    return _check("yalps_lpwarm", rc)
+
+
+class PackedWarm(PackedVariants):
+    """Variants of one LP as yalps_lpwarm_solve takes them: PackedVariants -- patches of the INITIAL tableau, here in row 0
+    and column 0 only -- plus the options of the base's own solve."""
+
+    def __init__(self, width, height, row, col, val, patches, options=None, flat=None, base_options=(1e-8, 8192.0, False)):
+        super().__init__(width, height, row, col, val, patches, options, flat)
+        self.base_precision, self.base_max_pivots = float(base_options[0]), float(base_options[1])
+        self.base_check_cycles = int(bool(base_options[2]))
+
+    def validate(self):
+        """The argument checks of yalps_lpwarm_solve, on the host (raises NativeError naming the variant)."""
+        lpwarm_check(lpwarm_lib().yalps_lpwarm_validate(
+            self.width, self.height, self.row.size, self.row.ctypes.data, self.col.ctypes.data, self.count,
+            self.offsets.ctypes.data, self.patch_row.ctypes.data, self.patch_col.ctypes.data))
+
+
+class LpWarm:
+    """Many variants of one LP per call, each reoptimised from the base's optimal tableau by one workgroup (yalps_lpwarm_*).
+    Belongs to one thread at a time."""
+
+    def __init__(self, device=0, stream=None):
+        self.handle = C.c_void_p()
+        lpwarm_check(lpwarm_lib().yalps_lpwarm_create(device, C.c_void_p(stream) if stream is not None else None,
+                                                     C.byref(self.handle)))
+        self.packed = None
+        self.base = None
+
+    def solve(self, packed, keep_tableaux=False):
+        """packed: a PackedWarm.  Returns (status names, results, pivot counts, gpu_ms) of the variants, or None where the
+        base did not end optimal (nothing ran for the variants); self.base = (status name, result, pivots) of the base."""
+        p = packed
+        n = p.count
+        st, res, piv, ms = np.empty(n, np.int32), np.empty(n, np.float64), np.empty(n, np.int64), C.c_float()
+        bst, bres, bpiv = C.c_int32(), C.c_double(), C.c_int64()
+        self.packed = self.base = None
+        lpwarm_check(lpwarm_lib().yalps_lpwarm_solve(
+            self.handle, p.width, p.height, p.row.size, p.row.ctypes.data, p.col.ctypes.data, p.val.ctypes.data,
+            p.base_precision, p.base_max_pivots, p.base_check_cycles, n, p.offsets.ctypes.data, p.patch_row.ctypes.data,
+            p.patch_col.ctypes.data, p.patch_val.ctypes.data, p.precision.ctypes.data, p.max_pivots.ctypes.data,
+            p.check_cycles.ctypes.data, int(bool(keep_tableaux)), C.addressof(bst), C.addressof(bres), C.addressof(bpiv),
+            st.ctypes.data, res.ctypes.data, piv.ctypes.data, C.byref(ms)))
+        self.base = (STATUS[bst.value], bres.value, bpiv.value)
+        if self.base[0] != "optimal":
+            return None
+        self.packed = p
+        return [STATUS[k] for k in st], res, piv, ms.value
+
+    def _check(self, i):
+        if self.packed is None or not 0 <= i < self.packed.count:
+            raise NativeError("LpWarm: no such variant in the last solve: %r" % (i,))
+        return self.packed.width, self.packed.height
+
+    def solution(self, i):
+        """(col0, positionOfVariable, variableAtPosition) of variant i of the last solve."""
+        w, h = self._check(i)
+        col0 = np.empty(h, np.float64)
+        pos, var = np.empty(w + h, np.int32), np.empty(w + h, np.int32)
+        lpwarm_check(lpwarm_lib().yalps_lpwarm_solution(self.handle, i, col0.ctypes.data, pos.ctypes.data, var.ctypes.data))
+        return col0, pos, var
+
+    def tableau(self, i):
+        """The whole final matrix of variant i of the last solve (solve(..., keep_tableaux=True)), flat row-major."""
+        w, h = self._check(i)
+        m = np.empty(w * h, np.float64)
+        lpwarm_check(lpwarm_lib().yalps_lpwarm_tableau(self.handle, i, m.ctypes.data))
+        return m
+
+    def info(self):
+        """{"launches", "reruns", "rerun_lps": [...], "base_status", "base_pivots", "patch_cells", "records", "image_bytes",
+        "kernels": [{kernel, class, aux, lps, grid, lds, pass, hist_cap}], "text"}"""
+        return _batch_info(_info_text("yalps_lpwarm", self.handle),
+                           more=("base_status", "base_pivots", "patch_cells", "records", "image_bytes"))
+
+    def close(self):
+        if self.handle:
+            lpwarm_lib().yalps_lpwarm_destroy(self.handle)
             self.handle = C.c_void_p()
 
 

@@ -400,5 +400,140 @@ def solve_variants(model, variants, options=None, stats=None):
     return _solve_variants_with(lpvariants_simplex, solve_many, model, variants, options, stats)
 
 
+_lpwarm = None  # the process's LpWarm, kept like _lpbatch
+
+
+def lpwarm_simplex(tableau, base_options, patches, options, stats=None):
+    """The warm backend of reoptimize_variants: the base tableau (built with sparse=True) with the options of its own solve,
+    and every variant's patch -- sorted [(flat index, value)], cells of row 0 and column 0 of the initial tableau -- through
+    ONE yalps_lpwarm_solve.  Returns ((status, result, pivots) of the base, per variant (status, result, pivots, col0,
+    positionOfVariable, variableAtPosition)), the second None where the base did not end optimal."""
+    import numpy as np
+    global _lpwarm
+    w = tableau.width
+    offsets = np.zeros(len(patches) + 1, np.int64)
+    np.cumsum([len(p) for p in patches], out=offsets[1:])
+    total = int(offsets[-1])
+    idx = np.fromiter((k for p in patches for k, _ in p), np.int64, total)
+    val = np.fromiter((v for p in patches for _, v in p), np.float64, total)
+    b = base_options
+    packed = _native.PackedWarm(w, tableau.height, *tableau.cells, patches,
+                                [(o["precision"], o["maxPivots"], o["checkCycles"]) for o in options],
+                                flat=(offsets, idx // w, idx % w, val),
+                                base_options=(b["precision"], b["maxPivots"], b["checkCycles"]))
+    with _lpbatch_lock:
+        if _lpwarm is None:
+            _lpwarm = _native.LpWarm(0)
+        lw = _lpwarm
+        ran = lw.solve(packed)
+        out = None
+        if ran is not None:
+            statuses, results, pivots, _ = ran
+            out = [(s, float(r), int(p), *lw.solution(i)) for i, (s, r, p) in enumerate(zip(statuses, results, pivots))]
+        if stats is not None:
+            info = lw.info()
+            stats.update(launches=info["launches"], reruns=info["reruns"], kernels=info["kernels"])
+    return lw.base, out
+
+
+def _reoptimize_variants_with(warm_backend, cold_fn, model, variants, options=None, base_options=None, stats=None):
+    """reoptimize_variants with its backends as parameters (tests drive the routing and the marshalling with the CPU oracle):
+    warm_backend(tableau, base options, patches, options, stats) -> ((status, result, pivots) of the base, per variant
+    (status, result, pivots, col0, pos, var) or None where the base is not optimal) for the variants that move only bounds
+    and objective coefficients, cold_fn(model, variants, options, stats) -- solve_variants -- for everything else; results
+    in input order."""
+    from .model import Tableau, TableauModel
+    variants = list(variants)
+    opts = list(options) if isinstance(options, (list, tuple)) else [options] * len(variants)
+    if len(opts) != len(variants):
+        raise ValueError("reoptimize_variants: %d variants but %d option sets" % (len(variants), len(opts)))
+    if stats is not None:
+        stats.update(warm=0, cold=len(variants), base_status=None, base_pivots=0, pivots=[], launches=0, reruns=0, kernels=[])
+
+    def all_cold():
+        sub = {} if stats is not None else None
+        out = cold_fn(model, variants, options, sub)
+        if stats is not None:
+            stats["solve_variants"] = sub
+        return out
+
+    tabmod, bounds_info = tableau_model_with_bounds(model, sparse=True)
+    t = tabmod.tableau
+    if tabmod.integers or 8 * t.width * t.height > NODE_BATCH_MAX_BYTES:
+        return all_cold()
+    w = t.width
+    row, col, val = t.cells
+    edge = (row == 0) | (col == 0)
+    base0 = dict(zip((row[edge].astype("int64") * w + col[edge]).tolist(), val[edge].tolist()))  # row 0 and column 0 of the initial tableau
+    warm, cold = [], []  # (index, patch without the cells that do not move, merged options) | index
+    for i, (v, o) in enumerate(zip(variants, opts)):
+        patch = variant_patch_cells(tabmod, bounds_info, v)
+        if patch is None or any(k >= w and k % w for k, _ in patch):
+            cold.append(i)  # another structure | a cell in the body of the tableau
+            continue
+        deltas = [x - base0.get(k, 0.0) for k, x in patch]
+        if not all(math.isfinite(d) for d in deltas):
+            cold.append(i)
+            continue
+        opt = dict(_DEFAULTS)
+        if o:
+            opt.update({k: x for k, x in o.items() if x is not None})
+        warm.append((i, [cell for cell, d in zip(patch, deltas) if d != 0.0], opt))
+    if not warm:
+        return all_cold()
+    base_opt = dict(_DEFAULTS)
+    if base_options:
+        base_opt.update({k: x for k, x in base_options.items() if x is not None})
+    base, results = warm_backend(t, base_opt, [p[1] for p in warm], [p[2] for p in warm], stats)
+    if stats is not None:
+        stats.update(base_status=base[0], base_pivots=int(base[2]))
+    if base[0] != "optimal" or results is None:
+        return all_cold()
+    out = [None] * len(variants)
+    for (i, _, opt), (status, result, pivots, col0, pos, var) in zip(warm, results):
+        view = TableauModel(Tableau(None, t.width, t.height, pos, var, col0), tabmod.sign, tabmod.variables, tabmod.integers)
+        out[i] = solution(view, status, result, opt)
+    if stats is not None:
+        stats.update(warm=len(warm), cold=len(cold), pivots=[int(r[2]) for r in results])
+    if cold:
+        sub = {} if stats is not None else None
+        for i, r in zip(cold, cold_fn(model, [variants[i] for i in cold], [opts[i] for i in cold], sub)):
+            out[i] = r
+        if stats is not None:
+            stats["solve_variants"] = sub
+    return out
+
+
+def reoptimize_variants(model, variants, options=None, base_options=None, stats=None):
+    """Many variants of ONE model, each REOPTIMISED from the optimal tableau of the model itself: the same list of dicts as
+    solve_variants, in input order, for scenario analysis, parametric sweeps and pricing loops in which a variant moves
+    bounds and objective coefficients.  `options` is one dict for all variants or one per variant; `base_options` are the
+    options of the one solve of `model` itself (default: the defaults).
+
+    The contract is NOT solve_variants'.  A variant that moves only right-hand sides and objective coefficients leaves the
+    body of the base's optimal tableau valid and changes only its column 0 and its row 0; each answer is what `simplex`
+    returns when started from that updated tableau with the base's basis (phase 1 repairs a right-hand side that went
+    negative, phase 2 continues, as after every branch-and-cut node's cuts).  It is a valid answer for the variant's LP --
+    the same status wherever the LP has one answer, the objective equal under the reference's validator -- but not
+    necessarily the dict solve() gives: where the LP has several optimal vertices another one is possible.  maxPivots and
+    checkCycles count the reoptimisation's pivots alone, so a budget that ends solve() early may not end this at all, and one
+    that ends it leaves another tableau.  The reference's phase 1 makes no promise from an arbitrary basis: after large moves
+    (bounds of a 300 x 280 dense LP by +-50 %: 20 of 256 variants, README) it can run into maxPivots and end "cycled" where
+    a solve from the initial tableau ends "optimal".  That answer is handed back as it is; solve_variants is the call for such
+    variants.
+
+    Routing, on the host in one pass.  The whole call goes to solve_variants, with the same arguments, where the base has
+    integer variables, a tableau above 4 MiB, or does not end "optimal".  A single variant goes there (all such variants in
+    one call) where it changes the tableau's structure (variant_patch_cells gives None), changes a constraint coefficient
+    (a cell with row > 0 and col > 0), or moves a cell by something that is not finite.  Everything else goes through ONE
+    yalps_lpwarm_solve: the base is solved once on the device, and every variant starts from a copy of its final tableau
+    with a few records folded into column 0 and row 0.  Cells whose value does not differ from the base's are dropped.
+
+    stats (a dict, optional) receives "warm" and "cold" (variants that went each way), "base_status" and "base_pivots",
+    "pivots" (per warm variant, in input order), "launches", "reruns" and "kernels" of the native call, and under
+    "solve_variants" the stats of the cold call."""
+    return _reoptimize_variants_with(lpwarm_simplex, solve_variants, model, variants, options, base_options, stats)
+
+
 # sensitivity(model, options) / sensitivity_many(models, options, stats): solve()'s answer plus duals, reduced costs and ranges
 from .sensitivity import _sensitivity_many_with, sensitivity, sensitivity_many  # noqa: E402,F401
