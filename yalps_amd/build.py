@@ -11,6 +11,7 @@
 The .so files are git-ignored but travel to the GPU box with the tree.
 """
 import os
+import re
 import shutil
 import subprocess
 
@@ -109,6 +110,17 @@ def kernel_metadata(lib=LIB):
 NO_SCRATCH = ("lp_sens", "lp_variants", "lp_warm", "milp_node_kernel", "dshard_kernel", "dshard_select_kernel", "dshard_sweep_kernel", "small_kernel", "batch_kernel", "assemble", "resident_kernel", "resident2_kernel", "stream_kernel", "stream2_kernel", "stream3_kernel", "sweep_kernel")
 
 
+# resident2_kernel<T, J, R>: scalar registers spilled to lanes of vector registers (sgpr_spill_count), at most what each
+# instantiation was built with when its rows became slot vectors (before that: 52, 75, 58, 58, 68, 105, 67; the aim of 0
+# for <512,2,9> was not reached).  Every reload is a v_readlane on a chain that is instruction-issue bound (DESIGN.md
+# 4.2b); the no-scratch rule does not see them.  The counts are this compiler's: if another ROCm moves one up, read the
+# kernel's ISA (the loop of resident2_kernel.cuh, v_readlane / v_writelane between the barriers) before raising its
+# bound -- a few more spills off the pivot chain cost nothing, a mask or a pointer reloaded on it every pivot does --
+# and lower the bounds a newer compiler undercuts.
+RESIDENT2_SGPR_SPILLS = {(256, 1, 4): 7, (256, 1, 9): 14, (256, 2, 4): 11, (512, 2, 4): 11, (512, 2, 6): 17, (512, 2, 9): 23,
+                         (512, 3, 4): 21}
+
+
 def check_register_budgets(lib=LIB, min_resident=15):
     """min_resident=0: a library without the register-resident kernels (libyalps_lpbatch.so); the no-scratch rule holds as it is,
     and the kernels under it may not use accumulator registers either."""
@@ -120,6 +132,13 @@ def check_register_budgets(lib=LIB, min_resident=15):
     for name, md in sorted(ks.items()):
         if ("resident_kernel" in name or "resident2_kernel" in name) and (int(md["vgpr_count"]) > 256 or int(md["agpr_count"]) != 0):
             bad.append("%s: vgpr_count %s agpr_count %s" % (name, md["vgpr_count"], md["agpr_count"]))
+        r2 = re.search(r"resident2_kernelILi(\d+)ELi(\d+)ELi(\d+)EE", name)
+        if r2:
+            shape = tuple(int(x) for x in r2.groups())
+            if shape not in RESIDENT2_SGPR_SPILLS:
+                bad.append("%s: no sgpr_spill_count bound for this instantiation" % name)
+            elif int(md.get("sgpr_spill_count", 0)) > RESIDENT2_SGPR_SPILLS[shape]:
+                bad.append("%s: sgpr_spill_count %s, bound %d" % (name, md.get("sgpr_spill_count"), RESIDENT2_SGPR_SPILLS[shape]))
         if any(tag in name for tag in NO_SCRATCH) and int(md["private_segment_fixed_size"]) != 0:
             bad.append("%s: private_segment_fixed_size %s (scratch)" % (name, md["private_segment_fixed_size"]))
         queue = "lp_batch_kernel" in name or "milp_node_kernel" in name or "lp_variants_kernel" in name or "lp_sens_kernel" in name or "lp_warm_kernel" in name

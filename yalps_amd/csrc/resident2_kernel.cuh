@@ -22,6 +22,9 @@
 //     step, ballot + readlane for the index, log2(waves) steps in the second level;
 //   * five workgroup barriers per pivot instead of eight; the candidate row is stored from the registers it was just
 //     computed in.
+//   * the rows are held as slot vectors (Slots<R> below): what a wave-uniform slot index selects at run time -- the
+//     candidate row, the pivot row -- is one register-relative move per word instead of an R-way ladder of branches
+//     with a copy of the row's code behind each.
 // Variants: plain rows in registers only (the LDS-row and tagged-granule variants stay on resident_kernel).
 // ------------------------------------------------------------------------------------------
 
@@ -101,6 +104,92 @@ __device__ __forceinline__ KI block_argmin2(KI v, double (*sk)[16], int (*si)[16
     return r;
 }
 
+// The R row slots of ONE tableau element of a lane as one vector value (vector lane = row slot).  A slot index known at
+// compile time (the unrolled loops over all slots) names a register as before; a wave-uniform index known at run time
+// compiles to a register-relative move (s_set_gpr_idx_on + v_mov_b32, two per double) -- a C array indexed like that goes
+// to scratch, a vector value does not.  R = 4: 4 wide; R = 6: 8 wide, two slots unused; R = 9: 8 wide plus slot 8 in a
+// register of its own (a 9-wide vector is widened to 16: 32 registers per element instead of 18).
+template <int R>
+struct Slots {
+    static constexpr int W = R <= 4 ? 4 : 8;
+    static_assert(R <= W + 1, "row slots per workgroup");
+    typedef double V __attribute__((ext_vector_type(W)));
+    V v;
+    double odd; // slot W (R == W + 1 only)
+    // g: a compile-time constant once the loop around the call is unrolled
+    __device__ __forceinline__ double at(int g) const { return g < W ? v[g & (W - 1)] : odd; }
+    __device__ __forceinline__ void set(int g, double a) {
+        if (g < W)
+            v[g & (W - 1)] = a;
+        else
+            odd = a;
+    }
+    // s: wave-uniform, in a scalar register.  The index reaches the vector as it is, with no mask in front of it: an index
+    // the compiler can prove to be in range lets it turn the access into address arithmetic on a copy in memory
+    // (scratch) wherever the vector is still behind a reference, as in the lambdas of the kernel.
+    __device__ __forceinline__ static int vslot(int s) {
+        s = __builtin_amdgcn_readfirstlane(s);
+        if constexpr (R > W) return s < W ? s : 0;
+        return s;
+    }
+    __device__ __forceinline__ double get(int s) const {
+        const double a = v[vslot(s)];
+        if constexpr (R > W) return s < W ? a : odd;
+        return a;
+    }
+    __device__ __forceinline__ void put(int s, double a) {
+        if constexpr (R > W) { // (selects on the two words, not a branch around the indexed write: no copy of the vector)
+            const int i = vslot(s);
+            const double keep = v[i];
+            v[i] = s < W ? a : keep;
+            odd = s < W ? odd : a;
+        } else {
+            v[vslot(s)] = a;
+        }
+    }
+};
+
+// The N = 2 J slot vectors of a lane, element k = 2 j + e, reached through compile-time indices only (EACH_ELEM below):
+// an array indexed by a loop variable stays in memory until the loop is unrolled, and by then the run-time slot reads
+// have been turned into address arithmetic on that memory -- scratch.  Members named by constants are values from the
+// first pass on.
+template <int R, int N>
+struct SlotRows {
+    Slots<R> head;
+    SlotRows<R, N - 1> tail;
+    template <int K>
+    __device__ __forceinline__ Slots<R> &el() {
+        if constexpr (K == 0)
+            return head;
+        else
+            return tail.template el<K - 1>();
+    }
+};
+template <int R>
+struct SlotRows<R, 0> {};
+template <int K>
+struct IntC {
+    static constexpr int value = K;
+};
+template <int N, int K = 0, class F>
+__device__ __forceinline__ void static_for(F &&f) {
+    if constexpr (K < N) {
+        f(IntC<K>{});
+        static_for<N, K + 1>(f);
+    }
+}
+// EACH_ELEM(k, j, e, xe) { ... };  -- the block once per element of mine, with j, e constants and xe its slot vector
+#define EACH_ELEM(k, j, e, xe)                                                                                          \
+    static_for<2 * J>([&](auto k) __attribute__((always_inline)) {                                                     \
+        constexpr int j = decltype(k)::value / 2, e = decltype(k)::value % 2;                                         \
+        [[maybe_unused]] Slots<R> &xe = x.template el<decltype(k)::value>();
+#define END_EACH_ELEM });
+// Last statement of an arm of a ladder over the elements (`if (j == .. && e == ..) { the same code on xe }`): an empty
+// asm with the element's number as an immediate, which no two arms share.  Without it the arms are merged into one
+// block that reaches its vector through a selected POINTER -- inside a lambda, where the vectors are still behind a
+// reference, that is legal and keeps them in memory (scratch) for good.
+#define KEEP_ARM(k) asm volatile("" ::"i"(decltype(k)::value))
+
 template <int T, int J, int R>
 __global__ __launch_bounds__(T) void resident2_kernel(Desc d, int parity, int chunk) {
     constexpr int SPLIT = YALPS_SPLIT_NUM * R / 4; // other rows eliminated between the candidate row's stores and its flag
@@ -114,7 +203,12 @@ __global__ __launch_bounds__(T) void resident2_kernel(Desc d, int parity, int ch
     __shared__ int sh_ci, sh_cg, sh_fail, sh_flag, sh_verdict, sh_pnz;
     extern __shared__ int sh_perm[]; // workgroup 0: var[perm_len] then pos[perm_len]
 
-    const int tid = threadIdx.x, NB = d.nb, b = blockIdx.x;
+    const int NB = d.nb, b = blockIdx.x;
+    // The lane's number, made opaque again at a few points of the loop (FRESH_TID): the lane tests on it -- tid < R,
+    // tid == 0, c0 < pitch ... -- are loop invariants, which the compiler otherwise computes once and carries through the
+    // whole loop as 64-bit masks in scalar registers, to the point of spilling them; a v_cmp where one is used is cheaper.
+    int tid = threadIdx.x;
+#define FRESH_TID() asm volatile("" : "+v"(tid))
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const YState *Sin = d.st + parity;
     YState *Sout = d.st + (parity ^ 1);
@@ -133,6 +227,10 @@ __global__ __launch_bounds__(T) void resident2_kernel(Desc d, int parity, int ch
     int64_t pivots = Sin->pivots;
     int64_t hist_len = Sin->hist_len; // checkCycles: pivots recorded in the current phase (src/simplex.ts:67,107)
     const bool check_cycles = C->check_cycles != 0;
+    // (the two counters nothing branches on per lane, kept in vector registers: as uniform values each held a pair of
+    // scalar registers through the whole loop, and `iter` came back from its v_add_f64 through two v_readfirstlane)
+    asm volatile("" : "+v"(iter));
+    asm volatile("" : "+v"(pivots));
     int slot = 0;
 
     int cofs[J];
@@ -150,7 +248,12 @@ __global__ __launch_bounds__(T) void resident2_kernel(Desc d, int parity, int ch
         for (int k = 0; k < 2; k++)
             if (2 * (tid + j * T) + k >= n) padmask |= 1u << (2 * j + k);
     // ---- load my rows, the objective replica, my rows' RHS (lane g), the basis (workgroup 0) ----
-    double2 x[R][J], o[J];
+    SlotRows<R, 2 * J> x; // element e of my unit j, every row slot: el<2 j + e>()
+    double2 o[J];
+    EACH_ELEM(k, j, e, xe)
+        xe.v = 0.0;
+        xe.odd = 0.0;
+    END_EACH_ELEM
 #pragma unroll
     for (int j = 0; j < J; j++) {
         o[j] = *reinterpret_cast<const double2 *>(matA + cofs[j]);
@@ -163,12 +266,18 @@ __global__ __launch_bounds__(T) void resident2_kernel(Desc d, int parity, int ch
     for (int g = 0; g < R; g++) {
         const int r = b + NB * g;
         const double *mr = matA + (size_t)(r < h ? r : b) * pitch;
+        double2 t[J];
 #pragma unroll
-        for (int j = 0; j < J; j++) x[g][j] = *reinterpret_cast<const double2 *>(mr + cofs[j]);
+        for (int j = 0; j < J; j++) t[j] = *reinterpret_cast<const double2 *>(mr + cofs[j]);
+        EACH_ELEM(k, j, e, xe)
+            xe.set(g, e ? t[j].y : t[j].x);
+        END_EACH_ELEM
     }
-    const int my_r = b + NB * tid; // lane g = tid < R owns the scalar side of row slot g
-    const bool my_live = tid < R && my_r < h;
-    double my_rhs = rhsA[my_live ? my_r : 0];
+    const int nlive = b < h ? (h - b + NB - 1) / NB : 0; // row slots of mine that hold a row: b + NB * g < h <=> g < nlive
+    // lane g = tid < R owns the scalar side of row slot g
+    auto my_row = [&]() __attribute__((always_inline)) { return b + NB * tid; };
+    auto my_live = [&]() __attribute__((always_inline)) { return tid < R && tid < nlive; };
+    double my_rhs = rhsA[my_live() ? my_row() : 0];
     if (b == 0) {
         for (int i = tid; i < d.perm_len; i += T) {
             sh_perm[i] = d.var[i];
@@ -210,18 +319,23 @@ __global__ __launch_bounds__(T) void resident2_kernel(Desc d, int parity, int ch
     auto deposit_la = [&](const double2 (&pvn)[J], unsigned nzmask, bool pending) __attribute__((always_inline)) {
         const int ula = (la - 1) >> 1, ela = (la - 1) & 1, lt = ula % T, lj = ula / T;
         if (la > 0 && wave == (lt >> 6)) { // (uniform)
+            if (tid == lt) { // (one lane of the workgroup holds the column)
+                EACH_ELEM(k, j, e, xe)
+                    if (j == lj && e == ela) { // (uniform: which of my 2 J vectors)
 #pragma unroll
-            for (int j = 0; j < J; j++)
-#pragma unroll
-                for (int e = 0; e < 2; e++)
-                    if (2 * (tid + j * T) + e + 1 == la) { // (one lane of the workgroup, one (j, e): no register is indexed at run time)
-#pragma unroll
-                        for (int g = 0; g < R; g++) sh_raw[g] = e ? x[g][j].y : x[g][j].x;
-                        if (pending) {
-                            sh_raw[R] = e ? pvn[j].y : pvn[j].x;
-                            sh_pnz = (nzmask >> (2 * j + e)) & 1u;
-                        }
+                        for (int g = 0; g < R; g++) sh_raw[g] = xe.at(g);
+                        KEEP_ARM(k);
                     }
+                END_EACH_ELEM
+                if (pending) {
+#pragma unroll
+                    for (int j = 0; j < J; j++)
+                        if (j == lj) {
+                            sh_raw[R] = elem(pvn[j], ela);
+                            sh_pnz = (nzmask >> (2 * j + ela)) & 1u;
+                        }
+                }
+            }
         }
         __syncthreads();
     };
@@ -231,7 +345,8 @@ __global__ __launch_bounds__(T) void resident2_kernel(Desc d, int parity, int ch
     auto candidate = [&](int kind, double value, int which, bool barrier) __attribute__((always_inline)) {
         if (wave == 0) {
             KI c = {INFINITY, INT_MAX};
-            if (my_live && my_r >= 1) {
+            const int my_r = my_row();
+            if (my_live() && my_r >= 1) {
                 if (kind == 1) {
                     if (my_rhs < -precision) {
                         c.k = my_rhs;
@@ -267,15 +382,17 @@ __global__ __launch_bounds__(T) void resident2_kernel(Desc d, int parity, int ch
     auto publish_stores = [&](int cg) __attribute__((always_inline)) {
         epoch++;
         double *dst = d.rc_rows[epoch & 1] + (size_t)b * pitch;
+        double2 crow[J]; // (cg: uniform -- one store sequence for whichever slot it names)
+        EACH_ELEM(k, j, e, xe)
+            if (e)
+                crow[j].y = xe.get(cg);
+            else
+                crow[j].x = xe.get(cg);
+        END_EACH_ELEM
 #pragma unroll
-        for (int g = 0; g < R; g++) {
-            if (g == cg) { // (uniform; the slot index stays a compile-time constant: the rows are registers)
-#pragma unroll
-                for (int j = 0; j < J; j++) {
-                    const int c0 = 2 * (tid + j * T);
-                    if (c0 < pitch) st16_sc1(dst + c0, x[g][j]);
-                }
-            }
+        for (int j = 0; j < J; j++) {
+            const int c0 = 2 * (tid + j * T);
+            if (c0 < pitch) st16_sc1(dst + c0, crow[j]);
         }
         if (tid == cg) st_sc1(d.rc_key[epoch & 1] + b, my_rhs); // the candidate row's RHS entry (lane cg)
     };
@@ -289,7 +406,7 @@ __global__ __launch_bounds__(T) void resident2_kernel(Desc d, int parity, int ch
     auto check = [&]() __attribute__((always_inline)) {
         if (done == chunk) {
             stop = true;
-        } else if (!(iter < max_pivots)) {
+        } else if (__builtin_amdgcn_ballot_w64(!(iter < max_pivots)) != 0) { // (every lane holds the same iter)
             term = YALPS_CYCLED;
             stop = true;
         } else if (phase == 2 && la == 0) {
@@ -320,6 +437,7 @@ __global__ __launch_bounds__(T) void resident2_kernel(Desc d, int parity, int ch
 #endif
     // (single back edge, single exit: every `stop` is a flag, so the rows stay in one set of registers)
     while (!stop) {
+        FRESH_TID();
         // ---------------- gather everyone's candidate -------------------------------------------
         const int par = epoch & 1;
         KI c = {INFINITY, INT_MAX};
@@ -424,11 +542,16 @@ __global__ __launch_bounds__(T) void resident2_kernel(Desc d, int parity, int ch
             // pivot-column entries of my rows, of the objective row, the quotient: from the lane that holds the column
             const int ucol1 = (col - 1) >> 1, ecol1 = (col - 1) & 1;
             if (tid == ucol1 % T) {
+                EACH_ELEM(k, j, e, xe)
+                    if (j == ucol1 / T && e == ecol1) {
+#pragma unroll
+                        for (int g = 0; g < R; g++) sh_cf[cur][g] = xe.at(g);
+                        KEEP_ARM(k);
+                    }
+                END_EACH_ELEM
 #pragma unroll
                 for (int j = 0; j < J; j++)
                     if (j == ucol1 / T) {
-#pragma unroll
-                        for (int g = 0; g < R; g++) sh_cf[cur][g] = elem(x[g][j], ecol1);
                         sh_cf[cur][R] = elem(o[j], ecol1);
                         sh_cf[cur][R + 1] = elem(pv[j], ecol1);
                     }
@@ -474,20 +597,23 @@ __global__ __launch_bounds__(T) void resident2_kernel(Desc d, int parity, int ch
             }
         }
         YSTAMP(3); // phase 1: entering column + column gather; checkCycles: verdict
+        FRESH_TID();
         // ---------------- pivot (src/simplex.ts:5-39) on my registers ----------------------------
         const int ucol = (col - 1) >> 1, ecol = (col - 1) & 1, col_tid = ucol % T, col_j = ucol / T;
         const int col_wave = col_tid >> 6;
-        double cf[R]; // uniform: pivot-column entry of each of my rows (phase 2: left there by the last look-ahead)
+        // uniform: pivot-column entry of each of my rows (phase 2: left there by the last look-ahead).  In vector registers
+        // (v_mul_f64 takes them as they are): as 2 R scalar registers they were most of what this kernel spilled
+        Slots<R> cf;
+        cf.v = 0.0;
+        cf.odd = 0.0;
 #pragma unroll
-        for (int g = 0; g < R; g++) // (scalar registers where the VGPR budget of 2 waves per SIMD is short)
-            cf[g] = (T >= 512 && J * R >= 18) ? uniform_f64(sh_cf[cur][g]) : sh_cf[cur][g];
+        for (int g = 0; g < R; g++) cf.set(g, sh_cf[cur][g]);
         const double my_coef = tid < R ? sh_cf[cur][tid] : 0.0;
-        // rows of mine this pivot changes (:31), one bit per slot, in scalar registers
+        // rows of mine this pivot changes (:31), one bit per slot (R <= 9 bits: one scalar register)
         const int lane = tid & 63;
         const double lane_cf = sh_cf[cur][lane < R ? lane : 0];
-        const unsigned long long touched = __builtin_amdgcn_ballot_w64(lane < R && b + NB * lane < h && fabs(lane_cf) > 1e-16);
-        const unsigned long long live = __builtin_amdgcn_ballot_w64(lane < R && b + NB * lane < h);
-        const bool all_touched = touched == live;
+        const unsigned touched = (unsigned)__builtin_amdgcn_ballot_w64(lane < R && lane < nlive && fabs(lane_cf) > 1e-16);
+        const bool all_touched = touched == (1u << (nlive < R ? nlive : R)) - 1u;
         // :14-24 normalise; which of my columns were flushed
         unsigned nzmask = 0;
 #pragma unroll
@@ -510,7 +636,7 @@ __global__ __launch_bounds__(T) void resident2_kernel(Desc d, int parity, int ch
             my_nq = quot;
             if (tid < R || tid == R + 1) sh_nq[tid] = quot;
             const double rhs_q = lane_f64(quot, R + 2);
-            if (my_live) { // RHS entry of my row (:33 at column 0)
+            if (my_live()) { // RHS entry of my row (:33 at column 0)
                 const double pn_rhs = nz_rhs ? rhs_q : 0.0;
                 if (tid == lslot)
                     my_rhs = pn_rhs;
@@ -558,53 +684,100 @@ __global__ __launch_bounds__(T) void resident2_kernel(Desc d, int parity, int ch
         price(); // la of the next pivot, from the updated objective replica (its barrier also publishes sh_nq)
         check();
         YSTAMP(6);
+        FRESH_TID();
         // my rows in the slots of `set` (bit g), fully, as pivot() leaves them
-        auto finish_rows = [&](unsigned long long set) __attribute__((always_inline)) {
-            const unsigned long long pivbit = lslot >= 0 ? (1ull << lslot) & set : 0ull; // the pivot row, if it is mine and in the set
-            const unsigned long long elim = set & touched & ~pivbit;                      // rows to eliminate (:31)
+        // R > 4: a loop over the slots in the set, each reached through the register-relative moves -- one copy of the
+        // row's code whatever R is, and only as many trips as rows change (on sparse tableaux, where this path runs, a
+        // few).  R <= 4: the slots in turn behind scalar tests, as constants, as before the slot vectors -- a ladder that
+        // short costs less than the moves (profiles/resident2_slots_shapes.json: the netlib LPs on <512,2,4> and <512,3,4>
+        // with the loop, the ladder and the parent's code, one call).
+        auto finish_rows = [&](unsigned set) __attribute__((always_inline)) {
+            const unsigned pivbit = lslot >= 0 ? (1u << lslot) & set : 0u; // the pivot row, if it is mine and in the set
+            const unsigned elim = set & touched & ~pivbit;                 // rows to eliminate (:31)
+            const bool holds_col = wave == col_wave && tid == col_tid;     // the one lane that holds the pivot column (:25, :36)
+            if constexpr (R <= 4) {
+                // the rows as separate registers for the length of the ladder (taking a vector apart and putting it together
+                // again with constant indices is register naming, no instruction): a conditional write to a slot of a vector
+                // merges two whole vectors behind the test, and the copies that costs did not fit <512,3,4>
+                double2 r[R][J];
+                EACH_ELEM(k, j, e, xe)
 #pragma unroll
-            for (int g = 0; g < R; g++) { // (g must stay a compile-time index: the rows are registers; every test is scalar)
-                if ((pivbit >> g) & 1u) {
+                    for (int g = 0; g < R; g++) {
+                        if (e)
+                            r[g][j].y = xe.at(g);
+                        else
+                            r[g][j].x = xe.at(g);
+                    }
+                END_EACH_ELEM
 #pragma unroll
-                    for (int j = 0; j < J; j++) x[g][j] = pv[j];
-                } else if ((elim >> g) & 1u) {
-                    if (fast) {
+                for (int g = 0; g < R; g++) { // (every test is scalar)
+                    if ((pivbit >> g) & 1u) {
 #pragma unroll
-                        for (int j = 0; j < J; j++) {
-                            const double px = cf[g] * pv[j].x, py = cf[g] * pv[j].y;
-                            x[g][j].x = x[g][j].x - px;
-                            x[g][j].y = x[g][j].y - py;
-                        }
-                    } else {
+                        for (int j = 0; j < J; j++) r[g][j] = pv[j];
+                    } else if ((elim >> g) & 1u) {
+                        if (fast) {
 #pragma unroll
-                        for (int j = 0; j < J; j++) {
-                            const double px = cf[g] * pv[j].x, py = cf[g] * pv[j].y;
-                            const double nx = x[g][j].x - px, ny = x[g][j].y - py;
-                            x[g][j].x = (nzmask & (1u << (2 * j))) ? nx : x[g][j].x;
-                            x[g][j].y = (nzmask & (1u << (2 * j + 1))) ? ny : x[g][j].y;
+                            for (int j = 0; j < J; j++) {
+                                const double px = cf.at(g) * pv[j].x, py = cf.at(g) * pv[j].y;
+                                r[g][j].x = r[g][j].x - px;
+                                r[g][j].y = r[g][j].y - py;
+                            }
+                        } else {
+#pragma unroll
+                            for (int j = 0; j < J; j++) {
+                                const double px = cf.at(g) * pv[j].x, py = cf.at(g) * pv[j].y;
+                                const double nx = r[g][j].x - px, ny = r[g][j].y - py;
+                                r[g][j].x = (nzmask & (1u << (2 * j))) ? nx : r[g][j].x;
+                                r[g][j].y = (nzmask & (1u << (2 * j + 1))) ? ny : r[g][j].y;
+                            }
                         }
                     }
                 }
-            }
-            if (wave == col_wave && (elim | pivbit) != 0) { // the pivot column itself (:25, :36): patched by the one lane that holds it
-                if (tid == col_tid) {
+                if (wave == col_wave && (elim | pivbit) != 0) { // the pivot column itself (:25, :36): patched by the one lane that holds it
+                    if (tid == col_tid) {
 #pragma unroll
-                    for (int g = 0; g < R; g++) {
-                        if (!(((elim | pivbit) >> g) & 1u)) continue;
-                        const double v = sh_nq[((pivbit >> g) & 1u) ? R + 1 : g];
+                        for (int g = 0; g < R; g++) {
+                            if (((elim | pivbit) >> g) & 1u) {
+                                const double v = sh_nq[((pivbit >> g) & 1u) ? R + 1 : g];
 #pragma unroll
-                        for (int j = 0; j < J; j++)
-                            if (j == col_j) {
-                                if (ecol)
-                                    x[g][j].y = v;
-                                else
-                                    x[g][j].x = v;
+                                for (int j = 0; j < J; j++)
+                                    if (j == col_j) {
+                                        if (ecol)
+                                            r[g][j].y = v;
+                                        else
+                                            r[g][j].x = v;
+                                    }
                             }
+                        }
                     }
+                }
+                EACH_ELEM(k, j, e, xe)
+#pragma unroll
+                    for (int g = 0; g < R; g++) xe.set(g, e ? r[g][j].y : r[g][j].x);
+                END_EACH_ELEM
+            } else {
+                if (pivbit) {
+                    const double inv = sh_nq[R + 1];
+                    EACH_ELEM(k, j, e, xe)
+                        const double p = e ? pv[j].y : pv[j].x;
+                        xe.put(lslot, (holds_col && j == col_j && e == ecol) ? inv : p);
+                    END_EACH_ELEM
+                }
+#pragma clang loop unroll(disable)
+                for (unsigned m = elim; m != 0; m &= m - 1) {
+                    const int g = __builtin_ctz(m); // (uniform)
+                    const double c = cf.get(g), nq = sh_nq[g];
+                    EACH_ELEM(k, j, e, xe)
+                        const double old = xe.get(g);
+                        const double p = c * (e ? pv[j].y : pv[j].x);
+                        double nv = old - p;
+                        if (!fast) nv = (nzmask & (1u << (2 * j + e))) ? nv : old;
+                        xe.put(g, (holds_col && j == col_j && e == ecol) ? nq : nv);
+                    END_EACH_ELEM
                 }
             }
         };
-        constexpr unsigned long long ONE = 1, ALL = (ONE << R) - 1, LOW = (ONE << SPLIT) - 1;
+        constexpr unsigned ONE = 1, ALL = (ONE << R) - 1, LOW = (ONE << SPLIT) - 1;
         if (!stop) {
             double value = 0.0;
             if (phase == 2) {
@@ -616,7 +789,7 @@ __global__ __launch_bounds__(T) void resident2_kernel(Desc d, int parity, int ch
                     value = sh_raw[tid];
                     if (tid == lslot)
                         value = la == col ? sh_nq[R + 1] : sh_raw[R];
-                    else if (my_live && fabs(my_coef) > 1e-16) {
+                    else if (my_live() && fabs(my_coef) > 1e-16) {
                         if (la == col)
                             value = my_nq;
                         else if (sh_pnz) {
@@ -637,14 +810,13 @@ __global__ __launch_bounds__(T) void resident2_kernel(Desc d, int parity, int ch
                 // the candidate row after this pivot, in registers of its own (x[cg] is updated with the others below: the
                 // same two roundings on the same inputs give the same bits)
                 double2 cand[J];
-                double ccf = 0.0;
-#pragma unroll
-                for (int g = 0; g < R; g++)
-                    if (g == cg) {
-                        ccf = cf[g];
-#pragma unroll
-                        for (int j = 0; j < J; j++) cand[j] = x[g][j];
-                    }
+                const double ccf = cf.get(cg); // (cg: uniform -- register-relative reads, no ladder over the slots)
+                EACH_ELEM(k, j, e, xe)
+                    if (e)
+                        cand[j].y = xe.get(cg);
+                    else
+                        cand[j].x = xe.get(cg);
+                END_EACH_ELEM
                 if (cg == lslot) {
 #pragma unroll
                     for (int j = 0; j < J; j++) cand[j] = pv[j];
@@ -680,38 +852,32 @@ __global__ __launch_bounds__(T) void resident2_kernel(Desc d, int parity, int ch
                     if (tid == cg) st_sc1(d.rc_key[epoch & 1] + b, my_rhs);
                 }
                 publish_flag();
+                EACH_ELEM(k, j, e, xe)
+                    const double p = e ? pv[j].y : pv[j].x;
 #pragma unroll
-                for (int g = 0; g < R; g++)
-#pragma unroll
-                    for (int j = 0; j < J; j++) {
-                        const double px = cf[g] * pv[j].x, py = cf[g] * pv[j].y;
-                        x[g][j].x = x[g][j].x - px;
-                        x[g][j].y = x[g][j].y - py;
+                    for (int g = 0; g < R; g++) {
+                        const double prod = cf.at(g) * p;
+                        xe.set(g, xe.at(g) - prod);
                     }
-                if (lslot >= 0) {
-#pragma unroll
-                    for (int g = 0; g < R; g++)
-                        if (g == lslot) {
-#pragma unroll
-                            for (int j = 0; j < J; j++) x[g][j] = pv[j];
-                        }
-                }
+                    if (lslot >= 0) xe.put(lslot, p); // (uniform: the pivot row, if it is mine)
+                END_EACH_ELEM
                 if (wave == col_wave) {
-                    if (tid == col_tid) {
+                    // (every test but the lane's is uniform and stays a scalar branch; the lane's is one select per word:
+                    // as `if (tid == col_tid)` around the loop, `g < nlive` became nine 64-bit masks carried through the loop)
+                    const bool holds_col = tid == col_tid;
+                    int nl = nlive;
+                    asm volatile("" : "+s"(nl)); // (opaque: R loop-invariant comparisons are R more masks to carry)
+                    EACH_ELEM(k, j, e, xe)
+                        if (j == col_j && e == ecol) { // (uniform: which of my 2 J vectors holds the column)
 #pragma unroll
-                        for (int g = 0; g < R; g++) {
-                            if (b + NB * g >= h) continue;
-                            const double v = sh_nq[g == lslot ? R + 1 : g];
-#pragma unroll
-                            for (int j = 0; j < J; j++)
-                                if (j == col_j) {
-                                    if (ecol)
-                                        x[g][j].y = v;
-                                    else
-                                        x[g][j].x = v;
+                            for (int g = 0; g < R; g++)
+                                if (g < nl) {
+                                    const double v = sh_nq[g == lslot ? R + 1 : g];
+                                    xe.set(g, holds_col ? v : xe.at(g));
                                 }
+                            KEEP_ARM(k);
                         }
-                    }
+                    END_EACH_ELEM
                 }
             } else {
                 candidate(phase, value, cur ^ 1, true);
@@ -759,19 +925,28 @@ __global__ __launch_bounds__(T) void resident2_kernel(Desc d, int parity, int ch
     // ---------------- leave: tableau to the other buffer, state, basis ---------------------------
     double *matB = d.mat[mbuf ^ 1];
     double *rhsB = d.rhs[mbuf ^ 1];
+    int nl = nlive;
+    asm volatile("" : "+s"(nl)); // (opaque: not R `r < h` masks carried from the load loop to here)
 #pragma unroll
     for (int g = 0; g < R; g++) {
         const int r = b + NB * g;
-        if (r < h) {
+        if (g < nl) { // <=> r < h
             double *mr = matB + (size_t)r * pitch;
+            double2 t[J];
+            EACH_ELEM(k, j, e, xe)
+                if (e)
+                    t[j].y = xe.at(g);
+                else
+                    t[j].x = xe.at(g);
+            END_EACH_ELEM
 #pragma unroll
             for (int j = 0; j < J; j++) {
                 const int c0 = 2 * (tid + j * T);
-                if (c0 < pitch) *reinterpret_cast<double2 *>(mr + c0) = x[g][j];
+                if (c0 < pitch) *reinterpret_cast<double2 *>(mr + c0) = t[j];
             }
         }
     }
-    if (my_live) rhsB[my_r] = my_rhs;
+    if (my_live()) rhsB[my_row()] = my_rhs;
     if (b == 0) {
         // (the last pivot's basis swap was one lane's LDS writes at the very end of the loop body, with no barrier behind
         // them: a wave that got here first copied the old entries -- seen once in 380 GPU tests, on a 60-pivot solve)
@@ -803,3 +978,7 @@ __global__ __launch_bounds__(T) void resident2_kernel(Desc d, int parity, int ch
         }
     }
 }
+#undef EACH_ELEM
+#undef FRESH_TID
+#undef KEEP_ARM
+#undef END_EACH_ELEM
