@@ -10,6 +10,10 @@ TEST-FIXTURE TOOLING, build container only (needs /root/reference and node).
      section 8d), (c) sparse mixed-sign tableaux with near-1e-16 entries and
      (d) the edge tableaux of tests/_edges.py (ties, infinite ratios, signed
      zeros, the flush band, exact thresholds, extreme exponents),
+     (f) `--only nonfinite`: the tableaux of tests/_nonfinite.py (NaN and
+     infinite entries and options), final state recorded with every NaN word
+     replaced by 0x7ff8000000000000 (V8 and a GPU give arithmetic NaNs
+     different sign bits),
      (e) `--only milp`: the MILP models of tests/_milps.py through the
      reference's solve() (YALPS.ts, branchAndCut.ts on the heap stand-in
      below), recording every popped node, the exit and the Solution,
@@ -60,11 +64,17 @@ const coo = (matrix) => {
   return { idx: b64(Int32Array.from(idx)), val: b64(Float64Array.from(vals)) }
 }
 
-const run = (rec, tableau, options, storeInit) => {
+// every NaN word becomes 0x7ff8000000000000 (little-endian halves), in place
+const canonNaN = (ta) => {
+  const u = new Uint32Array(ta.buffer, ta.byteOffset, 2 * ta.length)
+  for (let i = 0; i < ta.length; i++) if (ta[i] !== ta[i]) { u[2 * i] = 0; u[2 * i + 1] = 0x7ff80000 }
+}
+
+const run = (rec, tableau, options, storeInit, canon) => {
   rec.width = tableau.width; rec.height = tableau.height
   rec.init_sha256 = sha(tableau.matrix)
   if (storeInit) rec.init_coo = coo(tableau.matrix)
-  rec.options = { precision: options.precision, maxPivots: num(options.maxPivots), checkCycles: !!options.checkCycles }
+  rec.options = { precision: canon ? num(options.precision) : options.precision, maxPivots: num(options.maxPivots), checkCycles: !!options.checkCycles }
   globalThis.__yalps_trace = []
   const t0 = Date.now()
   const [status, result] = simplex(tableau, options)
@@ -73,10 +83,12 @@ const run = (rec, tableau, options, storeInit) => {
   rec.n_pivots = globalThis.__yalps_trace.length / 2
   rec.pivots = b64(Int32Array.from(globalThis.__yalps_trace))
   rec.pos = b64(tableau.positionOfVariable); rec.var = b64(tableau.variableAtPosition)
+  if (canon) canonNaN(tableau.matrix)
   const col0 = new Float64Array(tableau.height)
   for (let r = 0; r < tableau.height; r++) col0[r] = tableau.matrix[r * tableau.width]
+  if (canon) canonNaN(col0)
   rec.col0 = b64(col0)
-  rec.final_sha256 = sha(tableau.matrix)
+  rec[canon ? "final_canon_sha256" : "final_sha256"] = sha(tableau.matrix)
   console.log(JSON.stringify(rec))
 }
 
@@ -195,6 +207,17 @@ if (mode === "cases") {
     run({ kind: "edges", family: spec.family, M: spec.M, N: spec.N, seed: spec.seed, layout: spec.layout },
         { matrix, width: w, height: h, positionOfVariable: pos, variableAtPosition: vr }, opts, w * h <= 20000)
   }
+} else if (mode === "nonfinite") {
+  // tableaux of tests/_nonfinite.py, as raw float64 files; precision and maxPivots travel as strings (JSON has no NaN)
+  for (const spec of JSON.parse(fs.readFileSync(process.argv[3], "utf-8"))) {
+    const buf = fs.readFileSync(spec.file)
+    const matrix = new Float64Array(buf.buffer.slice(buf.byteOffset, buf.byteOffset + buf.length))
+    const w = spec.N + 1, h = spec.M + 1
+    const [pos, vr] = identityPerms(w + h)
+    const opts = { precision: Number(spec.precision), maxPivots: Number(spec.maxPivots), checkCycles: spec.checkCycles }
+    run({ kind: "nonfinite", family: spec.family, M: spec.M, N: spec.N, seed: spec.seed, layout: spec.layout },
+        { matrix, width: w, height: h, positionOfVariable: pos, variableAtPosition: vr }, opts, false, true)
+  }
 }
 """
 
@@ -280,6 +303,35 @@ def edge_specs(tmp):
     return os.path.join(tmp, "edges.json")
 
 
+def nonfinite_records(erased, tmp):
+    """The records of tests/_nonfinite.py, one shape at a time (the raw float64 files of a shape are removed before the
+    next one is written)."""
+    sys.path.insert(0, REPO)
+    from tests import _edges as E
+    from tests import _nonfinite as NF
+    js = {"nan": "NaN", "inf": "Infinity", "-inf": "-Infinity"}
+    recs = []
+    for shape in E.SHAPES:
+        specs, files = [], []
+        for family, M, N, seed in NF.specs():
+            if (M, N) != shape:
+                continue
+            layout = E.default_layout(M, N)
+            path = os.path.join(tmp, "nonfinite_%04d.f64" % len(files))
+            NF.make(family, M, N, seed, layout).tofile(path)
+            files.append(path)
+            o = NF.options(family, M, N, seed)
+            specs.append(dict(file=path, family=family, M=M, N=N, seed=seed, layout=[list(layout[0]), list(layout[1])],
+                              precision=js.get(repr(o["precision"]), repr(o["precision"])),
+                              maxPivots=js.get(repr(o["max_pivots"]), repr(o["max_pivots"])), checkCycles=o["check_cycles"]))
+        with open(os.path.join(tmp, "nonfinite.json"), "w") as f:
+            json.dump(specs, f)
+        recs += run_driver(erased, "nonfinite", os.path.join(tmp, "nonfinite.json"))
+        for path in files:
+            os.remove(path)
+    return recs
+
+
 def milp_specs(tmp):
     """The models of tests/_milps.py with their options, as the driver's "milp" mode reads them."""
     sys.path.insert(0, REPO)
@@ -306,7 +358,7 @@ def compact(rec):
         rec[key] = {"n": int(p.size), "idx": base64.b64encode(idx.tobytes()).decode(),
                     "val": base64.b64encode(p[idx].tobytes()).decode()}
     if rec["height"] > 1024:
-        rec["col0_sha256"] = hashlib.sha256(base64.b64decode(rec.pop("col0"))).hexdigest()
+        rec["col0_canon_sha256" if rec["kind"] == "nonfinite" else "col0_sha256"] = hashlib.sha256(base64.b64decode(rec.pop("col0"))).hexdigest()
     return rec
 
 
@@ -314,7 +366,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--max-dense", type=int, default=2048)
     ap.add_argument("--erased-dir", default="/tmp/yalps_erased")
-    ap.add_argument("--only", nargs="*", default=("cases", "mixed", "dense", "edges", "milp"))
+    ap.add_argument("--only", nargs="*", default=("cases", "mixed", "dense", "edges", "milp", "nonfinite"))
     args = ap.parse_args()
 
     erased = erase(args.erased_dir)
@@ -326,13 +378,16 @@ def main():
     os.makedirs(os.path.join(golden, "cases"), exist_ok=True)
 
     tmp = tempfile.mkdtemp(prefix="yalps_edges_")
-    for mode, extra in (("cases", ()), ("mixed", ()), ("dense", (args.max_dense,)), ("edges", ()), ("milp", ())):
+    for mode, extra in (("cases", ()), ("mixed", ()), ("dense", (args.max_dense,)), ("edges", ()), ("milp", ()), ("nonfinite", ())):
         if mode not in args.only:
             continue
         t0 = time.time()
         specs = {"edges": edge_specs, "milp": milp_specs}.get(mode)
-        recs = run_driver(erased, mode, *(extra if specs is None else (specs(tmp),)))
-        if mode == "edges":
+        if mode == "nonfinite":
+            recs = nonfinite_records(erased, tmp)
+        else:
+            recs = run_driver(erased, mode, *(extra if specs is None else (specs(tmp),)))
+        if mode in ("edges", "nonfinite"):
             recs = [compact(r) for r in recs]
         path = os.path.join(golden, f"simplex_{mode}.json.gz")
         src = "YALPS.ts, branchAndCut.ts on the heap stand-in of gen_golden.py" if mode == "milp" else "simplex.ts"

@@ -35,6 +35,22 @@ def sha256(arr):
     return hashlib.sha256(np.ascontiguousarray(arr).tobytes()).hexdigest()
 
 
+NAN_WORD = 0x7FF8000000000000
+
+
+def canon(arr):
+    """A copy with every NaN word replaced by the quiet NaN 0x7ff8000000000000: all NaNs are one value."""
+    out = np.ascontiguousarray(arr, dtype=np.float64).copy()
+    out.view(np.uint64)[np.isnan(out)] = NAN_WORD
+    return out
+
+
+def sha256_canon(arr):
+    """SHA-256 of the doubles with all NaNs made one value (the reference's engine and a GPU give arithmetic NaNs different
+    sign bits and payloads)."""
+    return sha256(canon(arr))
+
+
 def initial_matrix(rec, oracle=None, dense_gen=None):
     """Initial row-major tableau of a record (COO-decoded, or regenerated for dense records)."""
     w, h = rec["width"], rec["height"]
@@ -58,16 +74,18 @@ def _perm(x):
 
 
 def expected(rec):
-    """col0 is None where a record keeps only its digest (col0_sha256: edge records of more than 1024 rows)."""
+    """col0 is None where a record keeps only its digest (col0_sha256: edge records of more than 1024 rows).  The
+    non-finite records (tests/_nonfinite.py) hold col0 and the digests with all NaNs made one value (`*_canon_sha256`)."""
     return dict(status=rec["status"], result=_num(rec["result"]), n_pivots=rec["n_pivots"],
                 pivots=_dec(rec["pivots"], np.int32).reshape(-1, 2), pos=_perm(rec["pos"]), var=_perm(rec["var"]),
                 col0=_dec(rec["col0"], np.float64) if "col0" in rec else None, col0_sha256=rec.get("col0_sha256"),
-                final_sha256=rec["final_sha256"])
+                final_sha256=rec.get("final_sha256"), col0_canon_sha256=rec.get("col0_canon_sha256"),
+                final_canon_sha256=rec.get("final_canon_sha256"))
 
 
 def options(rec):
     o = rec["options"]
-    return dict(precision=o["precision"], max_pivots=_num(o["maxPivots"]), check_cycles=o["checkCycles"])
+    return dict(precision=_num(o["precision"]), max_pivots=_num(o["maxPivots"]), check_cycles=o["checkCycles"])
 
 
 def identity_perms(rec):

@@ -114,7 +114,8 @@ def test_every_family_is_rejected_by_some_mutant():
     mutant of its own."""
     hit = {f for fams in TARGETS.values() for f in fams}
     assert set(E.FAMILIES) - hit == {"E3", "E9c"}, set(E.FAMILIES) - hit
-    assert set(TARGETS) | {"keep_col"} == set(NP.MUTANTS)
+    from tests import test_nonfinite_records as T  # (the mutants that only a NaN or an infinity shows have their targets there)
+    assert set(TARGETS) | {"keep_col"} == set(NP.MUTANTS) - set(T.TARGETS)
 
 
 def test_chvatal_family_stops_by_has_cycle():

@@ -172,7 +172,10 @@ __device__ __forceinline__ double dpp_f64(double v) {
     const int lo = dpp_i32<CTRL>(__double2loint(v)), hi = dpp_i32<CTRL>(__double2hiint(v));
     return __hiloint2double(hi, lo);
 }
-// every lane of a 16-lane row gets the row's minimum (keys are never NaN)
+// every lane of a 16-lane row gets the row's minimum.  Keys are never NaN: a candidate becomes a key only behind a comparison
+// that is false for NaN -- `v < -precision` (phase 1 row), `ratio > -INFINITY` (phase 1 column), `rc > precision` (phase 2
+// column), `ratio < INFINITY` (phase 2 row) -- in every kernel, whatever the tableau and the precision hold; a lane without a
+// candidate holds +inf (tests/test_nonfinite_paths.py runs NaN and infinite entries and options through every kernel)
 __device__ __forceinline__ double row16_min(double v) {
     v = fmin(v, dpp_f64<DPP_XOR1>(v));
     v = fmin(v, dpp_f64<DPP_XOR2>(v));

@@ -28,7 +28,9 @@
 // Variants: plain rows in registers only (the LDS-row and tagged-granule variants stay on resident_kernel).
 // ------------------------------------------------------------------------------------------
 
-// v_min_f64 as the hardware has it (keys are never NaN): the builtin fmin costs a canonicalising v_max_f64 per operand
+// v_min_f64 as the hardware has it: the builtin fmin costs a canonicalising v_max_f64 per operand.  Keys are never NaN: the
+// candidate sites below test `ratio < INFINITY`, `ratio > -INFINITY`, `rc > best` (from best = precision) and `rhs < -precision`
+// first, all false for a NaN entry, a NaN ratio and a NaN precision; without a candidate the key is +inf (common.cuh, row16_min)
 __device__ __forceinline__ double min_f64_raw(double a, double b) {
     double r;
     asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
