@@ -1,6 +1,6 @@
 """ctypes binding of libyalps_hip.so (include/yalps_hip.h), libyalps_lpbatch.so (include/yalps_lpbatch.h),
-libyalps_milpbatch.so (include/yalps_milpbatch.h), libyalps_lpvar.so (include/yalps_lpvar.h) and libyalps_lpsens.so
-(include/yalps_lpsens.h).
+libyalps_milpbatch.so (include/yalps_milpbatch.h), libyalps_lpvar.so (include/yalps_lpvar.h), libyalps_lpsens.so
+(include/yalps_lpsens.h) and libyalps_milptree.so (include/yalps_milptree.h).
 
 There is no CPU path: if the library is missing, or no gfx950 device is usable,
 every call raises.  Nothing here imports the oracle.
@@ -64,6 +64,13 @@ SYMBOLS_LPWARM = (
     "yalps_lpwarm_solution", "yalps_lpwarm_tableau", "yalps_lpwarm_info",
 )
 LPWARM_MAX_BYTES = 4 << 20  # YALPS_LPWARM_MAX_BYTES
+# every symbol include/yalps_milptree.h declares (loaded on first use)
+MILPTREE_LIB_PATH = os.environ.get("YALPS_MILPTREE_LIB") or os.path.join(HERE, "libyalps_milptree.so")
+SYMBOLS_MILPTREE = (
+    "yalps_milptree_last_error", "yalps_milptree_create", "yalps_milptree_destroy", "yalps_milptree_solve", "yalps_milptree_validate",
+    "yalps_milptree_solution", "yalps_milptree_trace", "yalps_milptree_search", "yalps_milptree_info",
+)
+MILPTREE_MAX_BYTES = 4 << 20  # YALPS_MILPTREE_MAX_BYTES: a tree's largest possible node, root height + 2 * n_integers rows
 LPBATCH_HBM_CLASS = 4        # yalps_lpbatch_class: 0..3 the LDS form, 4 the HBM form
 
 
@@ -1194,3 +1201,171 @@ def milp_search(roots, evaluate, node_batch=8, consumed=None):
         out.append((STATUS[st[i]], float(res[i]), h, col0[c0_off[i]:c0_off[i] + h].copy(), pos[p_off[i]:p_off[i] + w + h].copy(),
                     var[p_off[i]:p_off[i] + w + h].copy(), int(stats[2 * i]), int(stats[2 * i + 1])))
     return out, rounds.value
+
+
+# ---------------------------------------------------------------------------------------------- libyalps_milptree.so
+
+_BATCH_LIBS["yalps_milptree"] = (MILPTREE_LIB_PATH, {
+        "solve": (_I32, [_VP, _I32] + [_VP] * 15 + [_I32, _VP, _VP, _VP, _VP]), "validate": (_I32, [_I32, _VP, _VP, _VP, _VP, _VP]),
+        "solution": (_I32, [_VP, _I32, C.POINTER(_I32), _VP, _VP, _VP]), "trace": (_I32, [_VP, _I32, C.POINTER(_I32)] + [_VP] * 8),
+        "search": (_I32, [_I32] + [_VP] * 14 + [_I32, _I32, MILP_EVAL_FN, MILP_CONSUMED_FN, _VP] + [_VP] * 8)})
+STATUS_MILPTREE = STATUS + ("overflow",)  # YALPS_MILPTREE_OVERFLOW: the tree's frontier outgrew the largest arena
+
+
+def milptree_lib():
+    return _load_lib("yalps_milptree")
+
+
+def milptree_check(rc):
+    return _check("yalps_milptree", rc)
+
+
+def milptree_validate(packed):
+    """The argument checks of yalps_milptree_solve on the integers, the node sizes and the timeouts, on the host."""
+    milptree_check(milptree_lib().yalps_milptree_validate(packed.count, packed.lps.width.ctypes.data, packed.lps.height.ctypes.data,
+                                                          packed.int_offsets.ctypes.data, packed.integers.ctypes.data,
+                                                          packed.timeout.ctypes.data))
+
+
+class MilpTree:
+    """Many independent MILPs per call, every branch-and-cut tree walked on the device (yalps_milptree_*): a root pass, then one
+    launch of milp_tree_kernel per (size class, checkCycles) pair.  Belongs to one thread at a time."""
+
+    def __init__(self, device=0, stream=None):
+        self.handle = C.c_void_p()
+        milptree_check(milptree_lib().yalps_milptree_create(device, C.c_void_p(stream) if stream is not None else None,
+                                                            C.byref(self.handle)))
+        self.packed, self.trace_cap = None, 0
+
+    def solve(self, milps, trace_cap=0):
+        """milps: a PackedMilps or the sequence it is made from.  Returns (status names -- "overflow" among them --, results,
+        nodes used, the sums of the nodes' pivots, {"reruns", "launches", "gpu_ms"})."""
+        p = milps if isinstance(milps, PackedMilps) else PackedMilps(milps)
+        n, lp = p.count, p.lps
+        st, res, stats, call = np.empty(n, np.int32), np.empty(n, np.float64), np.zeros(2 * n, np.int64), np.zeros(3, np.int64)
+        self.packed = None
+        milptree_check(milptree_lib().yalps_milptree_solve(
+            self.handle, n, lp.width.ctypes.data, lp.height.ctypes.data, lp.offsets.ctypes.data, lp.row.ctypes.data, lp.col.ctypes.data,
+            lp.val.ctypes.data, p.int_offsets.ctypes.data, p.integers.ctypes.data, p.sign.ctypes.data, lp.precision.ctypes.data,
+            lp.max_pivots.ctypes.data, lp.check_cycles.ctypes.data, p.tolerance.ctypes.data, p.timeout.ctypes.data,
+            p.max_iterations.ctypes.data, int(trace_cap), st.ctypes.data, res.ctypes.data, stats.ctypes.data, call.ctypes.data))
+        self.packed, self.trace_cap = p, int(trace_cap)
+        return ([STATUS_MILPTREE[k] for k in st], res, stats[0::2].copy(), stats[1::2].copy(),
+                {"reruns": int(call[0]), "launches": int(call[1]), "gpu_ms": call[2] / 1000.0})
+
+    def _model(self, i):
+        p = self.packed
+        if p is None or not 0 <= i < p.count:
+            raise NativeError("MilpTree: no such model in the last solve: %r" % (i,))
+        return int(p.lps.width[i]), int(p.lps.height[i]), int(p.n_integers[i])
+
+    def solution(self, i):
+        """(height, col0, positionOfVariable, variableAtPosition) of the best tableau of model i of the last solve."""
+        w, h0, ni = self._model(i)
+        cap = h0 + 2 * ni
+        col0, pos, var, h = np.empty(cap, np.float64), np.empty(w + cap, np.int32), np.empty(w + cap, np.int32), C.c_int32()
+        milptree_check(milptree_lib().yalps_milptree_solution(self.handle, i, C.byref(h), col0.ctypes.data, pos.ctypes.data,
+                                                              var.ctypes.data))
+        n = h.value
+        return n, col0[:n].copy(), pos[:w + n].copy(), var[:w + n].copy()
+
+    def trace(self, i):
+        """The first trace_cap nodes model i consumed, in pop order: [{"eval", "cuts": [(sign, variable, value)], "status",
+        "result", "n_pivots", "height"}]."""
+        w, h0, ni = self._model(i)
+        cap, room = self.trace_cap, max(1, self.trace_cap * 2 * ni)
+        ev, res = np.empty(cap, np.float64), np.empty(cap, np.float64)
+        st, hg, piv, cnt = np.empty(cap, np.int32), np.empty(cap, np.int32), np.empty(cap, np.int64), C.c_int32()
+        sg, vr, vl = np.empty(room, np.int32), np.empty(room, np.int32), np.empty(room, np.float64)
+        milptree_check(milptree_lib().yalps_milptree_trace(self.handle, i, C.byref(cnt), ev.ctypes.data, st.ctypes.data, res.ctypes.data,
+                                                           piv.ctypes.data, hg.ctypes.data, sg.ctypes.data, vr.ctypes.data, vl.ctypes.data))
+        out, c = [], 0
+        for k in range(cnt.value):
+            nc = int(hg[k]) - h0
+            out.append({"eval": float(ev[k]), "cuts": [(int(sg[c + q]), int(vr[c + q]), float(vl[c + q])) for q in range(nc)],
+                        "status": STATUS[st[k]], "result": float(res[k]), "n_pivots": int(piv[k]), "height": int(hg[k])})
+            c += nc
+        return out
+
+    def info(self):
+        """{"launches", "reruns", "overflows", "gpu_ms", "rerun_trees": [...], "kernels": [{kernel, class, trees | lps, grid, lds,
+        pass, hist_cap, arena}], "text"}"""
+        text = _info_text("yalps_milptree", self.handle, first=1 << 14)
+        head, kernels = _info_lines(text)
+        ids = [int(x) for x in head.get("rerun_trees", "[]").strip("[]").split(",") if x]
+        return {"launches": int(head.get("launches", 0)), "reruns": int(head.get("reruns", 0)), "overflows": int(head.get("overflows", 0)),
+                "gpu_ms": int(head.get("gpu_us", 0)) / 1000.0, "rerun_trees": ids, "kernels": kernels, "text": text}
+
+    def close(self):
+        if self.handle:
+            milptree_lib().yalps_milptree_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+
+def milp_tree_search(roots, evaluate, arena=None, consumed=None, arena_max=None):
+    """The search of yalps_milptree_solve -- the rules milp_tree_kernel runs -- on the host with `evaluate` as its node evaluator
+    (no device).  roots, evaluate and consumed as milp_search takes them (evaluate sees one node per call); arena: heap entries
+    of a tree's first arena (default 128), grown x 4 per rerun up to arena_max (default 65536), above which the tree's status is
+    "overflow".  Returns per model (status name, result, height, col0, pos, var, nodes used, nodes evaluated) and the number of
+    reruns."""
+    n = len(roots)
+    i32 = lambda it: np.ascontiguousarray(np.fromiter(it, np.int32, n))
+    f64 = lambda it: np.ascontiguousarray(np.fromiter((float(x) for x in it), np.float64, n))
+    width, height = i32(r[0] for r in roots), i32(r[1] for r in roots)
+    rstatus, rresult = i32(STATUS.index(r[2]) for r in roots), f64(r[3] for r in roots)
+    cat = lambda k, dt: np.ascontiguousarray(np.concatenate([np.asarray(r[k], dt) for r in roots]), dt) if n else np.zeros(0, dt)
+    rcol0, rpos, rvar = cat(4, np.float64), cat(5, np.int32), cat(6, np.int32)
+    nints = np.fromiter((len(r[7]) for r in roots), np.int64, n)
+    ioff = np.zeros(n + 1, np.int64)
+    ioff[1:] = np.cumsum(nints)
+    ints = cat(7, np.int32)
+    sign = f64(r[8] for r in roots)
+    prec, tol = f64(r[9]["precision"] for r in roots), f64(r[9]["tolerance"] for r in roots)
+    tmo, mit = f64(r[9]["timeout"] for r in roots), f64(r[9]["maxIterations"] for r in roots)
+    failure = []
+
+    def c_eval(user, count, model, off, sg, vr, vl, status, result, hout, col0, pos, var):
+        try:
+            m = model[0]
+            cuts = [(sg[c], vr[c], vl[c]) for c in range(off[0], off[1])]
+            (st, res, c0, p, v), = evaluate([(m, cuts)])
+            h, w = int(height[m]) + len(cuts), int(width[m])
+            status[0], result[0], hout[0] = STATUS.index(st), res, h
+            if st == "optimal":
+                hout[0] = len(c0)  # (a node of another height is refused by the search)
+                for j in range(min(h, len(c0))):
+                    col0[j] = c0[j]
+                for j in range(min(w + h, len(p), len(v))):
+                    pos[j], var[j] = p[j], v[j]
+            return 0
+        except BaseException as e:  # (no exception may cross the C frames)
+            failure.append(e)
+            return -1
+
+    def c_consumed(user, model, ev, ncuts, sg, vr, vl):
+        try:
+            consumed(model, ev, [(sg[c], vr[c], vl[c]) for c in range(ncuts)])
+        except BaseException as e:
+            failure.append(e)
+
+    caps = height.astype(np.int64) + 2 * nints
+    c0_off, p_off = np.concatenate([[0], np.cumsum(caps)]), np.concatenate([[0], np.cumsum(caps + width)])
+    st, res, hg = np.empty(n, np.int32), np.empty(n, np.float64), np.empty(n, np.int32)
+    col0, pos, var = np.zeros(int(c0_off[-1]), np.float64), np.zeros(int(p_off[-1]), np.int32), np.zeros(int(p_off[-1]), np.int32)
+    stats, reruns = np.zeros(2 * n, np.int64), C.c_int64()
+    first = 128 if arena is None else int(arena)
+    rc = milptree_lib().yalps_milptree_search(
+        n, width.ctypes.data, height.ctypes.data, rstatus.ctypes.data, rresult.ctypes.data, rcol0.ctypes.data, rpos.ctypes.data,
+        rvar.ctypes.data, ioff.ctypes.data, ints.ctypes.data, sign.ctypes.data, prec.ctypes.data, tol.ctypes.data, tmo.ctypes.data,
+        mit.ctypes.data, first, max(first, 65536) if arena_max is None else int(arena_max), MILP_EVAL_FN(c_eval),
+        MILP_CONSUMED_FN(c_consumed) if consumed else MILP_CONSUMED_FN(), None, st.ctypes.data, res.ctypes.data, hg.ctypes.data,
+        col0.ctypes.data, pos.ctypes.data, var.ctypes.data, stats.ctypes.data, C.addressof(reruns))
+    if failure:
+        raise failure[0]
+    milptree_check(rc)
+    out = []
+    for i in range(n):
+        h, w = int(hg[i]), int(width[i])
+        out.append((STATUS_MILPTREE[st[i]], float(res[i]), h, col0[c0_off[i]:c0_off[i] + h].copy(), pos[p_off[i]:p_off[i] + w + h].copy(),
+                    var[p_off[i]:p_off[i] + w + h].copy(), int(stats[2 * i]), int(stats[2 * i + 1])))
+    return out, reruns.value

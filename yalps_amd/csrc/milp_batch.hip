@@ -121,7 +121,7 @@ void tree_advance(Tree &t, int32_t index, yalps_milpbatch_consumed_fn consumed, 
         t.iter += 1.0;
     }
     if (t.finished) return;
-    const bool unfinished = (t.timedout || !(t.iter < t.max_iter)) && !t.branches.empty() && t.best_eval >= t.threshold; // :166-173
+    const bool unfinished = (t.timedout || t.iter >= t.max_iter) && !t.branches.empty() && t.best_eval >= t.threshold; // :166-173
     tree_finish(t, unfinished ? YALPS_MILPBATCH_TIMEDOUT : (t.found ? YALPS_OPTIMAL : YALPS_INFEASIBLE), t.found ? t.best_eval : NAN);
 }
 

@@ -260,7 +260,7 @@ extern "C" int32_t yalps_milp_f64(const double *matrix, int32_t width, int32_t h
         timedout = milp_now_ms() >= stop_time;
         iter += 1.0;
     }
-    const bool unfinished = (timedout || !(iter < maxIterations)) && !branches.empty() && best_eval >= optimal_threshold; // :166-173
+    const bool unfinished = (timedout || iter >= maxIterations) && !branches.empty() && best_eval >= optimal_threshold; // :166-173
     const int32_t status = unfinished ? 4 /* timedout */ : (solution_found ? YALPS_OPTIMAL : YALPS_INFEASIBLE);
     return finish(status, solution_found ? best_eval : NAN);
 }

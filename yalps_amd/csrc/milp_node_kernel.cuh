@@ -34,6 +34,7 @@ struct NodeLaunch : QueueLaunch {
 };
 
 // applyCuts (src/branchAndCut.ts:22-61): the root, one row per cut, permutations extended by identity
+// (milp_tree_kernel.cuh's tree_fill is a copy of fill() below with the cuts read from a slot: a change here goes there too)
 struct NodeJob : QueueJobBase {
     const NodeLaunch &L;
     const NodeDesc *d;

@@ -236,6 +236,39 @@ def milpbatch_solve(items, stats=None, node_batch=None):
     return out
 
 
+_milptree = None  # the process's MilpTree, kept like _lpbatch
+
+
+def milptree_solve(items, stats=None, fallback=None, make=None):
+    """The device-search MILP backend of solve_many(milp_search="device"): items = [(tabmod, options)] through ONE
+    yalps_milptree_solve -- a root pass, then every tree walked to its end by one workgroup (milp_tree_kernel), no rounds.
+    Returns what milpbatch_solve returns.  A tree whose frontier outgrew the largest arena comes back "overflow": those go
+    through `fallback` (milpbatch_solve) together and their answers are spliced in.  make: () -> the MilpTree to use (tests)."""
+    global _milptree
+    with _lpbatch_lock:
+        if make is not None:
+            batch = make()
+        else:
+            if _milptree is None:
+                _milptree = _native.MilpTree(0)
+            batch = _milptree
+        packed = _native.PackedMilps([(tm.tableau.width, tm.tableau.height, *tm.tableau.cells, tm.integers, tm.sign, o)
+                                      for tm, o in items])
+        statuses, results, used, _, call = batch.solve(packed)
+        out = [(s, float(r), *batch.solution(i)) for i, (s, r) in enumerate(zip(statuses, results))]
+        info = batch.info()
+    over = [i for i, s in enumerate(statuses) if s == "overflow"]
+    more = {}
+    if over:
+        for i, o in zip(over, (fallback or milpbatch_solve)([items[i] for i in over], more)):
+            out[i] = o
+    if stats is not None:
+        walked = sum(int(u) for s, u in zip(statuses, used) if s != "overflow")
+        stats.update(tree_launches=call["launches"], tree_reruns=info["reruns"], tree_overflows=len(over),
+                     nodes_used=walked + more.get("nodes_used", 0))
+    return out
+
+
 def milp_batchable(tabmod, opt):
     """A model with integers joins the MILP batch when its largest possible node (2 cuts per integer variable) is within
     4 MiB and its timeout is infinite or <= 0: a finite positive timeout keeps solve(), whose clock counts that model alone."""
@@ -293,7 +326,7 @@ def _solve_many_with(batch_simplex, solve_one, models, options=None, stats=None,
     return out
 
 
-def solve_many(models, options=None, stats=None):
+def solve_many(models, options=None, stats=None, milp_search="host"):
     """[solve(m, o) for m, o in zip(models, options)] -- same dicts, same order -- in at most two batched GPU calls plus
     solve() for what fits neither.  `options` is one dict for all models or one per model.
 
@@ -307,8 +340,16 @@ def solve_many(models, options=None, stats=None):
 
     stats (a dict, optional) receives how many models went which way ("batched" LPs, "milp" = every model with integers,
     "milp_batched" of them in the MILP batch, "large"), the LP batch's launches, and "node_rounds", "nodes_evaluated",
-    "nodes_used" of the MILP batch."""
-    return _solve_many_with(lpbatch_simplex, solve, models, options, stats, milpbatch_solve)
+    "nodes_used" of the MILP batch.
+
+    milp_search="device" sends the MILP batch through yalps_milptree_solve instead (milptree_solve: the search loop runs
+    inside the kernel, one workgroup per tree; same routing, same answers; stats then has "tree_launches", "tree_reruns",
+    "tree_overflows" and "nodes_used").  "host", the default, is the lockstep driver above."""
+    if milp_search == "host":
+        return _solve_many_with(lpbatch_simplex, solve, models, options, stats, milpbatch_solve)
+    if milp_search != "device":
+        raise ValueError("solve_many: milp_search must be \"host\" or \"device\", not %r" % (milp_search,))
+    return _solve_many_with(lpbatch_simplex, solve, models, options, stats, milptree_solve)
 
 
 _lpvariants = None  # the process's LpVariants, kept like _lpbatch
