@@ -1,0 +1,106 @@
+/*
+ * yalps_lpdense.h -- C ABI of libyalps_lpdense.so: a batch of dense LPs of one shape, read from and answered in DEVICE
+ * memory (MI355X, gfx950).
+ *
+ * yalps_lpbatch.h takes every LP as a packed cell list in host memory.  Here the `count` LPs of a call share one shape
+ * and lie in device memory as dense operands, scipy's linprog form with x >= 0:
+ *     maximize | minimize  c . x   subject to   A_ub x <= b_ub,   A_eq x = b_eq,   x >= 0
+ * with n variables, m_ub inequality rows and m_eq equality rows.  Every LP is assembled on the device into the tableau
+ * `tableauModel` builds for the equivalent model (reference src/tableau.ts:47-137; width n + 1, height 1 + m_ub + 2 m_eq:
+ * row 0 = +0.0, sign * c; then b_ub[i], A_ub[i, :]; then per equality b_eq[k], A_eq[k, :] and the row of their negations),
+ * solved by `simplex(tableau, options)` (src/simplex.ts:106-144), one workgroup per LP, and read out on the device as
+ * `solution()` reads it (src/YALPS.ts:8-50) into dense rows.  Values are taken as they lie in memory, NaN and infinities
+ * included.  Per call one int32 per LP crosses PCIe: the statuses the host needs to decide about a rerun.
+ *
+ * An operand is (device pointer, element strides): element (i, r, c) of a matrix operand at ptr[i * batch + r * row + c * col],
+ * element (i, r) of a vector operand at ptr[i * batch + r * row] (its col stride is ignored).  Strides are counted in
+ * doubles and are >= 0; batch = 0 shares one operand among all LPs of the call; any row / col stride is legal (transposed
+ * and sliced views); col = 1 is the fast case, read coalesced.
+ *
+ * Return protocol as yalps_hip.h: the YALPS_* codes below, negative = native failure with text through
+ * yalps_lpdense_last_error() (per thread).  There is NO CPU fallback: without a usable gfx950 device
+ * yalps_lpdense_create fails with YALPS_E_DEVICE.  A handle belongs to one thread at a time; its device buffers are
+ * kept and grown between calls.
+ *
+ * Pointers and streams belong to the HIP runtime that made them.  A process that holds two HIP runtimes (a framework
+ * that brings its own, loaded after this library) must hand over only what THIS library's runtime knows:
+ * yalps_lpdense_solve asks it about every operand and output pointer and refuses what it does not know.
+ */
+#ifndef YALPS_LPDENSE_H
+#define YALPS_LPDENSE_H
+
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#ifndef YALPS_OPTIMAL
+#define YALPS_OPTIMAL 0
+#define YALPS_INFEASIBLE 1
+#define YALPS_UNBOUNDED 2
+#define YALPS_CYCLED 3
+#define YALPS_E_ARG (-1)    /* bad argument */
+#define YALPS_E_DEVICE (-2) /* no usable HIP device / HIP runtime error */
+#define YALPS_E_NOMEM (-3)  /* device or host allocation failed */
+#endif
+
+#define YALPS_LPDENSE_MAX_BYTES (4 << 20) /* the largest tableau, 8 * (n + 1) * (1 + m_ub + 2 * m_eq) bytes */
+
+typedef struct yalps_lpdense yalps_lpdense;
+
+typedef struct yalps_lpdense_operand {
+    const double *ptr; /* device memory; NULL where the operand has no element */
+    int64_t batch, row, col;
+} yalps_lpdense_operand;
+
+const char *yalps_lpdense_last_error(void);
+
+/* hip_stream: NULL = a private stream; otherwise every kernel / copy is enqueued on the caller's HIP stream.  The device's
+ * default stream, whose handle is NULL, is named by hipStreamLegacy ((hipStream_t)1). */
+int32_t yalps_lpdense_create(int32_t device, void *hip_stream, yalps_lpdense **out);
+void yalps_lpdense_destroy(yalps_lpdense *d);
+
+/* Host only (no device needed, no pointer dereferenced): what yalps_lpdense_solve checks of the shape and the operands
+ * before it touches the device.  0, or YALPS_E_ARG with the reason in the error text: count < 0, a negative dimension, a
+ * tableau above YALPS_LPDENSE_MAX_BYTES, an operand descriptor that is NULL, a negative stride, a NULL pointer of an
+ * operand that has elements (count > 0 and: n > 0 for c; m_ub > 0 for b_ub, and n > 0 too for A_ub; likewise *_eq). */
+int32_t yalps_lpdense_validate(int32_t count, int32_t n, int32_t m_ub, int32_t m_eq, const yalps_lpdense_operand *c,
+                               const yalps_lpdense_operand *A_ub, const yalps_lpdense_operand *b_ub,
+                               const yalps_lpdense_operand *A_eq, const yalps_lpdense_operand *b_eq);
+
+/* Solves LPs 0 .. count-1.  maximize != 0: maximise c . x, else minimise.  precision / maxPivots (may be +Infinity) /
+ * checkCycles hold for the whole call.  keep_tableaux != 0 also keeps every final matrix on the device for
+ * yalps_lpdense_tableau.  All four outputs are DEVICE pointers, contiguous, and may be NULL:
+ *   x_out[count][n]       optimal: the variables' values, those above precision rounded to it, the others (a NaN too) +0.0;
+ *                         unbounded: +0.0 but +inf at the unbounded variable (where it is one of the n); else NaN
+ *   objective_out[count]  optimal: -sign * result; unbounded: sign * inf; else NaN       (sign = +1 maximise, -1 minimise)
+ *   status_out[count]     int32, YALPS_OPTIMAL .. YALPS_CYCLED
+ *   pivots_out[count]     int64
+ * They are complete when the call returns.  gpu_ms_out (host, optional) = HIP-event time of the kernels.
+ * count == 0 succeeds and launches nothing.  Before anything is enqueued every non-NULL operand and output pointer is
+ * looked up in this library's HIP runtime (hipPointerGetAttributes): host memory, memory of another device and a pointer
+ * the runtime does not know are refused with YALPS_E_ARG and a text that names the argument.  Returns 0 or a negative
+ * error; nothing is launched when an argument is refused. */
+int32_t yalps_lpdense_solve(yalps_lpdense *d, int32_t count, int32_t n, int32_t m_ub, int32_t m_eq,
+                            const yalps_lpdense_operand *c, const yalps_lpdense_operand *A_ub,
+                            const yalps_lpdense_operand *b_ub, const yalps_lpdense_operand *A_eq,
+                            const yalps_lpdense_operand *b_eq, int32_t maximize, double precision, double maxPivots,
+                            int32_t checkCycles, int32_t keep_tableaux, double *x_out, double *objective_out,
+                            int32_t *status_out, int64_t *pivots_out, float *gpu_ms_out);
+
+/* LP i of the last solve, copied to the HOST (for tests and debugging): what solution() reads -- column 0 (height
+ * doubles) and both permutations (width + height int32 each).  NULL pointers are skipped. */
+int32_t yalps_lpdense_solution(yalps_lpdense *d, int32_t i, double *col0, int32_t *positionOfVariable,
+                               int32_t *variableAtPosition);
+/* LP i of the last solve: the whole final matrix, row-major width * height, to the host.  Needs keep_tableaux. */
+int32_t yalps_lpdense_tableau(yalps_lpdense *d, int32_t i, double *matrix);
+/* Text about the last solve: launches made, per launch the kernel's spelling, its size class, LP count, grid and LDS
+ * bytes, and the LPs rerun because their checkCycles history overflowed.  Writes at most len - 1 characters and returns the
+ * length of the whole text: a return value >= len means the text was cut (call again with a larger buffer). */
+int32_t yalps_lpdense_info(const yalps_lpdense *d, char *buf, int32_t len);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* YALPS_LPDENSE_H */

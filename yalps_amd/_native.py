@@ -1,6 +1,6 @@
 """ctypes binding of libyalps_hip.so (include/yalps_hip.h), libyalps_lpbatch.so (include/yalps_lpbatch.h),
 libyalps_milpbatch.so (include/yalps_milpbatch.h), libyalps_lpvar.so (include/yalps_lpvar.h), libyalps_lpsens.so
-(include/yalps_lpsens.h) and libyalps_milptree.so (include/yalps_milptree.h).
+(include/yalps_lpsens.h), libyalps_milptree.so (include/yalps_milptree.h) and libyalps_lpdense.so (include/yalps_lpdense.h).
 
 There is no CPU path: if the library is missing, or no gfx950 device is usable,
 every call raises.  Nothing here imports the oracle.
@@ -71,6 +71,13 @@ SYMBOLS_MILPTREE = (
     "yalps_milptree_solution", "yalps_milptree_trace", "yalps_milptree_search", "yalps_milptree_info",
 )
 MILPTREE_MAX_BYTES = 4 << 20  # YALPS_MILPTREE_MAX_BYTES: a tree's largest possible node, root height + 2 * n_integers rows
+# every symbol include/yalps_lpdense.h declares (loaded on first use)
+LPDENSE_LIB_PATH = os.environ.get("YALPS_LPDENSE_LIB") or os.path.join(HERE, "libyalps_lpdense.so")
+SYMBOLS_LPDENSE = (
+    "yalps_lpdense_last_error", "yalps_lpdense_create", "yalps_lpdense_destroy", "yalps_lpdense_validate", "yalps_lpdense_solve",
+    "yalps_lpdense_solution", "yalps_lpdense_tableau", "yalps_lpdense_info",
+)
+LPDENSE_MAX_BYTES = 4 << 20  # YALPS_LPDENSE_MAX_BYTES
 LPBATCH_HBM_CLASS = 4        # yalps_lpbatch_class: 0..3 the LDS form, 4 the HBM form
 
 
@@ -943,6 +950,96 @@ class LpWarm:
     def close(self):
         if self.handle:
             lpwarm_lib().yalps_lpwarm_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+
+# ---------------------------------------------------------------------------------------------- libyalps_lpdense.so
+
+class DenseOperand(C.Structure):
+    """yalps_lpdense_operand: a device pointer and its element strides (batch, row, col), counted in doubles."""
+    _fields_ = [("ptr", C.c_void_p), ("batch", C.c_int64), ("row", C.c_int64), ("col", C.c_int64)]
+
+
+_DOP = C.POINTER(DenseOperand)
+_BATCH_LIBS["yalps_lpdense"] = (LPDENSE_LIB_PATH, {
+        "validate": (_I32, [_I32, _I32, _I32, _I32, _DOP, _DOP, _DOP, _DOP, _DOP]),
+        "solve": (_I32, [_VP, _I32, _I32, _I32, _I32, _DOP, _DOP, _DOP, _DOP, _DOP, _I32, C.c_double, C.c_double, _I32, _I32,
+                         _VP, _VP, _VP, _VP, C.POINTER(C.c_float)]),
+        "solution": (_I32, [_VP, _I32, _VP, _VP, _VP]), "tableau": (_I32, [_VP, _I32, _VP])})
+
+
+def lpdense_lib():
+    return _load_lib("yalps_lpdense")
+
+
+def lpdense_check(rc):
+    return _check("yalps_lpdense", rc)
+
+
+def _dense_operands(operands):
+    """Five (ptr, batch, row, col) tuples (None: an operand without elements) as yalps_lpdense_operand structs."""
+    assert len(operands) == 5
+    return [DenseOperand(*(o if o is not None else (None, 0, 0, 0))) for o in operands]
+
+
+def lpdense_validate(count, n, m_ub, m_eq, operands):
+    """The host-only argument checks of yalps_lpdense_solve (raises NativeError with the reason); operands = (c, A_ub, b_ub,
+    A_eq, b_eq), each (ptr, batch, row, col) or None.  No pointer is dereferenced."""
+    ops = _dense_operands(operands)
+    lpdense_check(lpdense_lib().yalps_lpdense_validate(int(count), int(n), int(m_ub), int(m_eq), *(C.byref(o) for o in ops)))
+
+
+class LpDense:
+    """Batches of dense LPs of one shape, operands and answers in device memory (yalps_lpdense_*).  Pointers are plain
+    integers (a tensor's data_ptr()); nothing here imports torch.  Belongs to one thread at a time."""
+
+    def __init__(self, device=0, stream=None):
+        self.handle = C.c_void_p()
+        lpdense_check(lpdense_lib().yalps_lpdense_create(device, C.c_void_p(stream) if stream is not None else None,
+                                                         C.byref(self.handle)))
+        self.shape = None  # (count, width, height) of the last solve
+
+    def solve(self, count, n, m_ub, m_eq, operands, maximize=False, precision=1e-8, max_pivots=8192.0, check_cycles=False,
+              keep_tableaux=False, x=None, objective=None, status=None, pivots=None):
+        """operands = (c, A_ub, b_ub, A_eq, b_eq), each (device pointer, batch, row, col strides in doubles) or None where it
+        has no element; x / objective / status / pivots: device pointers of contiguous float64 [count][n], float64 [count],
+        int32 [count], int64 [count], or None.  The outputs are complete on return.  Returns gpu_ms."""
+        ops = _dense_operands(operands)
+        ms = C.c_float()
+        self.shape = None
+        lpdense_check(lpdense_lib().yalps_lpdense_solve(
+            self.handle, int(count), int(n), int(m_ub), int(m_eq), *(C.byref(o) for o in ops), int(bool(maximize)), float(precision),
+            float(max_pivots), int(bool(check_cycles)), int(bool(keep_tableaux)), x, objective, status, pivots, C.byref(ms)))
+        self.shape = (int(count), int(n) + 1, 1 + int(m_ub) + 2 * int(m_eq))
+        return ms.value
+
+    def _check(self, i):
+        if self.shape is None or not 0 <= i < self.shape[0]:
+            raise NativeError("LpDense: no such LP in the last solve: %r" % (i,))
+        return self.shape[1], self.shape[2]
+
+    def solution(self, i):
+        """(col0, positionOfVariable, variableAtPosition) of LP i of the last solve, copied to the host."""
+        w, h = self._check(i)
+        col0 = np.empty(h, np.float64)
+        pos, var = np.empty(w + h, np.int32), np.empty(w + h, np.int32)
+        lpdense_check(lpdense_lib().yalps_lpdense_solution(self.handle, i, col0.ctypes.data, pos.ctypes.data, var.ctypes.data))
+        return col0, pos, var
+
+    def tableau(self, i):
+        """The whole final matrix of LP i of the last solve (solve(..., keep_tableaux=True)), flat row-major, on the host."""
+        w, h = self._check(i)
+        m = np.empty(w * h, np.float64)
+        lpdense_check(lpdense_lib().yalps_lpdense_tableau(self.handle, i, m.ctypes.data))
+        return m
+
+    def info(self):
+        """{"launches", "reruns", "rerun_lps": [...], "kernels": [{kernel, class, aux, lps, grid, lds, pass, hist_cap}], "text"}"""
+        return _batch_info(_info_text("yalps_lpdense", self.handle))
+
+    def close(self):
+        if self.handle:
+            lpdense_lib().yalps_lpdense_destroy(self.handle)
             self.handle = C.c_void_p()
 
 

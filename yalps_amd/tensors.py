@@ -1,0 +1,143 @@
+"""linprog_batch: batches of small dense LPs straight from torch tensors on the GPU (libyalps_lpdense.so).
+
+This module imports torch; `import yalps_amd` does not.  Nothing here computes with torch: it supplies the device pointers,
+the strides and the stream, and allocates the outputs.
+
+Loading rule: torch brings its own HIP runtime, and a pointer or a stream is only good in the runtime that made it.  torch
+must be initialised in the process before the first call into ANY of this package's libraries (solve, solve_many, _native
+...): then they all resolve to the runtime torch loaded.  In the other order the library's runtime does not know torch's
+memory, and linprog_batch refuses the call with a message that says so instead of handing the kernel a foreign pointer.
+"""
+import atexit
+import threading
+from collections import namedtuple
+
+import torch
+
+from . import _native
+
+LinprogBatch = namedtuple("LinprogBatch", ("x", "objective", "status", "pivots"))
+
+STATUS_NAMES = _native.STATUS[:4]  # the YALPS_* codes 0..3 as solve() spells them
+
+_handles = {}  # (device index, stream) -> LpDense: stream, events and device buffers are kept and grown between calls
+_lock = threading.Lock()  # (a handle belongs to one thread at a time)
+
+
+def status_names(status):
+    """The strings solve() uses -- "optimal", "infeasible", "unbounded", "cycled" -- for a status tensor (or any iterable
+    of the codes)."""
+    codes = status.tolist() if hasattr(status, "tolist") else list(status)
+    return [STATUS_NAMES[int(k)] for k in codes]
+
+
+@atexit.register
+def _close_handles():
+    with _lock:
+        for h in _handles.values():
+            h.close()
+        _handles.clear()
+
+
+def _operand(name, t, ndim):
+    """A float64 tensor of `ndim` dimensions or one more (the batch in front): (tensor, B or None, its own shape)."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("linprog_batch: %s must be a torch.Tensor, not %s" % (name, type(t).__name__))
+    if t.dtype != torch.float64:
+        raise TypeError("linprog_batch: %s is %s; only torch.float64 is solved" % (name, t.dtype))
+    if t.dim() not in (ndim, ndim + 1):
+        raise ValueError("linprog_batch: %s has %d dimensions, expected %d or %d (with the batch in front)" % (name, t.dim(), ndim, ndim + 1))
+    batched = t.dim() == ndim + 1
+    return t, (t.shape[0] if batched else None), tuple(t.shape[1:] if batched else t.shape)
+
+
+def _strides(t, batched, matrix):
+    """(ptr, batch, row, col) of yalps_lpdense_operand, in elements; None where the tensor has no element."""
+    if t is None or t.numel() == 0:
+        return None
+    s = t.stride()
+    return (t.data_ptr(), s[0] if batched else 0, s[-2] if matrix else s[-1], s[-1] if matrix else 0)
+
+
+def linprog_batch(c, A_ub=None, b_ub=None, A_eq=None, b_eq=None, *, maximize=False, precision=1e-8, max_pivots=8192,
+                  check_cycles=False, stats=None):
+    """Solves B dense LPs of one shape in one call, from device tensors to device tensors:
+
+        minimize (or maximize=True: maximize)  c . x   subject to   A_ub x <= b_ub,   A_eq x = b_eq,   x >= 0
+
+    c is [B, n] or [n]; A_ub / A_eq are [B, m, n] or [m, n]; b_ub / b_eq are [B, m] or [m]; all torch.float64 on one GPU.
+    B is taken from whichever operand has the batch dimension (they must agree); with none, B = 1.  An operand without it
+    is shared by all LPs: it is read with a batch stride of 0, nothing is materialised, and no operand is made contiguous
+    -- transposed, sliced and expanded views are read through their strides (a last-dimension stride of 1 reads fastest).
+    precision, max_pivots (may be inf) and check_cycles are the reference's options, for the whole call.
+
+    Returns LinprogBatch(x [B, n] float64, objective [B] float64, status [B] int32, pivots [B] int64) on the inputs'
+    device; status_names(status) spells the codes as solve() does.  The work is enqueued on torch's current stream of that
+    device and the call returns after its one wait: the outputs are ready on return, and the inputs need only live as long
+    as the call.  One int32 per LP crosses PCIe.
+
+    The contract.  For finite data, row i is what solve() returns for the equivalent model -- constraints u0.. {"max":
+    b_ub[i, r]}, then e0.. {"equal": b_eq[i, k]}, every variable listing every coefficient, zeros included -- with
+    includeZeroVariables read off the dense x: "optimal" gives the variables' values (those not above precision are +0.0)
+    and objective = solve()'s result; "unbounded" gives +0.0 but +inf at the unbounded variable and objective = +-inf;
+    "infeasible" and "cycled" give NaN everywhere.  For any data, NaN and infinities included, it is what the reference's
+    `simplex` and `solution` give on the tableau as built: values are taken as they lie in memory.
+
+    Raises TypeError / ValueError, before the library is touched, for anything but float64 tensors, mismatched B, m or n,
+    a tableau (n + 1) x (1 + m_ub + 2 m_eq) above 4 MiB (solve() is the route for such models), CPU tensors and tensors on
+    different devices.  stats (a dict, optional) receives "launches", "reruns", "kernels" and "gpu_ms" of the call.
+
+    See the module's docstring for the loading rule: torch first."""
+    c, cB, (n,) = _operand("c", c, 1)
+    batch = {"c": cB}
+    sides = []
+    for tag, A, b in (("ub", A_ub, b_ub), ("eq", A_eq, b_eq)):
+        if (A is None) != (b is None):
+            raise ValueError("linprog_batch: A_%s and b_%s come together" % (tag, tag))
+        if A is None:
+            sides.append((None, None, 0))
+            continue
+        A, batch["A_" + tag], (m, An) = _operand("A_" + tag, A, 2)
+        b, batch["b_" + tag], (bm,) = _operand("b_" + tag, b, 1)
+        if An != n:
+            raise ValueError("linprog_batch: A_%s has %d columns, c has %d variables" % (tag, An, n))
+        if bm != m:
+            raise ValueError("linprog_batch: A_%s has %d rows, b_%s has %d" % (tag, m, tag, bm))
+        sides.append((A, b, m))
+    sizes = {k: v for k, v in batch.items() if v is not None}
+    if len(set(sizes.values())) > 1:
+        raise ValueError("linprog_batch: the operands disagree about B: %s" % ", ".join("%s has %d" % kv for kv in sizes.items()))
+    B = next(iter(sizes.values()), 1)
+    (A_ub, b_ub, m_ub), (A_eq, b_eq, m_eq) = sides
+    w, h = n + 1, 1 + m_ub + 2 * m_eq
+    if 8 * w * h > _native.LPDENSE_MAX_BYTES:
+        raise ValueError("linprog_batch: a tableau of %d x %d doubles (%d bytes) is above the batch limit of %d bytes; "
+                         "solve() is the route for such models" % (h, w, 8 * w * h, _native.LPDENSE_MAX_BYTES))
+    tensors = [t for t in (c, A_ub, b_ub, A_eq, b_eq) if t is not None]
+    if any(not t.is_cuda for t in tensors):
+        raise ValueError("linprog_batch: the operands are read on the GPU where they lie: a CPU tensor was given "
+                         "(move it with .cuda(), or use solve_many for models in host memory)")
+    device = c.device
+    if any(t.device != device for t in tensors):
+        raise ValueError("linprog_batch: the operands lie on different devices: %s" % sorted({str(t.device) for t in tensors}))
+
+    operands = (_strides(c, batch["c"] is not None, False),
+                _strides(A_ub, batch.get("A_ub") is not None, True), _strides(b_ub, batch.get("b_ub") is not None, False),
+                _strides(A_eq, batch.get("A_eq") is not None, True), _strides(b_eq, batch.get("b_eq") is not None, False))
+    x = torch.empty((B, n), dtype=torch.float64, device=device)
+    objective = torch.empty((B,), dtype=torch.float64, device=device)
+    status = torch.empty((B,), dtype=torch.int32, device=device)
+    pivots = torch.empty((B,), dtype=torch.int64, device=device)
+    ptr = lambda t: t.data_ptr() if t.numel() else None
+    with torch.cuda.device(device), _lock:  # (the library selects the handle's device; torch's choice comes back afterwards)
+        stream = torch.cuda.current_stream(device).cuda_stream or 1  # (the default stream's handle is 0: hipStreamLegacy names it)
+        key = (device.index, stream)
+        handle = _handles.get(key)
+        if handle is None:
+            handle = _handles[key] = _native.LpDense(device.index, stream=stream)
+        ms = handle.solve(B, n, m_ub, m_eq, operands, maximize=maximize, precision=precision, max_pivots=max_pivots,
+                          check_cycles=check_cycles, x=ptr(x), objective=ptr(objective), status=ptr(status), pivots=ptr(pivots))
+        if stats is not None:
+            info = handle.info()
+            stats.update(launches=info["launches"], reruns=info["reruns"], kernels=info["kernels"], gpu_ms=ms)
+    return LinprogBatch(x, objective, status, pivots)
