@@ -64,11 +64,12 @@ int32_t yalps_oracle_set_threads(int32_t n) {
 }
 #endif
 
-/* JS Math.round: nearest integer, halves toward +infinity (src/util.ts:2-3). */
+/* JS Math.round: nearest integer, halves toward +infinity, a zero with the sign of x: -0 on [-0.5, -0] (src/util.ts:2-3). */
 static double js_round(double x) {
     if (!(x == x) || isinf(x)) return x;
     double f = floor(x);
-    return (x - f >= 0.5) ? f + 1.0 : f;
+    double r = (x - f >= 0.5) ? f + 1.0 : f;
+    return r == 0.0 ? copysign(0.0, x) : r;
 }
 
 /* src/util.ts:1-4 */

@@ -16,6 +16,7 @@ of branchAndCut.ts pointed at a stand-in module the caller writes (./heap.mjs), 
 trace hooks in branchAndCut() and solve() that only read: the popped node, the
 node's tableau before and after simplex(), the loop's final state, the root solve
 and the tableau handed to solution().  A hook is called only where the caller set it.
+solution() of YALPS.ts is exported as well (gen_golden.py --only rounding calls it on hand-built final states).
 """
 import os
 import re
@@ -138,7 +139,7 @@ YALPS_EDITS = [
     ("const solution = <VarKey, ConKey>(\n  { tableau, sign, variables: vars }: TableauModel<VarKey, ConKey>,\n"
      "  status: SolutionStatus,\n  result: number,\n  { precision, includeZeroVariables }: Required<Options>,\n"
      "): Solution<VarKey> => {\n",
-     "const solution = (\n  { tableau, sign, variables: vars },\n  status,\n  result,\n  { precision, includeZeroVariables },\n) => {\n"
+     "export const solution = (\n  { tableau, sign, variables: vars },\n  status,\n  result,\n  { precision, includeZeroVariables },\n) => {\n"
      "  if (globalThis.__yalps_solve) globalThis.__yalps_solve.solution(tableau, status, result)\n"),
     ("const variables: [VarKey, number][] = []", "const variables = []"),
     ("const defaultOptionValues: Required<Options> = {", "const defaultOptionValues = {"),

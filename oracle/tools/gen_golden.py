@@ -14,6 +14,11 @@ TEST-FIXTURE TOOLING, build container only (needs /root/reference and node).
      infinite entries and options), final state recorded with every NaN word
      replaced by 0x7ff8000000000000 (V8 and a GPU give arithmetic NaNs
      different sign bits),
+     (g) `--only rounding`: roundToPrecision (util.ts) on the table of
+     tests/_rounding.py and solution() (YALPS.ts) on its hand-built final
+     states, every float as its 64-bit word in hex (a JSON number drops the
+     sign of a zero), and `--only rounding_edges`: the family R of the same
+     module through simplex(), `result_hex` beside `result`,
      (e) `--only milp`: the MILP models of tests/_milps.py through the
      reference's solve() (YALPS.ts, branchAndCut.ts on the heap stand-in
      below), recording every popped node, the exit and the Solution,
@@ -44,13 +49,17 @@ from erase_types import erase  # noqa: E402
 DRIVER = r"""
 import { simplex } from "./simplex.mjs"
 import { tableauModel } from "./tableau.mjs"
-import { solve } from "./YALPS.mjs"
+import { solve, solution } from "./YALPS.mjs"
+import { roundToPrecision } from "./util.mjs"
 import * as fs from "fs"
 import * as crypto from "crypto"
 
 const b64 = (ta) => Buffer.from(ta.buffer, ta.byteOffset, ta.byteLength).toString("base64")
 const sha = (ta) => crypto.createHash("sha256").update(Buffer.from(ta.buffer, ta.byteOffset, ta.byteLength)).digest("hex")
 const num = (x) => (Number.isFinite(x) ? x : String(x))
+// a double as its 64-bit word in hex, all NaNs one value; and back
+const hexw = (x) => { if (x !== x) return "7ff8000000000000"; const b = Buffer.alloc(8); b.writeDoubleBE(x, 0); return b.toString("hex") }
+const unhex = (s) => Buffer.from(s, "hex").readDoubleBE(0)
 
 // the reference test-suite's PRNG (tests/helpers/util.ts:20-41), restated
 const hash32 = (n) => { let x = n; x ^= x >>> 16; x = Math.imul(x, 0x21f0aaad); x ^= x >>> 15; x = Math.imul(x, 0xd35a2d97); x ^= x >>> 15; return x }
@@ -80,6 +89,7 @@ const run = (rec, tableau, options, storeInit, canon) => {
   const [status, result] = simplex(tableau, options)
   rec.wall_ms = Date.now() - t0
   rec.status = status; rec.result = num(result)
+  if (rec.kind === "rounding_edges") rec.result_hex = hexw(result)  // (a JSON number cannot hold the sign of a zero)
   rec.n_pivots = globalThis.__yalps_trace.length / 2
   rec.pivots = b64(Int32Array.from(globalThis.__yalps_trace))
   rec.pos = b64(tableau.positionOfVariable); rec.var = b64(tableau.variableAtPosition)
@@ -207,6 +217,34 @@ if (mode === "cases") {
     run({ kind: "edges", family: spec.family, M: spec.M, N: spec.N, seed: spec.seed, layout: spec.layout },
         { matrix, width: w, height: h, positionOfVariable: pos, variableAtPosition: vr }, opts, w * h <= 20000)
   }
+} else if (mode === "rounding") {
+  // tests/_rounding.py: argv[3] holds {table: [{precision, nums}], states: [...]}, every float as its 64-bit word in hex
+  const spec = JSON.parse(fs.readFileSync(process.argv[3], "utf-8"))
+  for (const row of spec.table) {
+    const p = unhex(row.precision)
+    console.log(JSON.stringify({ kind: "round", precision: row.precision, nums: row.nums, outs: row.nums.map((h) => hexw(roundToPrecision(unhex(h), p))) }))
+  }
+  for (const s of spec.states) {
+    const w = spec.n + 1, h = 1 + spec.m_ub + 2 * spec.m_eq
+    const matrix = new Float64Array(w * h)
+    s.col0.forEach((x, r) => { matrix[r * w] = unhex(x) })
+    const tableau = { matrix, width: w, height: h, positionOfVariable: Int32Array.from(s.pos), variableAtPosition: Int32Array.from(s.var) }
+    const vars = []
+    for (let j = 0; j < spec.n; j++) vars.push([j, []])
+    const sol = solution({ tableau, sign: s.sign, variables: vars }, s.status, unhex(s.result), { precision: unhex(s.precision), includeZeroVariables: true })
+    console.log(JSON.stringify(Object.assign({ kind: "solution" }, s, { out: { status: sol.status, result: hexw(sol.result), variables: sol.variables.map(([k, v]) => [k, hexw(v)]) } })))
+  }
+} else if (mode === "rounding_edges") {
+  // the family R of tests/_rounding.py (final roundings that end at -0 or NaN), as raw float64 files like "edges"
+  for (const spec of JSON.parse(fs.readFileSync(process.argv[3], "utf-8"))) {
+    const buf = fs.readFileSync(spec.file)
+    const matrix = new Float64Array(buf.buffer.slice(buf.byteOffset, buf.byteOffset + buf.length))
+    const w = spec.N + 1, h = spec.M + 1
+    const [pos, vr] = identityPerms(w + h)
+    const opts = { precision: spec.precision, maxPivots: spec.maxPivots, checkCycles: spec.checkCycles }
+    run({ kind: "rounding_edges", family: spec.family, M: spec.M, N: spec.N, seed: spec.seed, layout: spec.layout },
+        { matrix, width: w, height: h, positionOfVariable: pos, variableAtPosition: vr }, opts, false)
+  }
 } else if (mode === "nonfinite") {
   // tableaux of tests/_nonfinite.py, as raw float64 files; precision and maxPivots travel as strings (JSON has no NaN)
   for (const spec of JSON.parse(fs.readFileSync(process.argv[3], "utf-8"))) {
@@ -332,6 +370,44 @@ def nonfinite_records(erased, tmp):
     return recs
 
 
+def rounding_spec(tmp):
+    """The table and the states of tests/_rounding.py, as the driver's "rounding" mode reads them."""
+    sys.path.insert(0, REPO)
+    from tests import _rounding as RD
+    spec = dict(n=RD.N, m_ub=RD.M_UB, m_eq=RD.M_EQ,
+                table=[dict(precision=RD.hexd(p), nums=[RD.hexd(x) for x in nums]) for p, nums in RD.table()],
+                states=[RD.state_spec(s) for s in RD.states()])
+    with open(os.path.join(tmp, "rounding.json"), "w") as f:
+        json.dump(spec, f)
+    return os.path.join(tmp, "rounding.json")
+
+
+def rounding_edge_records(erased, tmp):
+    """The records of the family R of tests/_rounding.py, one shape at a time like nonfinite_records."""
+    sys.path.insert(0, REPO)
+    from tests import _edges as E
+    from tests import _rounding as RD
+    recs = []
+    for shape in E.SHAPES:
+        specs, files = [], []
+        for family, M, N, seed in RD.r_specs():
+            if (M, N) != shape:
+                continue
+            layout = E.default_layout(M, N)
+            path = os.path.join(tmp, "rounding_%04d.f64" % len(files))
+            RD.r_make(family, M, N, seed, layout).tofile(path)
+            files.append(path)
+            o = RD.r_options(family, M, N, seed)
+            specs.append(dict(file=path, family=family, M=M, N=N, seed=seed, layout=[list(layout[0]), list(layout[1])],
+                              precision=o["precision"], maxPivots=o["max_pivots"], checkCycles=o["check_cycles"]))
+        with open(os.path.join(tmp, "rounding_edges.json"), "w") as f:
+            json.dump(specs, f)
+        recs += run_driver(erased, "rounding_edges", os.path.join(tmp, "rounding_edges.json"))
+        for path in files:
+            os.remove(path)
+    return recs
+
+
 def milp_specs(tmp):
     """The models of tests/_milps.py with their options, as the driver's "milp" mode reads them."""
     sys.path.insert(0, REPO)
@@ -378,19 +454,25 @@ def main():
     os.makedirs(os.path.join(golden, "cases"), exist_ok=True)
 
     tmp = tempfile.mkdtemp(prefix="yalps_edges_")
-    for mode, extra in (("cases", ()), ("mixed", ()), ("dense", (args.max_dense,)), ("edges", ()), ("milp", ()), ("nonfinite", ())):
+    for mode, extra in (("cases", ()), ("mixed", ()), ("dense", (args.max_dense,)), ("edges", ()), ("milp", ()), ("nonfinite", ()),
+                        ("rounding", ()), ("rounding_edges", ())):
         if mode not in args.only:
             continue
         t0 = time.time()
-        specs = {"edges": edge_specs, "milp": milp_specs}.get(mode)
+        specs = {"edges": edge_specs, "milp": milp_specs, "rounding": rounding_spec}.get(mode)
         if mode == "nonfinite":
             recs = nonfinite_records(erased, tmp)
+        elif mode == "rounding_edges":
+            recs = rounding_edge_records(erased, tmp)
         else:
             recs = run_driver(erased, mode, *(extra if specs is None else (specs(tmp),)))
-        if mode in ("edges", "nonfinite"):
+        if mode in ("edges", "nonfinite", "rounding_edges"):
             recs = [compact(r) for r in recs]
+        if mode == "rounding_edges":
+            for r in recs:
+                del r["wall_ms"]
         path = os.path.join(golden, f"simplex_{mode}.json.gz")
-        src = "YALPS.ts, branchAndCut.ts on the heap stand-in of gen_golden.py" if mode == "milp" else "simplex.ts"
+        src = {"milp": "YALPS.ts, branchAndCut.ts on the heap stand-in of gen_golden.py", "rounding": "util.ts, YALPS.ts"}.get(mode, "simplex.ts")
         node = subprocess.run(["node", "--version"], capture_output=True, text=True).stdout.strip()
         with gzip.GzipFile(path, "wb", mtime=0) as gz:
             gz.write(json.dumps({"generator": "oracle/tools/gen_golden.py",

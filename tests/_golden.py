@@ -94,4 +94,13 @@ def identity_perms(rec):
 
 
 def same_number(a, b):
+    """Equal as numbers: -0.0 and +0.0 are the same here.  The golden files written before simplex_rounding.json.gz hold
+    `result` as a JSON number, and JSON.stringify(-0) is "0": they cannot say which zero the reference produced, so a
+    comparison with them cannot ask for one.  The sign of a rounded zero is pinned by tests/golden/simplex_rounding.json.gz
+    and simplex_rounding_edges.json.gz (tests/_rounding.py), whose floats are 64-bit words in hex: compare with same_bits."""
     return (a != a and b != b) or a == b
+
+
+def same_bits(a, b):
+    """Equal word for word, all NaNs one value: tells -0.0 from +0.0."""
+    return canon(np.array([a], np.float64)).tobytes() == canon(np.array([b], np.float64)).tobytes()

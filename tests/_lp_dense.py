@@ -23,6 +23,7 @@ from tests import _edges as E
 from tests import _lp_batch as LB
 from tests import _nonfinite as NF
 from tests import _np_dense as ND
+from tests import _rounding as RD
 
 INF = math.inf
 STATUS = ("optimal", "infeasible", "unbounded", "cycled")
@@ -112,6 +113,71 @@ def nonfinite_families(oracle):
     return out
 
 
+N7_SEEDS = tuple(range(NF.SEED, NF.SEED + 10))  # the ten variants of N7: options that are not finite, on finite tableaux
+PRECISION_SHAPES = ((65, 65), (257, 16), (1025, 64))  # (n, m_ub) of the precision calls: 256 lanes in LDS twice, 1024 lanes in HBM
+
+
+def precision_names():
+    return ["precision %r n=%d" % (p, n) for n, _ in PRECISION_SHAPES for p in RD.PRECISIONS]
+
+
+def precision_lp(n, m, p):
+    """maximize 5 (x_k1 + .. + x_km) + 0 x_free - (the others), 4 x_ki <= b_i: every bounded variable ends basic at b_i / 4
+    (exact: a power of two), x_free and the others stay out of the basis.  b / 4 holds `precision`, its two neighbours, the
+    ties (j + 0.5) * precision, the ends of the -0 window of its rounding and 1e300, in turn; where the precision is not
+    positive and finite they are built around 1e-8.  The bounded variables are spread over 0 .. n - 1, both ends among them."""
+    q = p if 0.0 < p < math.inf else 1e-8
+    edges = [q, math.nextafter(q, math.inf), math.nextafter(q, 0.0)] + [(j + 0.5) * q for j in range(6)]
+    edges += [max(1.5 * q - RD.EPS, 0.0), math.nextafter(1.5 * q, math.inf), 1e300, 0.375, 3.0, 2.0 ** 53 * q, 0.49999999999999994 * q + q]
+    cols = sorted({(i * (n - 1)) // (m - 1) for i in range(m)}) if m < n else list(range(n))
+    free = next(j for j in range(n - 2, -1, -1) if j not in cols) if m < n else None
+    c = np.full(n, -1.0)
+    c[cols] = 5.0
+    A = np.zeros((len(cols), n))
+    b = np.zeros(len(cols))
+    for i, j in enumerate(cols):
+        A[i, j] = 4.0
+        b[i] = 4.0 * edges[i % len(edges)]
+    if free is not None:
+        c[free] = 0.0
+    else:  # (m = n: one variable is given up as the free one; its row bounds nothing)
+        free = n - 2
+        c[free], A[free, free] = 0.0, 0.0
+    return c, A, b, None, None
+
+
+def precision_call(n, m, p):
+    return Call("precision %r n=%d" % (p, n), [precision_lp(n, m, p)], maximize=True, precision=p)
+
+
+def ending_calls():
+    """Endings of `after` no other call reaches by design: a negative precision on an LP that ends optimal (reduced costs of -2
+    and right-hand sides of 1 and more, so that neither `> precision` nor `< -precision` starts anything) with variables out of
+    the basis: their 0.0 passes `value > precision` and is rounded, by the reference to +0.0; "unbounded" at the last of n
+    variables (n - 1 = 1024: the lane that writes +inf is lane 0 of the second round); "unbounded" where the entering column
+    holds a slack after a phase-1 pivot (no +inf anywhere)."""
+    n = 9
+    c = np.array([5.0, 5.0, 5.0, -2.0, -2.0, 5.0, -2.0, -2.0, 5.0])
+    A = np.zeros((5, n))
+    A[np.arange(5), [0, 1, 2, 5, 8]] = 4.0
+    b = np.array([4.0, 8.0, 12.0, 6.0, 4.0 * (1.0 + 2.5e-8)])
+    neg = [Call("negative precision %r, zeros" % p, [(c, A, b, None, None)], maximize=True, precision=p) for p in (-1e-8, -1.0)]
+    n = 1025
+    c = np.zeros(n)
+    c[-1] = 1.0
+    c[:8] = 0.5
+    A = np.zeros((3, n))
+    A[0, :8], A[1, 8:16], A[2, -1] = 1.0, 1.0, -1.0
+    last = Call("unbounded at the last variable", [(c, A, np.array([2.0, 3.0, 1.0]), None, None)], maximize=True)
+    slack = Call("unbounded at a slack after a pivot", [(np.array([1.0, -1.0, 0.0]), np.array([[-1.0, 0.0, 0.0], [0.0, 1.0, 1.0]]),
+                                                        np.array([-1.0, 2.0]), None, None)], maximize=True)
+    return neg + [last, slack]
+
+
+ENDING_NAMES = ["negative precision -1e-08, zeros", "negative precision -1.0, zeros", "unbounded at the last variable",
+                "unbounded at a slack after a pivot"]
+
+
 def names():
     """The names of table()'s calls, without building one (the tests are parametrised by them)."""
     out = ["n=1 m=1", "n=2 m=1", "odd n, both kinds of rows", "even n, both kinds of rows, maximize", "equalities only", "n=0",
@@ -123,6 +189,7 @@ def names():
     out += ["edge %s" % f for f in E.FAMILIES if E.shapes_for(f, *EDGE_SHAPE)]
     out += ["nonfinite %s" % f for f in NF.FAMILIES[:6]]
     out += ["cycled by budget", "hist clean", "queue"]
+    out += ["nonfinite N7 s%d" % seed for seed in N7_SEEDS] + precision_names() + ENDING_NAMES
     return out
 
 
@@ -168,6 +235,12 @@ def table(oracle):
     T.append(tableau_call("cycled by budget", [D(30, 29, 3), D(30, 29, 4)], 30, 31, max_pivots=3.0))
     T.append(hist_call(oracle))
     T.append(random_call("queue", QUEUE_LPS, 4, 4, 0, maximize=True))
+    for seed in N7_SEEDS:
+        m = NF.make("N7", M, N, seed, dense_lp=D)
+        o = NF.options("N7", M, N, seed)
+        T.append(tableau_call("nonfinite N7 s%d" % seed, [m], N + 1, M + 1, precision=o["precision"], max_pivots=o["max_pivots"], check=o["check_cycles"]))
+    T += [precision_call(n, m, p) for n, m in PRECISION_SHAPES for p in RD.PRECISIONS]
+    T += ending_calls()
     assert [c.name for c in T] == names()
     return T
 
@@ -225,6 +298,18 @@ def strided_inputs():
     return dict(c=ints(-2, 5, B, n), A_ub=ints(0, 4, m_ub, n), b_ub=ints(1, 9, B, m_ub), A_eq=ints(0, 3, B, m_eq, n), b_eq=ints(1, 4, m_eq))
 
 
+def offset_inputs():
+    """The LPs of the second views test: B = 5, n = 6, m_ub = 3; c and b_ub are one row each, expanded over the batch (a batch
+    stride of 0 in a batched tensor), A_ub lies inside a wider tensor behind a storage offset."""
+    rng = np.random.default_rng(20261023)
+    ints = lambda lo, hi, *shape: rng.integers(lo, hi, shape).astype(np.float64)
+    return dict(c=ints(1, 6, 6), A_ub=ints(0, 4, 5, 3, 6), b_ub=ints(1, 9, 3))
+
+
+def offset_call(inputs):
+    return Call("offset views", [(inputs["c"], inputs["A_ub"][i], inputs["b_ub"], None, None) for i in range(inputs["A_ub"].shape[0])], maximize=True)
+
+
 def strided_call(inputs):
     """strided_inputs() as the Call the oracle answers: every LP with its own copy of the shared operands."""
     B = inputs["c"].shape[0]
@@ -262,6 +347,20 @@ def plumbing(torch, out):
     out["views/unchanged"] = np.bool_(all(a.tobytes() == t.cpu().numpy().tobytes() for a, t in zip(before, held)))
     call = strided_call(inp)
     put("contiguous", answer(tensors.linprog_batch(*[dev(a) for a in call.stacked()])))
+
+    # views again: c and b_ub expanded over the batch (stride 0), A_ub behind a storage offset inside a wider tensor
+    inp = offset_inputs()
+    B, m, n = inp["A_ub"].shape
+    A_wide = torch.full((B, m + 1, n + 2), -9.0, dtype=torch.float64, device="cuda")
+    A_wide[:, 1:, 2:] = dev(inp["A_ub"])
+    c_row, b_row = dev(inp["c"]), dev(inp["b_ub"])
+    held = [A_wide, c_row, b_row]
+    before = [t.cpu().numpy().copy() for t in held]
+    views = (c_row.expand(B, n), A_wide[:, 1:, 2:], b_row.expand(B, m))
+    assert views[0].stride() == (0, 1) and views[2].stride() == (0, 1) and views[1].storage_offset() == (n + 2) + 2 and not views[1].is_contiguous()
+    put("offset views", answer(tensors.linprog_batch(*views, maximize=True)))
+    out["offset views/unchanged"] = np.bool_(all(a.tobytes() == t.cpu().numpy().tobytes() for a, t in zip(before, held)))
+    put("offset contiguous", answer(tensors.linprog_batch(*[dev(a) for a in offset_call(inp).stacked()[:3]], maximize=True)))
     default_handles = len(tensors._handles)
 
     # the producer of A_ub on a side stream, directly before the call on that stream; then another shape on the same handle

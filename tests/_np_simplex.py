@@ -48,13 +48,14 @@ def _js_round(x):
     if x != x or math.isinf(x):
         return x
     f = math.floor(x)
-    return f + 1.0 if x - f >= 0.5 else float(f)
+    r = f + 1.0 if x - f >= 0.5 else float(f)
+    return math.copysign(0.0, x) if r == 0.0 else r  # (Math.round keeps the sign of a zero: -0 on [-0.5, -0])
 
 
 def round_to_precision(num, precision):  # src/util.ts:1-4
-    rounding = _js_round(1.0 / precision if precision != 0 else math.inf)  # (JS: 1 / 0 = Infinity, the result NaN)
-    with np.errstate(all="ignore"):  # (JS divides by zero: precision +inf gives rounding 0 and the result 0 / 0 = NaN)
-        return float(np.float64(_js_round((num + 2.220446049250313e-16) * rounding)) / np.float64(rounding))
+    with np.errstate(all="ignore"):  # (JS divides by zero: 1 / +-0 = +-Infinity; a rounding of 0 gives the result 0 / 0 = NaN)
+        rounding = np.float64(_js_round(float(np.float64(1.0) / np.float64(precision))))
+        return float(np.float64(_js_round(float((np.float64(num) + np.float64(2.220446049250313e-16)) * rounding))) / rounding)
 
 
 def pivot(M, pos, var, row, col, block=1024, rules=frozenset()):

@@ -9,6 +9,7 @@ import pytest
 
 from tests import _edges as E
 from tests import _golden as G
+from tests import _rounding as RD
 
 pytestmark = pytest.mark.gpu
 
@@ -107,6 +108,39 @@ SHARD_CASES = [pytest.param(name, rec, id="%s-%s" % (name, E.label(rec))) for na
                for rec in _records(shape, True, SHARD_FAMILIES, least)]
 
 
+# the family R (tests/_rounding.py, tests/golden/simplex_rounding_edges.json.gz): runs that end "optimal" with the result -0 (or
+# NaN: precision 3.0) after 0, 1 and many pivots, through the same two tables; the row shards run R0, R1 and Rn
+R_SHARD_FAMILIES = ("R0", "R1", "Rn")
+
+
+def _r_records(shape, families=None, min_pivots=0):
+    return [r for r in G.records("rounding_edges") if (r["M"], r["N"]) == shape and (families is None or r["family"] in families)
+            and r["n_pivots"] >= min_pivots]
+
+
+R_CASES = [pytest.param(name, rec, id="%s-%s" % (name, E.label(rec))) for name, (_, shape, _, _, _) in PATHS.items()
+           for rec in _r_records(shape)]
+R_SHARD_CASES = [pytest.param(name, rec, id="%s-%s" % (name, E.label(rec))) for name, (_, _, _, shape, _, _, _, least) in SHARDS.items()
+                 for rec in _r_records(shape, R_SHARD_FAMILIES, least)]
+
+
+def test_path_table_runs_the_rounding_family_on_every_row():
+    """Every path and every shard row has R records with at least as many pivots as the row needs, each of them "optimal"
+    with the reference's result -0 (NaN at precision 3.0): the sign of a rounded zero is compared on every kernel path."""
+    for name, (_, shape, _, _, _) in PATHS.items():
+        recs = _r_records(shape)
+        assert {r["family"] for r in recs} == set(RD.R_FAMILIES), name
+        assert any(r["n_pivots"] >= 8 for r in recs), name
+    for name, (_, _, _, shape, _, _, _, least) in SHARDS.items():
+        recs = _r_records(shape, R_SHARD_FAMILIES, least)
+        assert recs and any(r["n_pivots"] >= max(least, 8) for r in recs), name
+        assert least > 0 or {r["family"] for r in recs} == set(R_SHARD_FAMILIES), name
+    for p in R_CASES + R_SHARD_CASES:
+        rec = p.values[1]
+        assert rec["status"] == "optimal" and rec["result_hex"] in (RD.hexd(-0.0), RD.hexd(float("nan"))), p.id
+        assert (rec["result_hex"] == RD.hexd(float("nan"))) == (rec["family"] == "R1n"), p.id
+
+
 def test_path_table_names_every_kernel_family():
     """Dropping a path from the tables (or its every record) fails here, whatever else runs."""
     assert {v[0] for v in PATHS.values()} | {v[0] for v in SHARDS.values()} == KERNEL_FAMILIES
@@ -147,13 +181,13 @@ def _compare(rec, status, result, npiv, matrix, pos, var):
     assert G.sha256(matrix) == exp["final_sha256"]
 
 
-@pytest.mark.parametrize("name,rec", CASES)
-def test_edge_record_on_path(nat, monkeypatch, name, rec):
+def _run_on_path(nat, monkeypatch, name, rec, initial):
+    """The record's tableau (initial(rec, dense_lp)) through the path `name`: asserts the kernel, returns what _compare takes."""
     _, _, env, want, _ = PATHS[name]
     for k, v in env.items():
         monkeypatch.setenv(k, v)
     from tests import _oracle
-    m = E.initial(rec, _oracle.load().dense_lp)
+    m = initial(rec, _oracle.load().dense_lp)
     w, h = rec["width"], rec["height"]
     pos, var = G.identity_perms(rec)
     o = G.options(rec)
@@ -184,18 +218,29 @@ def test_edge_record_on_path(nat, monkeypatch, name, rec):
                 assert _matches(k, info.get(k, ""), v), (k, v, info)
     finally:
         ctx.close()
-    _compare(rec, status, result, npiv, got, gpos, gvar)
+    return status, result, npiv, got, gpos, gvar
 
 
-@pytest.mark.parametrize("name,rec", SHARD_CASES)
-def test_edge_record_on_row_shards(tmp_path, monkeypatch, name, rec):
-    """tests/_shard_worker.py with the record's tableau (`npy:`), precision, checkCycles and pivot budget."""
+@pytest.mark.parametrize("name,rec", CASES)
+def test_edge_record_on_path(nat, monkeypatch, name, rec):
+    _compare(rec, *_run_on_path(nat, monkeypatch, name, rec, E.initial))
+
+
+@pytest.mark.parametrize("name,rec", R_CASES)
+def test_rounding_record_on_path(nat, monkeypatch, name, rec):
+    """test_edge_record_on_path on the family R, and the result word for word: -0 is not +0."""
+    out = _run_on_path(nat, monkeypatch, name, rec, RD.r_initial)
+    _compare(rec, *out)
+    assert RD.hexd(out[1]) == rec["result_hex"], (out[1], rec["result_hex"])
+
+
+def _run_on_row_shards(tmp_path, monkeypatch, name, rec, initial):
     from tests import _oracle
     from tests.test_sharded import run_world
     _, kind, world, _, env, kernel, sweep, _ = SHARDS[name]
     for k, v in env.items():
         monkeypatch.setenv(k, v)
-    m = E.initial(rec, _oracle.load().dense_lp)
+    m = initial(rec, _oracle.load().dense_lp)
     path = str(tmp_path / "edge.npy")
     np.save(path, m)
     o = G.options(rec)
@@ -205,3 +250,17 @@ def test_edge_record_on_row_shards(tmp_path, monkeypatch, name, rec):
     assert str(res["shard_sweep"]) == sweep, (str(res["shard_sweep"]), sweep)
     _compare(rec, str(res["status"]), float(res["result"]), int(res["pivots"]), res["matrix"], res["pos"], res["var"])
     os.remove(path)
+    return float(res["result"])
+
+
+@pytest.mark.parametrize("name,rec", SHARD_CASES)
+def test_edge_record_on_row_shards(tmp_path, monkeypatch, name, rec):
+    """tests/_shard_worker.py with the record's tableau (`npy:`), precision, checkCycles and pivot budget."""
+    _run_on_row_shards(tmp_path, monkeypatch, name, rec, E.initial)
+
+
+@pytest.mark.parametrize("name,rec", R_SHARD_CASES)
+def test_rounding_record_on_row_shards(tmp_path, monkeypatch, name, rec):
+    """test_edge_record_on_row_shards on the family R, and the result word for word."""
+    result = _run_on_row_shards(tmp_path, monkeypatch, name, rec, RD.r_initial)
+    assert RD.hexd(result) == rec["result_hex"], (result, rec["result_hex"])

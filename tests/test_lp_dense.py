@@ -96,9 +96,18 @@ def test_call_against_the_oracle(ran, calls, oracle, name):
         assert refs[0]["status"] == "cycled" and refs[0]["n_pivots"] < call.max_pivots and call.check
     if name == "cycled by budget":
         assert all(r["status"] == "cycled" and r["n_pivots"] == 3 for r in refs)
-    if name.startswith("nonfinite"):  # planted in the operands, or (N5) made by overflow from finite input
+    if name.startswith("nonfinite N7"):  # finite operands, an option that is not finite or is negative
+        assert np.isfinite(refs[0]["start"]).all() and not (0.0 <= call.precision < np.inf and 0.0 <= call.max_pivots), name
+    elif name.startswith("nonfinite"):  # planted in the operands, or (N5) made by overflow from finite input
         planted, made = not np.isfinite(refs[0]["start"]).all(), not np.isfinite(refs[0]["matrix"]).all()
         assert (made and not planted) if name == "nonfinite N5" else planted, (name, planted, made)
+    if name == "unbounded at the last variable":
+        assert refs[0]["status"] == "unbounded" and np.flatnonzero(refs[0]["x"] == np.inf).tolist() == [call.n - 1] and call.n - 1 == 1024
+    if name == "unbounded at a slack after a pivot":
+        assert refs[0]["status"] == "unbounded" and refs[0]["n_pivots"] == 1 and not np.isinf(refs[0]["x"]).any()
+        assert int(refs[0]["var"][int(refs[0]["result"])]) - 1 >= call.n
+    if name.startswith("negative precision"):  # the reference rounds zeros there, to +0.0: no -0.0 in x
+        assert refs[0]["status"] == "optimal" and (refs[0]["x"] == 0.0).any() and not np.signbit(refs[0]["x"]).any(), refs[0]["x"]
     if name == "queue":
         assert len(call.lps) > int(got["grids"][0]) >= 2048, "every workgroup is to take several LPs"
         assert {r["status"] for r in refs} == {"optimal", "infeasible", "unbounded"}
@@ -144,6 +153,37 @@ def test_views_give_the_bits_of_contiguous_operands(ran, oracle):
         assert views[key].tobytes() == contiguous[key].tobytes(), key
     assert bool(views["unchanged"])
     assert any(r["status"] == "optimal" for r in refs)
+
+
+def test_expanded_and_offset_views_give_the_bits_of_contiguous_operands(ran, oracle):
+    """c and b_ub as one row expanded over the batch (a batch stride of 0), A_ub as the slice [:, 1:, 2:] of a wider tensor (a
+    storage offset, padded rows): the oracle's bits, the bits of contiguous copies, and no input changed."""
+    call = LD.offset_call(LD.offset_inputs())
+    views, contiguous = of(ran, "offset views"), of(ran, "offset contiguous")
+    refs = check_answers(views, call, oracle, "offset views", kept=False)
+    check_answers(contiguous, call, oracle, "offset contiguous", kept=False)
+    for key in ("x", "objective", "status", "pivots"):
+        assert views[key].tobytes() == contiguous[key].tobytes(), key
+    assert bool(views["unchanged"])
+    assert any(r["status"] == "optimal" for r in refs)
+
+
+def test_precision_calls_put_basic_values_on_the_edges(calls, oracle):
+    """What the precision calls are there for, by the oracle: at every precision from 1e-8 up the run ends optimal with every
+    bounded variable basic at b / 4, values at the precision itself (not above it: 0), one ulp above it, on ties; the free variable
+    stays out of the basis; a rounded x differs from the value somewhere; the last variable is among the basic ones."""
+    for (n, m) in LD.PRECISION_SHAPES:
+        for p in (1e-8, 0.25, 0.75, 2.0, 2.5, 3.0):  # (at 1e-17 and 5e-324 the pivot flushes such right-hand sides to +0.0: |x| <= 1e-16)
+            call = calls["precision %r n=%d" % (p, n)]
+            ref = call.oracle_answer(oracle, 0)
+            c, A, b = call.lps[0][:3]
+            bound = {int(np.flatnonzero(row)[0]): b[i] / 4.0 for i, row in enumerate(A) if row.any()}
+            cols = sorted(bound)
+            assert ref["status"] == "optimal" and ref["n_pivots"] == len(cols), (p, n, ref["status"], ref["n_pivots"])
+            basic = {j: float(ref["col0"][int(ref["pos"][j + 1]) - call.w]) for j in range(n) if ref["pos"][j + 1] >= call.w}
+            assert basic == bound and cols[0] == 0 and cols[-1] == n - 1 and len(cols) < n, (p, n)
+            assert p in basic.values() and np.nextafter(p, np.inf) in basic.values()
+            assert ref["x"][[j for j in cols if basic[j] == p]].tolist() == [0.0] * sum(1 for j in cols if basic[j] == p)
 
 
 def test_producer_on_a_side_stream_and_one_handle_for_two_shapes(ran, oracle):

@@ -234,11 +234,12 @@ __device__ __forceinline__ KI block_argmin(KI v, double (*sk)[16], int (*si)[16]
     return row16_argmin(r); // every 16-lane row holds all NW wave results
 }
 
-// JS Math.round (halves toward +inf) and roundToPrecision (src/util.ts:1-4)
+// JS Math.round (halves toward +inf; a zero keeps the sign of x: -0 on [-0.5, -0]) and roundToPrecision (src/util.ts:1-4)
 __host__ __device__ inline double js_round(double x) {
     if (!(fabs(x) < INFINITY)) return x; // NaN, +-inf
     const double f = floor(x);
-    return (x - f >= 0.5) ? f + 1.0 : f;
+    const double r = (x - f >= 0.5) ? f + 1.0 : f;
+    return r == 0.0 ? copysign(0.0, x) : r;
 }
 __host__ __device__ inline double round_to_precision(double num, double precision) {
     const double rounding = js_round(1.0 / precision);

@@ -153,7 +153,8 @@ __host__ __device__ inline int mt_slot_add(const MtArena &a, int32_t s, int32_t 
 __host__ __device__ inline double mt_js_round(double x) { // Math.round
     if (!(fabs(x) < INFINITY)) return x;
     const double f = floor(x);
-    return (x - f >= 0.5) ? f + 1.0 : f;
+    const double r = (x - f >= 0.5) ? f + 1.0 : f;
+    return r == 0.0 ? copysign(0.0, x) : r; // (-0 on [-0.5, -0]; the caller takes fabs(val - round), which cannot tell)
 }
 __host__ __device__ inline double mt_most_fractional(const MtTree &T, const double *col0, const int32_t *pos, int32_t *variable,
                                                      double *value) {

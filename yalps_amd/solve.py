@@ -31,21 +31,26 @@ SPARSE_MIN_BYTES = 128 << 10  # below this the dense tableau goes through the si
 
 
 def round_to_precision(num, precision):
-    """src/util.ts:1-4 with JS Math.round (halves toward +infinity)."""
+    """src/util.ts:1-4 with JS Math.round: halves toward +infinity, and a zero keeps the sign of its argument (-0 on
+    [-0.5, -0]).  Divisions by zero give what IEEE gives, as in the reference: 1 / +-0 is +-infinity, and a rounding of 0
+    (any precision above 2) makes the result 0 / 0 = NaN."""
     def js_round(x):
         if x != x or math.isinf(x):
             return x
         f = math.floor(x)
-        return f + 1.0 if x - f >= 0.5 else float(f)
+        r = f + 1.0 if x - f >= 0.5 else float(f)
+        return math.copysign(0.0, x) if r == 0.0 else r
     if precision == 0:
-        rounding = math.inf
+        rounding = math.copysign(math.inf, precision)
     else:
         rounding = js_round(1.0 / precision)
-    v = (num + 2.220446049250313e-16) * rounding
+    v = js_round((num + 2.220446049250313e-16) * rounding)
+    if rounding == 0:
+        return math.nan
     # precision 0: inf / inf (or NaN) divided in hardware, as the reference divides.  The NaN's bits are the ISA's default
     # NaN (x86-64: sign bit set, 0xfff8...; aarch64: 0x7ff8...), so they equal the reference's on the same ISA; the MILP
     # records (tests/golden/simplex_milp.json.gz) were made on x86-64.
-    return js_round(v) / rounding
+    return v / rounding
 
 
 def hip_simplex(tableau, options):
