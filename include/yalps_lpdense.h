@@ -89,6 +89,31 @@ int32_t yalps_lpdense_solve(yalps_lpdense *d, int32_t count, int32_t n, int32_t 
                             int32_t checkCycles, int32_t keep_tableaux, double *x_out, double *objective_out,
                             int32_t *status_out, int64_t *pivots_out, float *gpu_ms_out);
 
+/* yalps_lpdense_solve (which is this call with three NULLs) plus the marginals of every LP, written by the workgroup that
+ * solved it from the final row 0 and positionOfVariable: three more DEVICE pointers, contiguous, each may be NULL, looked up
+ * and refused like the other outputs; one that has no element (m_ub = 0, m_eq = 0, n = 0 or count = 0) is never looked up
+ * or written.  With s = +1 maximise, -1 minimise, w = n + 1, pos = the final positionOfVariable,
+ * cost(c) = row0[c] < 0 ? row0[c] : 0 (a NaN row0[c] gives NaN), and for tableau row r
+ * y(r) = -cost(pos[w + r]) where pos[w + r] < w (the row's slack is non-basic), else 0:
+ *   ineqlin_out[count][m_ub]  optimal: s * y(1 + i) + 0.0; else NaN
+ *   eqlin_out[count][m_eq]    optimal: s * (y(1 + m_ub + 2k) - y(2 + m_ub + 2k)) + 0.0 -- the row of b_eq[k] minus the row of
+ *                             its negation; both slacks can be non-basic at once; else NaN
+ *   reduced_out[count][n]     optimal: s * cost(pos[j + 1]) + 0.0 where pos[j + 1] < w (variable j is non-basic), else +0.0;
+ *                             not optimal: NaN
+ * (+ 0.0: a -0.0 becomes +0.0.)  "unbounded" gives NaN too: there is no dual solution.  These are d(objective_out) / d(b_ub),
+ * d(objective_out) / d(b_eq) and the reduced costs of x >= 0 in the caller's own direction: for minimise scipy's
+ * ineqlin.marginals, eqlin.marginals and lower.marginals, for maximise the negations of what scipy reports for -c; at a
+ * degenerate vertex those of the basis the reference's pivot rule ends in.  For every optimal LP
+ * objective = ineqlin . b_ub + eqlin . b_eq and reduced = c - A_ub^T ineqlin - A_eq^T eqlin, up to rounding.  They are what
+ * yalps_amd.sensitivity gives as `dual` and `reduced_cost` for the equivalent model, bit for bit. */
+int32_t yalps_lpdense_solve_duals(yalps_lpdense *d, int32_t count, int32_t n, int32_t m_ub, int32_t m_eq,
+                                  const yalps_lpdense_operand *c, const yalps_lpdense_operand *A_ub,
+                                  const yalps_lpdense_operand *b_ub, const yalps_lpdense_operand *A_eq,
+                                  const yalps_lpdense_operand *b_eq, int32_t maximize, double precision, double maxPivots,
+                                  int32_t checkCycles, int32_t keep_tableaux, double *x_out, double *objective_out,
+                                  int32_t *status_out, int64_t *pivots_out, double *ineqlin_out, double *eqlin_out,
+                                  double *reduced_out, float *gpu_ms_out);
+
 /* LP i of the last solve, copied to the HOST (for tests and debugging): what solution() reads -- column 0 (height
  * doubles) and both permutations (width + height int32 each).  NULL pointers are skipped. */
 int32_t yalps_lpdense_solution(yalps_lpdense *d, int32_t i, double *col0, int32_t *positionOfVariable,

@@ -75,7 +75,7 @@ MILPTREE_MAX_BYTES = 4 << 20  # YALPS_MILPTREE_MAX_BYTES: a tree's largest possi
 LPDENSE_LIB_PATH = os.environ.get("YALPS_LPDENSE_LIB") or os.path.join(HERE, "libyalps_lpdense.so")
 SYMBOLS_LPDENSE = (
     "yalps_lpdense_last_error", "yalps_lpdense_create", "yalps_lpdense_destroy", "yalps_lpdense_validate", "yalps_lpdense_solve",
-    "yalps_lpdense_solution", "yalps_lpdense_tableau", "yalps_lpdense_info",
+    "yalps_lpdense_solve_duals", "yalps_lpdense_solution", "yalps_lpdense_tableau", "yalps_lpdense_info",
 )
 LPDENSE_MAX_BYTES = 4 << 20  # YALPS_LPDENSE_MAX_BYTES
 LPBATCH_HBM_CLASS = 4        # yalps_lpbatch_class: 0..3 the LDS form, 4 the HBM form
@@ -965,6 +965,8 @@ _BATCH_LIBS["yalps_lpdense"] = (LPDENSE_LIB_PATH, {
         "validate": (_I32, [_I32, _I32, _I32, _I32, _DOP, _DOP, _DOP, _DOP, _DOP]),
         "solve": (_I32, [_VP, _I32, _I32, _I32, _I32, _DOP, _DOP, _DOP, _DOP, _DOP, _I32, C.c_double, C.c_double, _I32, _I32,
                          _VP, _VP, _VP, _VP, C.POINTER(C.c_float)]),
+        "solve_duals": (_I32, [_VP, _I32, _I32, _I32, _I32, _DOP, _DOP, _DOP, _DOP, _DOP, _I32, C.c_double, C.c_double, _I32, _I32,
+                               _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.POINTER(C.c_float)]),
         "solution": (_I32, [_VP, _I32, _VP, _VP, _VP]), "tableau": (_I32, [_VP, _I32, _VP])})
 
 
@@ -1000,16 +1002,21 @@ class LpDense:
         self.shape = None  # (count, width, height) of the last solve
 
     def solve(self, count, n, m_ub, m_eq, operands, maximize=False, precision=1e-8, max_pivots=8192.0, check_cycles=False,
-              keep_tableaux=False, x=None, objective=None, status=None, pivots=None):
+              keep_tableaux=False, x=None, objective=None, status=None, pivots=None, ineqlin=None, eqlin=None, reduced=None):
         """operands = (c, A_ub, b_ub, A_eq, b_eq), each (device pointer, batch, row, col strides in doubles) or None where it
         has no element; x / objective / status / pivots: device pointers of contiguous float64 [count][n], float64 [count],
-        int32 [count], int64 [count], or None.  The outputs are complete on return.  Returns gpu_ms."""
+        int32 [count], int64 [count], or None; ineqlin / eqlin / reduced: the marginals (yalps_lpdense_solve_duals), device
+        pointers of contiguous float64 [count][m_ub], [count][m_eq], [count][n], or None -- with all three None the call is
+        yalps_lpdense_solve.  The outputs are complete on return.  Returns gpu_ms."""
         ops = _dense_operands(operands)
         ms = C.c_float()
         self.shape = None
-        lpdense_check(lpdense_lib().yalps_lpdense_solve(
-            self.handle, int(count), int(n), int(m_ub), int(m_eq), *(C.byref(o) for o in ops), int(bool(maximize)), float(precision),
-            float(max_pivots), int(bool(check_cycles)), int(bool(keep_tableaux)), x, objective, status, pivots, C.byref(ms)))
+        head = (self.handle, int(count), int(n), int(m_ub), int(m_eq), *(C.byref(o) for o in ops), int(bool(maximize)), float(precision),
+                float(max_pivots), int(bool(check_cycles)), int(bool(keep_tableaux)), x, objective, status, pivots)
+        if ineqlin is None and eqlin is None and reduced is None:
+            lpdense_check(lpdense_lib().yalps_lpdense_solve(*head, C.byref(ms)))
+        else:
+            lpdense_check(lpdense_lib().yalps_lpdense_solve_duals(*head, ineqlin, eqlin, reduced, C.byref(ms)))
         self.shape = (int(count), int(n) + 1, 1 + int(m_ub) + 2 * int(m_eq))
         return ms.value
 

@@ -68,9 +68,9 @@ int validate(int32_t count, int32_t n, int32_t m_ub, int32_t m_eq, const yalps_l
 }
 
 // A pointer the kernel is to dereference: device (or managed) memory of the handle's device, known to THIS runtime.
-int check_pointer(const yalps_lpdense *b, const char *name, const void *p) {
+int check_pointer(const yalps_lpdense *b, const char *entry, const char *name, const void *p) {
     if (!p) return 0;
-    const std::string who = std::string("yalps_lpdense_solve: ") + name;
+    const std::string who = std::string(entry) + ": " + name;
     hipPointerAttribute_t attr;
     std::memset(&attr, 0, sizeof attr);
     if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
@@ -98,10 +98,11 @@ int create_impl(int32_t device, void *hip_stream, yalps_lpdense **out) {
     return raise_lds_limit(kDenseKernels);
 }
 
-int solve_impl(yalps_lpdense *b, int32_t count, int32_t n, int32_t m_ub, int32_t m_eq, const yalps_lpdense_operand *c,
+int solve_impl(yalps_lpdense *b, const char *entry, int32_t count, int32_t n, int32_t m_ub, int32_t m_eq, const yalps_lpdense_operand *c,
                const yalps_lpdense_operand *A_ub, const yalps_lpdense_operand *b_ub, const yalps_lpdense_operand *A_eq,
                const yalps_lpdense_operand *b_eq, int32_t maximize, double precision, double maxPivots, int32_t checkCycles, int32_t keep,
-               double *x_out, double *objective_out, int32_t *status_out, int64_t *pivots_out, float *gpu_ms_out) {
+               double *x_out, double *objective_out, int32_t *status_out, int64_t *pivots_out, double *ineqlin_out,
+               double *eqlin_out, double *reduced_out, float *gpu_ms_out) {
     if (int rc = validate(count, n, m_ub, m_eq, c, A_ub, b_ub, A_eq, b_eq)) return rc;
     b->count = 0;
     b->q.keep = keep != 0;
@@ -120,9 +121,12 @@ int solve_impl(yalps_lpdense *b, int32_t count, int32_t n, int32_t m_ub, int32_t
                     {"x_out", n ? x_out : nullptr},
                     {"objective_out", objective_out},
                     {"status_out", status_out},
-                    {"pivots_out", pivots_out}};
+                    {"pivots_out", pivots_out},
+                    {"ineqlin_out", m_ub ? ineqlin_out : nullptr},
+                    {"eqlin_out", m_eq ? eqlin_out : nullptr},
+                    {"reduced_out", n ? reduced_out : nullptr}};
     for (const auto &a : pointers)
-        if (int rc = check_pointer(b, a.name, a.p)) return rc;
+        if (int rc = check_pointer(b, entry, a.name, a.p)) return rc;
 
     hipStream_t s = b->stream;
     const int32_t w = n + 1, h = 1 + m_ub + 2 * m_eq;
@@ -151,6 +155,9 @@ int solve_impl(yalps_lpdense *b, int32_t count, int32_t n, int32_t m_ub, int32_t
     D.b_eq = operand(b_eq, true);
     D.x = x_out ? x_out : reinterpret_cast<double *>(behind);
     D.objective = objective_out ? objective_out : reinterpret_cast<double *>(behind + own_x);
+    D.ineqlin = m_ub ? ineqlin_out : nullptr; // (an output without an element is not written, whatever was passed)
+    D.eqlin = m_eq ? eqlin_out : nullptr;
+    D.reduced = n ? reduced_out : nullptr;
     HIP_TRY(hipMemcpyAsync(b->call.p, &D, sizeof D, hipMemcpyHostToDevice, s));
     if (int rc = reset_status(b->q, s, cnt)) return rc;
     b->w = w;
@@ -226,8 +233,24 @@ int32_t yalps_lpdense_solve(yalps_lpdense *d, int32_t count, int32_t n, int32_t 
                             int32_t checkCycles, int32_t keep_tableaux, double *x_out, double *objective_out,
                             int32_t *status_out, int64_t *pivots_out, float *gpu_ms_out) {
     if (!d) return fail(YALPS_E_ARG, "yalps_lpdense_solve: handle is NULL");
-    const int32_t rc = solve_impl(d, count, n, m_ub, m_eq, c, A_ub, b_ub, A_eq, b_eq, maximize, precision, maxPivots, checkCycles,
-                                  keep_tableaux, x_out, objective_out, status_out, pivots_out, gpu_ms_out);
+    const int32_t rc = solve_impl(d, "yalps_lpdense_solve", count, n, m_ub, m_eq, c, A_ub, b_ub, A_eq, b_eq, maximize, precision, maxPivots,
+                                  checkCycles, keep_tableaux, x_out, objective_out, status_out, pivots_out, nullptr, nullptr, nullptr,
+                                  gpu_ms_out);
+    if (rc) d->count = 0; // (no last solve to read from)
+    return rc;
+}
+
+int32_t yalps_lpdense_solve_duals(yalps_lpdense *d, int32_t count, int32_t n, int32_t m_ub, int32_t m_eq,
+                                  const yalps_lpdense_operand *c, const yalps_lpdense_operand *A_ub,
+                                  const yalps_lpdense_operand *b_ub, const yalps_lpdense_operand *A_eq,
+                                  const yalps_lpdense_operand *b_eq, int32_t maximize, double precision, double maxPivots,
+                                  int32_t checkCycles, int32_t keep_tableaux, double *x_out, double *objective_out,
+                                  int32_t *status_out, int64_t *pivots_out, double *ineqlin_out, double *eqlin_out,
+                                  double *reduced_out, float *gpu_ms_out) {
+    if (!d) return fail(YALPS_E_ARG, "yalps_lpdense_solve_duals: handle is NULL");
+    const int32_t rc = solve_impl(d, "yalps_lpdense_solve_duals", count, n, m_ub, m_eq, c, A_ub, b_ub, A_eq, b_eq, maximize, precision,
+                                  maxPivots, checkCycles, keep_tableaux, x_out, objective_out, status_out, pivots_out, ineqlin_out,
+                                  eqlin_out, reduced_out, gpu_ms_out);
     if (rc) d->count = 0; // (no last solve to read from)
     return rc;
 }

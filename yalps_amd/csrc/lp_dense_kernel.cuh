@@ -15,6 +15,10 @@
 //   after  does solution()'s work (src/YALPS.ts:8-50) for row i of the outputs x[count][n], objective[count]; what it reads --
 //          the LP's result, the permutations, column 0 -- it reads where the queue has just written them, behind a barrier
 //          of its own.  Skipped, but for that barrier, where the history was full: the rerun writes the row.
+//          Where the call asks for them (a uniform branch on three pointers) it also writes row i of the marginals
+//          ineqlin[count][m_ub], eqlin[count][m_eq], reduced[count][n]: sensitivity_of's `dual` and `reduced_cost`
+//          (yalps_amd/sensitivity.py) of the equivalent model, read off the final row 0 -- mat[c - 1] for column c >= 1 --
+//          and the final positionOfVariable; see marginals() below.
 // In between: the same work queue (wg_queue.cuh), wg_simplex unchanged, the same outputs.
 // The call's description lies in device memory (one DenseCall per call), not in the kernel's arguments: five operands with
 // three 64-bit strides each would sit in scalar registers through the solve.
@@ -31,11 +35,63 @@ struct DenseCall {
     DenseOperand c, A_ub, b_ub, A_eq, b_eq; // c and the b's: (batch, row) = (i, j), sc unused
     double *x;                    // [count][n]
     double *objective;            // [count]
+    double *ineqlin;              // [count][m_ub]  the marginals: nullptr where the call does not ask for them
+    double *eqlin;                // [count][m_eq]
+    double *reduced;              // [count][n]
 };
 
 struct DenseLaunch : QueueLaunch {
     const DenseCall *call;
 };
+
+// min(row0[c], 0) as np.minimum gives it: a NaN stays a NaN (this is not fmin); c >= 1
+__device__ __forceinline__ double dense_cost(const double *mat, int c) {
+    const double v = mat[c - 1];
+    return v < 0.0 ? v : (v == v ? 0.0 : v);
+}
+// y_r of tableau row r: -cost at the column its slack ended in, 0 where the slack is basic
+__device__ __forceinline__ double dense_row_dual(const double *mat, const int32_t *pos, int w, int r) {
+    const int p = pos[w + r];
+    return p < w ? -dense_cost(mat, p) : 0.0;
+}
+
+// Row i of the marginals, d(objective) / d(bound) in the caller's direction (s = sign); anything but optimal: NaN.
+//   ineqlin[r] = s * y(1 + r) + 0.0
+//   eqlin[k]   = s * (y(1 + m_ub + 2k) - y(2 + m_ub + 2k)) + 0.0     the upper row minus the negated one: both slacks can be
+//                                                                    non-basic at once
+//   reduced[j] = s * cost(pos[j + 1]) + 0.0 where variable j is non-basic, else +0.0
+// (+ 0.0 turns -0.0 into +0.0.)  Selects, negations, one subtraction, products with +-1: one lane per element, the lanes
+// striding as x's do; every lane of the workgroup calls it, under a condition all share; no LDS, no barrier.
+// Inlined: it costs the six instantiations two VGPRs (101-116 of 128) and no scratch; out of line (as sens_epilogue,
+// lp_sens_kernel.cuh) it built to 99-115 and a call, so there was nothing to buy.
+template <int T>
+__device__ __forceinline__ void dense_marginals(const DenseCall *d, const int32_t *pos, const double *mat, long long i,
+                                                       int w, bool optimal) {
+    const int tid = threadIdx.x, n = w - 1, m_ub = d->m_ub, m_eq = d->m_eq;
+    const double sign = d->sign, nan = __longlong_as_double(0x7ff8000000000000ll);
+    if (double *out = d->ineqlin) {
+        out += i * m_ub;
+        for (int r = tid; r < m_ub; r += T) out[r] = optimal ? sign * dense_row_dual(mat, pos, w, 1 + r) + 0.0 : nan;
+    }
+    if (double *out = d->eqlin) {
+        out += i * m_eq;
+        for (int k = tid; k < m_eq; k += T) {
+            const int r = 1 + m_ub + 2 * k;
+            out[k] = optimal ? sign * (dense_row_dual(mat, pos, w, r) - dense_row_dual(mat, pos, w, r + 1)) + 0.0 : nan;
+        }
+    }
+    if (double *out = d->reduced) {
+        out += i * n;
+        for (int j = tid; j < n; j += T) {
+            double v = nan;
+            if (optimal) {
+                const int p = pos[j + 1];
+                v = p < w ? sign * dense_cost(mat, p) + 0.0 : 0.0;
+            }
+            out[j] = v;
+        }
+    }
+}
 
 struct DenseJob : QueueJobBase {
     const DenseLaunch &L;
@@ -97,7 +153,7 @@ struct DenseJob : QueueJobBase {
 
     // solution() on the device: row idx of x and objective.  Every lane; the barrier is met whatever the status.
     template <int T>
-    __device__ __forceinline__ void after(const QueueItem &it, int status, const double *, const double *rhs, int) const {
+    __device__ __forceinline__ void after(const QueueItem &it, int status, const double *mat, const double *rhs, int) const {
         __syncthreads(); // the queue's copies of pos / var / col0 and lane T - 1's result are written
         if (status == WG_HISTORY_FULL) return;
         const int tid = threadIdx.x, w = it.w, n = w - 1;
@@ -124,6 +180,7 @@ struct DenseJob : QueueJobBase {
             for (int j = tid; j < n; j += T) x[j] = nan;
         }
         if (tid == 0) d->objective[i] = objective;
+        if (d->ineqlin || d->eqlin || d->reduced) dense_marginals<T>(d, L.pos + it.perm_off, mat, i, w, status == YALPS_OPTIMAL);
     }
 };
 

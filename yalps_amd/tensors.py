@@ -1,7 +1,9 @@
-"""linprog_batch: batches of small dense LPs straight from torch tensors on the GPU (libyalps_lpdense.so).
+"""linprog_batch: batches of small dense LPs straight from torch tensors on the GPU (libyalps_lpdense.so), with their dual
+solutions on request, and linprog_objective: the optimal value as a differentiable torch function.
 
-This module imports torch; `import yalps_amd` does not.  Nothing here computes with torch: it supplies the device pointers,
-the strides and the stream, and allocates the outputs.
+This module imports torch; `import yalps_amd` does not.  linprog_batch computes nothing with torch: it supplies the device
+pointers, the strides and the stream, and allocates the outputs.  linprog_objective's backward is a handful of torch
+operations on the tensors linprog_batch returned.
 
 Loading rule: torch brings its own HIP runtime, and a pointer or a stream is only good in the runtime that made it.  torch
 must be initialised in the process before the first call into ANY of this package's libraries (solve, solve_many, _native
@@ -17,6 +19,7 @@ import torch
 from . import _native
 
 LinprogBatch = namedtuple("LinprogBatch", ("x", "objective", "status", "pivots"))
+LinprogDuals = namedtuple("LinprogDuals", LinprogBatch._fields + ("ineqlin", "eqlin", "reduced_costs"))
 
 STATUS_NAMES = _native.STATUS[:4]  # the YALPS_* codes 0..3 as solve() spells them
 
@@ -60,7 +63,7 @@ def _strides(t, batched, matrix):
 
 
 def linprog_batch(c, A_ub=None, b_ub=None, A_eq=None, b_eq=None, *, maximize=False, precision=1e-8, max_pivots=8192,
-                  check_cycles=False, stats=None):
+                  check_cycles=False, stats=None, duals=False):
     """Solves B dense LPs of one shape in one call, from device tensors to device tensors:
 
         minimize (or maximize=True: maximize)  c . x   subject to   A_ub x <= b_ub,   A_eq x = b_eq,   x >= 0
@@ -86,6 +89,18 @@ def linprog_batch(c, A_ub=None, b_ub=None, A_eq=None, b_eq=None, *, maximize=Fal
     Raises TypeError / ValueError, before the library is touched, for anything but float64 tensors, mismatched B, m or n,
     a tableau (n + 1) x (1 + m_ub + 2 m_eq) above 4 MiB (solve() is the route for such models), CPU tensors and tensors on
     different devices.  stats (a dict, optional) receives "launches", "reruns", "kernels" and "gpu_ms" of the call.
+
+    duals=True returns LinprogDuals(x, objective, status, pivots, ineqlin [B, m_ub], eqlin [B, m_eq], reduced_costs [B, n]):
+    the same four tensors, bit for bit, and the dual solution of every LP, float64 on the inputs' device (a side without
+    rows gives a tensor with no element, not None), written by the workgroup that solved the LP from its final tableau.
+    Sign: ineqlin = d(objective) / d(b_ub), eqlin = d(objective) / d(b_eq) and reduced_costs = the objective's change per
+    unit of a variable that is at zero, all in the caller's own direction, `objective` being the tensor returned.  With
+    maximize=False they are scipy.optimize.linprog's ineqlin.marginals, eqlin.marginals and lower.marginals; with
+    maximize=True the negations of what scipy reports for -c.  At a degenerate vertex the duals are not unique: these are
+    the ones of the basis the reference's pivot rule ends in.  Every "optimal" row satisfies, up to rounding,
+        objective = ineqlin . b_ub + eqlin . b_eq        and        reduced_costs = c - A_ub^T ineqlin - A_eq^T eqlin.
+    Any other status -- "unbounded" too, which has no dual solution -- gives NaN in all three rows.  They equal, bit for
+    bit, the "dual" and "reduced_cost" sensitivity() reports for the equivalent model.
 
     See the module's docstring for the loading rule: torch first."""
     c, cB, (n,) = _operand("c", c, 1)
@@ -128,6 +143,7 @@ def linprog_batch(c, A_ub=None, b_ub=None, A_eq=None, b_eq=None, *, maximize=Fal
     objective = torch.empty((B,), dtype=torch.float64, device=device)
     status = torch.empty((B,), dtype=torch.int32, device=device)
     pivots = torch.empty((B,), dtype=torch.int64, device=device)
+    marginals = [torch.empty((B, k), dtype=torch.float64, device=device) for k in (m_ub, m_eq, n)] if duals else []
     ptr = lambda t: t.data_ptr() if t.numel() else None
     with torch.cuda.device(device), _lock:  # (the library selects the handle's device; torch's choice comes back afterwards)
         stream = torch.cuda.current_stream(device).cuda_stream or 1  # (the default stream's handle is 0: hipStreamLegacy names it)
@@ -136,8 +152,83 @@ def linprog_batch(c, A_ub=None, b_ub=None, A_eq=None, b_eq=None, *, maximize=Fal
         if handle is None:
             handle = _handles[key] = _native.LpDense(device.index, stream=stream)
         ms = handle.solve(B, n, m_ub, m_eq, operands, maximize=maximize, precision=precision, max_pivots=max_pivots,
-                          check_cycles=check_cycles, x=ptr(x), objective=ptr(objective), status=ptr(status), pivots=ptr(pivots))
+                          check_cycles=check_cycles, x=ptr(x), objective=ptr(objective), status=ptr(status), pivots=ptr(pivots),
+                          **{k: ptr(t) for k, t in zip(("ineqlin", "eqlin", "reduced"), marginals)})
         if stats is not None:
             info = handle.info()
             stats.update(launches=info["launches"], reruns=info["reruns"], kernels=info["kernels"], gpu_ms=ms)
+    if duals:
+        return LinprogDuals(x, objective, status, pivots, *marginals)
     return LinprogBatch(x, objective, status, pivots)
+
+
+class _Objective(torch.autograd.Function):
+    """objective [B] of B LPs whose five operands all carry the batch dimension (None: no rows of that kind); the solve's
+    whole answer rides along as non-differentiable outputs.  Backward is the envelope theorem on what forward saved."""
+
+    @staticmethod
+    def forward(ctx, options, c, A_ub, b_ub, A_eq, b_eq):
+        out = linprog_batch(c, A_ub, b_ub, A_eq, b_eq, duals=True, **options)
+        ctx.sides = (A_ub is not None, A_eq is not None)
+        ctx.save_for_backward(out.x, out.status, out.ineqlin, out.eqlin)
+        rest = out[:1] + out[2:]
+        ctx.mark_non_differentiable(*rest)
+        return (out.objective, *rest)
+
+    @staticmethod
+    def backward(ctx, g, *_):
+        x, status, ineqlin, eqlin = ctx.saved_tensors
+        ok = (status == 0).unsqueeze(1)
+        zero = torch.zeros((), dtype=x.dtype, device=x.device)
+        # (where, not a product: the NaN of a row that did not end optimal times 0 would still be NaN)
+        g = torch.where(ok, g.unsqueeze(1), zero)
+        x, ineqlin, eqlin = torch.where(ok, x, zero), torch.where(ok, ineqlin, zero), torch.where(ok, eqlin, zero)
+        need = ctx.needs_input_grad
+        grads = [None, g * x if need[1] else None]
+        for k, (has, y) in enumerate(zip(ctx.sides, (ineqlin, eqlin))):
+            gy = g * y
+            grads.append(-gy.unsqueeze(2) * x.unsqueeze(1) if has and need[2 + 2 * k] else None)
+            grads.append(gy if has and need[3 + 2 * k] else None)
+        return tuple(grads)
+
+
+def linprog_objective(c, A_ub=None, b_ub=None, A_eq=None, b_eq=None, *, maximize=False, precision=1e-8, max_pivots=8192,
+                      check_cycles=False):
+    """The optimal value of B dense LPs as a differentiable function of their data: (objective [B], LinprogDuals).
+
+    The operands and options are linprog_batch's.  Forward is one linprog_batch(..., duals=True) on the detached operands;
+    `objective` is LinprogDuals.objective, and carries a grad_fn when any operand requires grad.  Backward solves nothing:
+    it is the envelope theorem on the tensors of the forward call, computed with torch operations on the device.  Per LP,
+    with g the incoming gradient:
+
+        dc = g x      db_ub = g ineqlin      db_eq = g eqlin      dA_ub = -g ineqlin (x) x      dA_eq = -g eqlin (x) x
+
+    An operand without the batch dimension is shared by the LPs and receives the sum over the batch.
+
+    A row whose status is not "optimal" contributes a zero gradient to every operand: its objective is +-inf or NaN and its
+    marginals are NaN, and neither may poison the sum a shared operand receives.  The returned LinprogDuals.status says
+    which rows those are; mask their objectives before reducing them to a loss.
+
+    The optimal value is piecewise linear in b and c.  Inside a piece these are its derivatives; at a degenerate vertex,
+    where pieces meet, they are one subgradient -- the one of the basis the solve ended in.  `objective` is rounded to
+    `precision` as solve() rounds its result, so finite differences of it are only good to precision / step.  x itself is
+    piecewise constant and is returned without a gradient."""
+    options = dict(maximize=maximize, precision=precision, max_pivots=max_pivots, check_cycles=check_cycles)
+    given = {"c": c, "A_ub": A_ub, "b_ub": b_ub, "A_eq": A_eq, "b_eq": b_eq}
+    for tag in ("ub", "eq"):
+        if (given["A_" + tag] is None) != (given["b_" + tag] is None):
+            raise ValueError("linprog_objective: A_%s and b_%s come together" % (tag, tag))
+    ndim = {"c": 1, "A_ub": 2, "b_ub": 1, "A_eq": 2, "b_eq": 1}
+    sizes = {}
+    for name, t in given.items():
+        if t is not None:
+            batched = _operand(name, t, ndim[name])[1]
+            if batched is not None:
+                sizes[name] = batched
+    if len(set(sizes.values())) > 1:
+        raise ValueError("linprog_objective: the operands disagree about B: %s" % ", ".join("%s has %d" % kv for kv in sizes.items()))
+    B = next(iter(sizes.values()), 1)
+    # a shared operand as a view with a batch stride of 0, in front of the Function: autograd sums its gradient over the batch
+    expanded = [None if t is None else (t if name in sizes else t.unsqueeze(0).expand(B, *t.shape)) for name, t in given.items()]
+    objective, *rest = _Objective.apply(options, *expanded)
+    return objective, LinprogDuals(rest[0], objective.detach(), *rest[1:])
