@@ -1,0 +1,129 @@
+/*
+ * yalps_milpdense.h -- C ABI of libyalps_milpdense.so: a batch of dense MILPs of one shape, read from and answered in DEVICE
+ * memory, every branch-and-cut tree walked on the device (MI355X, gfx950).
+ *
+ * yalps_lpdense.h reads dense LPs where they lie; yalps_milptree.h walks whole trees on the device but takes packed cell
+ * lists from host memory.  Here the `count` MILPs of a call share one shape and one set of integer and binary variables and
+ * lie in device memory as yalps_lpdense.h's operands:
+ *     maximize | minimize  c . x   subject to   A_ub x <= b_ub,   A_eq x = b_eq,   x >= 0,
+ *     x[j] integer for j in `integers`,   x[j] in {0, 1} for j in `binaries`
+ * Three device parts on one stream:
+ *   root pass   milp_dense_root_kernel assembles the tableau `tableauModel` builds for the equivalent model (reference
+ *               src/tableau.ts:47-137): the 1 + m_ub + 2 m_eq rows of yalps_lpdense.h, then one row per binary variable in
+ *               ascending index -- column 0 1.0, the variable's column 1.0, the rest +0.0 -- so width = n + 1 and
+ *               height = 1 + m_ub + 2 m_eq + n_binaries; `simplex` solves it, one workgroup per MILP, tableaux kept.
+ *   tree pass   milp_tree_kernel as yalps_milptree.h runs it (src/branchAndCut.ts:89-176): arenas, reruns with four times
+ *               the room, and above the cap the status YALPS_MILPDENSE_OVERFLOW.  Skipped when n_integers = 0, as solve()
+ *               never enters branchAndCut then (src/YALPS.ts:81).
+ *   epilogue    milp_dense_solution_kernel reads every best tableau as `solution()` does (src/YALPS.ts:8-50) into dense rows.
+ * Values are taken as they lie in memory, NaN and infinities included.  The device reads no clock: the timeout is +Infinity.
+ * Per call the descriptors go up (one call description, the integer lists, 72 + 80 bytes per tree) and one int32 per tree
+ * per pass comes back: the statuses the host needs to decide about a rerun.
+ *
+ * Operands, strides, the return protocol, the stream rule and the pointer rule are yalps_lpdense.h's: element (i, r, c) of a
+ * matrix operand at ptr[i * batch + r * row + c * col]; negative = native failure with text through
+ * yalps_milpdense_last_error() (per thread); NO CPU fallback; every operand and output pointer is looked up in this
+ * library's HIP runtime and refused by name when it is host memory, memory of another device, or unknown to it.
+ *
+ * Environment (test hooks, read by yalps_milpdense_create): YALPS_MILPDENSE_ARENA (heap entries of the first arena, default
+ * 128), YALPS_MILPDENSE_ARENA_MAX (the cap, default 65536), YALPS_MILPDENSE_HIST (first checkCycles history capacity of both
+ * passes) and YALPS_MILPDENSE_GRID (workgroups per tree launch: one workgroup then walks many trees one after the other).
+ */
+#ifndef YALPS_MILPDENSE_H
+#define YALPS_MILPDENSE_H
+
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#ifndef YALPS_OPTIMAL
+#define YALPS_OPTIMAL 0
+#define YALPS_INFEASIBLE 1
+#define YALPS_UNBOUNDED 2
+#define YALPS_CYCLED 3
+#define YALPS_E_ARG (-1)    /* bad argument */
+#define YALPS_E_DEVICE (-2) /* no usable HIP device / HIP runtime error */
+#define YALPS_E_NOMEM (-3)  /* device or host allocation failed */
+#endif
+#define YALPS_MILPDENSE_TIMEDOUT 4 /* the search ended unfinished (src/branchAndCut.ts:166-173) */
+#define YALPS_MILPDENSE_OVERFLOW 5 /* the tree's frontier outgrew the largest arena: no result */
+
+#define YALPS_MILPDENSE_MAX_BYTES (4 << 20) /* the largest node, 8 * (n + 1) * (height + 2 * n_integers) bytes */
+
+typedef struct yalps_milpdense yalps_milpdense;
+
+typedef struct yalps_milpdense_operand {
+    const double *ptr; /* device memory; NULL where the operand has no element */
+    int64_t batch, row, col;
+} yalps_milpdense_operand;
+
+const char *yalps_milpdense_last_error(void);
+
+/* hip_stream: NULL = a private stream; otherwise every kernel / copy is enqueued on the caller's HIP stream.  The device's
+ * default stream, whose handle is NULL, is named by hipStreamLegacy ((hipStream_t)1). */
+int32_t yalps_milpdense_create(int32_t device, void *hip_stream, yalps_milpdense **out);
+void yalps_milpdense_destroy(yalps_milpdense *d);
+
+/* Host only (no device needed, no pointer dereferenced): what yalps_milpdense_solve checks before it touches the device.
+ * 0, or YALPS_E_ARG with the reason in the error text: everything yalps_lpdense_validate refuses, by the same words; a
+ * negative n_integers or n_binaries; a NULL list that has elements; `integers` or `binaries` (HOST arrays of 0-based
+ * variable indices) not strictly ascending or out of 0 .. n - 1; a binary variable that is not in `integers` (the integer
+ * list is the union of both sets); a largest node of 8 * (n + 1) * (height + 2 * n_integers) bytes above
+ * YALPS_MILPDENSE_MAX_BYTES. */
+int32_t yalps_milpdense_validate(int32_t count, int32_t n, int32_t m_ub, int32_t m_eq, const yalps_milpdense_operand *c,
+                                 const yalps_milpdense_operand *A_ub, const yalps_milpdense_operand *b_ub,
+                                 const yalps_milpdense_operand *A_eq, const yalps_milpdense_operand *b_eq,
+                                 int32_t n_integers, const int32_t *integers, int32_t n_binaries, const int32_t *binaries);
+
+/* Solves MILPs 0 .. count-1.  maximize != 0: maximise c . x, else minimise.  precision / maxPivots (may be +Infinity) /
+ * checkCycles / tolerance / maxIterations are the reference's Options, for the whole call.  trace_cap >= 0: the first
+ * trace_cap nodes every tree consumes are recorded for yalps_milpdense_trace.  All six outputs are DEVICE pointers,
+ * contiguous, and may be NULL:
+ *   x_out[count][n]         optimal, or timedout with a result: the variables' values in the best tableau, those above
+ *                           precision rounded to it, the others (a NaN too) +0.0; unbounded: +0.0 but +inf at the unbounded
+ *                           variable; else NaN
+ *   objective_out[count]    optimal / timedout with a result: -sign * result; unbounded: sign * inf; else NaN
+ *   status_out[count]       int32, YALPS_OPTIMAL .. YALPS_CYCLED, YALPS_MILPDENSE_TIMEDOUT or YALPS_MILPDENSE_OVERFLOW
+ *   nodes_out[count]        int64, nodes consumed (0 without a tree pass, and for an overflowed tree)
+ *   node_pivots_out[count]  int64, the sum of their pivots (likewise)
+ *   root_pivots_out[count]  int64, the root LP's pivots
+ * An overflowed tree has NaN in x_out and objective_out; yalps_milpdense_overflowed names those trees.  With n_integers = 0
+ * the first three outputs and root_pivots_out are yalps_lpdense_solve's x, objective, status and pivots, bit for bit.
+ * They are complete when the call returns.  call_stats_out (host, optional): [0] trees run again, [1] launches (all three
+ * parts), [2] overflowed trees, [3] / [4] / [5] HIP-event microseconds of root pass, tree pass and epilogue.
+ * count == 0 succeeds and launches nothing.  Nothing is launched when an argument is refused. */
+int32_t yalps_milpdense_solve(yalps_milpdense *d, int32_t count, int32_t n, int32_t m_ub, int32_t m_eq,
+                              const yalps_milpdense_operand *c, const yalps_milpdense_operand *A_ub,
+                              const yalps_milpdense_operand *b_ub, const yalps_milpdense_operand *A_eq,
+                              const yalps_milpdense_operand *b_eq, int32_t n_integers, const int32_t *integers,
+                              int32_t n_binaries, const int32_t *binaries, int32_t maximize, double precision,
+                              double maxPivots, int32_t checkCycles, double tolerance, double maxIterations,
+                              int32_t trace_cap, double *x_out, double *objective_out, int32_t *status_out,
+                              int64_t *nodes_out, int64_t *node_pivots_out, int64_t *root_pivots_out,
+                              int64_t *call_stats_out);
+
+/* The trees of the last solve that ended YALPS_MILPDENSE_OVERFLOW, ascending: at most `cap` indices into ids (HOST, may be
+ * NULL with cap = 0).  Returns their number. */
+int32_t yalps_milpdense_overflowed(const yalps_milpdense *d, int32_t *ids, int32_t cap);
+
+/* MILP i of the last solve, copied to the HOST (for tests and debugging): the tree's status and result, and what solution()
+ * reads of its best tableau -- *height_out rows, column 0 (room for height + 2 * n_integers doubles) and both permutations
+ * (room for width + height + 2 * n_integers).  NULL pointers are skipped. */
+int32_t yalps_milpdense_solution(yalps_milpdense *d, int32_t i, int32_t *status_out, double *result_out, int32_t *height_out,
+                                 double *col0, int32_t *positionOfVariable, int32_t *variableAtPosition);
+/* MILP i of the last solve (trace_cap > 0), as yalps_milptree_trace: its first *count_out <= trace_cap consumed nodes in pop
+ * order, cuts packed node after node (room for trace_cap * 2 * n_integers each).  Any output may be NULL. */
+int32_t yalps_milpdense_trace(yalps_milpdense *d, int32_t i, int32_t *count_out, double *eval, int32_t *status, double *result,
+                              int64_t *pivots, int32_t *height, int32_t *cut_sign, int32_t *cut_var, double *cut_val);
+/* Text about the last solve: "launches=.. reruns=.. overflows=.. gpu_us=.. root_us=.. tree_us=.. epilogue_us=..
+ * rerun_lps=[..] rerun_trees=[..]", then one line per launch with the kernel's spelling, its size class, LP or tree count,
+ * grid, LDS bytes, history and arena capacity.  Writes at most len - 1 characters and returns the length of the whole text
+ * (>= len: cut, call again with a larger buffer). */
+int32_t yalps_milpdense_info(const yalps_milpdense *d, char *buf, int32_t len);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* YALPS_MILPDENSE_H */

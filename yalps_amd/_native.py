@@ -78,6 +78,12 @@ SYMBOLS_LPDENSE = (
     "yalps_lpdense_solve_duals", "yalps_lpdense_solution", "yalps_lpdense_tableau", "yalps_lpdense_info",
 )
 LPDENSE_MAX_BYTES = 4 << 20  # YALPS_LPDENSE_MAX_BYTES
+MILPDENSE_LIB_PATH = os.environ.get("YALPS_MILPDENSE_LIB") or os.path.join(HERE, "libyalps_milpdense.so")
+SYMBOLS_MILPDENSE = (
+    "yalps_milpdense_create", "yalps_milpdense_destroy", "yalps_milpdense_validate", "yalps_milpdense_solve",
+    "yalps_milpdense_overflowed", "yalps_milpdense_solution", "yalps_milpdense_trace", "yalps_milpdense_info",
+    "yalps_milpdense_last_error")
+MILPDENSE_MAX_BYTES = 4 << 20  # YALPS_MILPDENSE_MAX_BYTES: the largest possible node, root height + 2 * n_integers rows
 LPBATCH_HBM_CLASS = 4        # yalps_lpbatch_class: 0..3 the LDS form, 4 the HBM form
 
 
@@ -1473,3 +1479,125 @@ def milp_tree_search(roots, evaluate, arena=None, consumed=None, arena_max=None)
         out.append((STATUS_MILPTREE[st[i]], float(res[i]), h, col0[c0_off[i]:c0_off[i] + h].copy(), pos[p_off[i]:p_off[i] + w + h].copy(),
                     var[p_off[i]:p_off[i] + w + h].copy(), int(stats[2 * i]), int(stats[2 * i + 1])))
     return out, reruns.value
+
+
+# ---------------------------------------------------------------------------------------------- libyalps_milpdense.so
+
+_BATCH_LIBS["yalps_milpdense"] = (MILPDENSE_LIB_PATH, {
+        "validate": (_I32, [_I32, _I32, _I32, _I32, _DOP, _DOP, _DOP, _DOP, _DOP, _I32, _VP, _I32, _VP]),
+        "solve": (_I32, [_VP, _I32, _I32, _I32, _I32, _DOP, _DOP, _DOP, _DOP, _DOP, _I32, _VP, _I32, _VP, _I32, C.c_double, C.c_double,
+                         _I32, C.c_double, C.c_double, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+        "overflowed": (_I32, [_VP, _VP, _I32]),
+        "solution": (_I32, [_VP, _I32, C.POINTER(_I32), C.POINTER(C.c_double), C.POINTER(_I32), _VP, _VP, _VP]),
+        "trace": (_I32, [_VP, _I32, C.POINTER(_I32)] + [_VP] * 8)})
+
+
+def milpdense_lib():
+    return _load_lib("yalps_milpdense")
+
+
+def milpdense_check(rc):
+    return _check("yalps_milpdense", rc)
+
+
+def _index_list(idx):
+    return np.ascontiguousarray(np.asarray(list(idx), np.int64), np.int32)
+
+
+def milpdense_validate(count, n, m_ub, m_eq, operands, integers=(), binaries=()):
+    """The host-only argument checks of yalps_milpdense_solve (raises NativeError with the reason); operands as
+    lpdense_validate takes them, integers / binaries: 0-based variable indices as the library takes them -- both ascending,
+    `integers` holding every binary variable.  No pointer is dereferenced."""
+    ops, ints, bins = _dense_operands(operands), _index_list(integers), _index_list(binaries)
+    milpdense_check(milpdense_lib().yalps_milpdense_validate(int(count), int(n), int(m_ub), int(m_eq), *(C.byref(o) for o in ops),
+                                                             ints.size, ints.ctypes.data, bins.size, bins.ctypes.data))
+
+
+class MilpDense:
+    """Batches of dense MILPs of one shape, operands and answers in device memory, every tree walked on the device
+    (yalps_milpdense_*).  Pointers are plain integers (a tensor's data_ptr()); nothing here imports torch.  Belongs to one
+    thread at a time."""
+
+    def __init__(self, device=0, stream=None):
+        self.handle = C.c_void_p()
+        milpdense_check(milpdense_lib().yalps_milpdense_create(device, C.c_void_p(stream) if stream is not None else None,
+                                                               C.byref(self.handle)))
+        self.shape, self.trace_cap = None, 0  # (count, width, root height, n_integers) of the last solve
+
+    def solve(self, count, n, m_ub, m_eq, operands, integers=(), binaries=(), maximize=False, precision=1e-8, max_pivots=8192.0,
+              check_cycles=False, tolerance=0.0, max_iterations=32768.0, trace_cap=0, x=None, objective=None, status=None,
+              nodes=None, node_pivots=None, root_pivots=None):
+        """operands = (c, A_ub, b_ub, A_eq, b_eq) as LpDense.solve takes them; integers / binaries: ascending 0-based variable
+        indices, `integers` the union of both sets; x / objective / status / nodes / node_pivots / root_pivots: device pointers
+        of contiguous float64 [count][n], float64 [count], int32 [count] and three int64 [count], or None.  The outputs are
+        complete on return.  Returns {"reruns", "launches", "overflows", "root_ms", "tree_ms", "epilogue_ms", "gpu_ms"}."""
+        ops, ints, bins = _dense_operands(operands), _index_list(integers), _index_list(binaries)
+        call = np.zeros(6, np.int64)
+        self.shape = None
+        milpdense_check(milpdense_lib().yalps_milpdense_solve(
+            self.handle, int(count), int(n), int(m_ub), int(m_eq), *(C.byref(o) for o in ops), ints.size, ints.ctypes.data, bins.size,
+            bins.ctypes.data, int(bool(maximize)), float(precision), float(max_pivots), int(bool(check_cycles)), float(tolerance),
+            float(max_iterations), int(trace_cap), x, objective, status, nodes, node_pivots, root_pivots, call.ctypes.data))
+        self.shape = (int(count), int(n) + 1, 1 + int(m_ub) + 2 * int(m_eq) + bins.size, ints.size)
+        self.trace_cap = int(trace_cap)
+        root, tree, epi = (call[k] / 1000.0 for k in (3, 4, 5))
+        return {"reruns": int(call[0]), "launches": int(call[1]), "overflows": int(call[2]), "root_ms": root, "tree_ms": tree,
+                "epilogue_ms": epi, "gpu_ms": root + tree + epi}
+
+    def overflowed(self):
+        """The trees of the last solve whose frontier outgrew the largest arena (their rows hold NaN and the status 5)."""
+        n = milpdense_check(milpdense_lib().yalps_milpdense_overflowed(self.handle, None, 0))
+        ids = np.empty(n, np.int32)
+        if n:
+            milpdense_check(milpdense_lib().yalps_milpdense_overflowed(self.handle, ids.ctypes.data, n))
+        return [int(i) for i in ids]
+
+    def _model(self, i):
+        if self.shape is None or not 0 <= i < self.shape[0]:
+            raise NativeError("MilpDense: no such MILP in the last solve: %r" % (i,))
+        return self.shape[1:]
+
+    def solution(self, i):
+        """(status name, result, height, col0, positionOfVariable, variableAtPosition) of MILP i of the last solve: the tree's
+        status and result and its best tableau, copied to the host."""
+        w, h0, ni = self._model(i)
+        cap = h0 + 2 * ni
+        col0, pos, var = np.empty(cap, np.float64), np.empty(w + cap, np.int32), np.empty(w + cap, np.int32)
+        st, res, h = C.c_int32(), C.c_double(), C.c_int32()
+        milpdense_check(milpdense_lib().yalps_milpdense_solution(self.handle, i, C.byref(st), C.byref(res), C.byref(h), col0.ctypes.data,
+                                                                 pos.ctypes.data, var.ctypes.data))
+        n = h.value
+        return STATUS_MILPTREE[st.value], res.value, n, col0[:n].copy(), pos[:w + n].copy(), var[:w + n].copy()
+
+    def trace(self, i):
+        """The first trace_cap nodes MILP i consumed, in pop order, as MilpTree.trace gives them."""
+        w, h0, ni = self._model(i)
+        cap, room = self.trace_cap, max(1, self.trace_cap * 2 * ni)
+        ev, res = np.empty(cap, np.float64), np.empty(cap, np.float64)
+        st, hg, piv, cnt = np.empty(cap, np.int32), np.empty(cap, np.int32), np.empty(cap, np.int64), C.c_int32()
+        sg, vr, vl = np.empty(room, np.int32), np.empty(room, np.int32), np.empty(room, np.float64)
+        milpdense_check(milpdense_lib().yalps_milpdense_trace(self.handle, i, C.byref(cnt), ev.ctypes.data, st.ctypes.data, res.ctypes.data,
+                                                              piv.ctypes.data, hg.ctypes.data, sg.ctypes.data, vr.ctypes.data, vl.ctypes.data))
+        out, c = [], 0
+        for k in range(cnt.value):
+            nc = int(hg[k]) - h0
+            out.append({"eval": float(ev[k]), "cuts": [(int(sg[c + q]), int(vr[c + q]), float(vl[c + q])) for q in range(nc)],
+                        "status": STATUS[st[k]], "result": float(res[k]), "n_pivots": int(piv[k]), "height": int(hg[k])})
+            c += nc
+        return out
+
+    def info(self):
+        """{"launches", "reruns", "overflows", "gpu_ms", "root_ms", "tree_ms", "epilogue_ms", "rerun_lps": [...], "rerun_trees":
+        [...], "kernels": [{kernel, class, lps | trees, grid, lds, pass, hist_cap[, aux | arena]}], "text"}"""
+        text = _info_text("yalps_milpdense", self.handle, first=1 << 14)
+        head, kernels = _info_lines(text)
+        ids = lambda key: [int(x) for x in head.get(key, "[]").strip("[]").split(",") if x]
+        out = {k: int(head.get(k, 0)) for k in ("launches", "reruns", "overflows")}
+        out.update({k + "_ms": int(head.get(k + "_us", 0)) / 1000.0 for k in ("gpu", "root", "tree", "epilogue")})
+        out.update(rerun_lps=ids("rerun_lps"), rerun_trees=ids("rerun_trees"), kernels=kernels, text=text)
+        return out
+
+    def close(self):
+        if self.handle:
+            milpdense_lib().yalps_milpdense_destroy(self.handle)
+            self.handle = C.c_void_p()

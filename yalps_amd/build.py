@@ -8,6 +8,7 @@
   yalps_amd/libyalps_lpwarm.so    variants of one LP from its optimal tableau (include/yalps_lpwarm.h) hipcc
   yalps_amd/libyalps_milptree.so  batches of MILPs, every tree walked on the device (include/yalps_milptree.h) hipcc
   yalps_amd/libyalps_lpdense.so   batches of dense LPs of one shape, device tensors in and out (include/yalps_lpdense.h) hipcc
+  yalps_amd/libyalps_milpdense.so batches of dense MILPs of one shape, device tensors in and out, trees walked on the device (include/yalps_milpdense.h) hipcc
   yalps_amd/napi/yalps_napi.node  thin N-API shim over the C ABI (optional)  g++
 
 The .so files are git-ignored but travel to the GPU box with the tree.
@@ -27,7 +28,7 @@ HIP_SRC = os.path.join(CSRC, "yalps_hip.hip")  # host side + C ABI + the launch-
 # the persistent kernels' instantiations, one translation unit per group: compiled side by side (the device compile of
 # ~40 register-heavy kernels in one unit took 2.5 minutes)
 HIP_UNITS = [HIP_SRC] + [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.startswith("persistent_") and f.endswith(".hip")]
-HIP_DEPS = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith((".cuh", ".inc", ".h")) and not f.startswith(("lp_batch", "lp_dense", "lp_variants", "lp_sens", "lp_warm", "milp_node", "milp_tree", "wg_queue"))]
+HIP_DEPS = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith((".cuh", ".inc", ".h")) and not f.startswith(("lp_batch", "lp_dense", "lp_variants", "lp_sens", "lp_warm", "milp_node", "milp_tree", "milp_dense", "wg_queue"))]
 # the batch library: one translation unit of its own around the shared workgroup loop, never linked into libyalps_hip.so
 LIB_LPBATCH = os.path.join(HERE, "libyalps_lpbatch.so")
 LPBATCH_SRC = os.path.join(CSRC, "lp_batch.hip")
@@ -57,13 +58,19 @@ LPWARM_HEADER = os.path.join(ROOT, "include", "yalps_lpwarm.h")
 # the tree library: the LP batch's root pass compiled again next to milp_tree_kernel, whose search rules the host shares
 LIB_MILPTREE = os.path.join(HERE, "libyalps_milptree.so")
 MILPTREE_SRC = os.path.join(CSRC, "milp_tree.hip")
-MILPTREE_DEPS = LPBATCH_DEPS + [os.path.join(CSRC, f) for f in ("milp_tree_kernel.cuh", "milp_tree_rules.cuh")] + [LPBATCH_HEADER]
+MILPTREE_DEPS = LPBATCH_DEPS + [os.path.join(CSRC, f) for f in ("milp_tree_kernel.cuh", "milp_tree_rules.cuh", "milp_tree_host.inc")] + [LPBATCH_HEADER]
 MILPTREE_HEADER = os.path.join(ROOT, "include", "yalps_milptree.h")
 # the dense library: operands and answers in device memory, one translation unit around the same workgroup loop
 LIB_LPDENSE = os.path.join(HERE, "libyalps_lpdense.so")
 LPDENSE_SRC = os.path.join(CSRC, "lp_dense.hip")
 LPDENSE_DEPS = [os.path.join(CSRC, "lp_dense_kernel.cuh")] + QUEUE_DEPS
 LPDENSE_HEADER = os.path.join(ROOT, "include", "yalps_lpdense.h")
+# the dense MILP library: a dense root pass, milp_tree_kernel compiled again on the tree pass both libraries share, and solution() on the device
+LIB_MILPDENSE = os.path.join(HERE, "libyalps_milpdense.so")
+MILPDENSE_SRC = os.path.join(CSRC, "milp_dense.hip")
+MILPDENSE_DEPS = [os.path.join(CSRC, f) for f in ("milp_dense_kernel.cuh", "milp_tree_kernel.cuh", "milp_tree_rules.cuh", "milp_tree_host.inc",
+                                                  "lp_batch_kernel.cuh")] + QUEUE_DEPS
+MILPDENSE_HEADER = os.path.join(ROOT, "include", "yalps_milpdense.h")
 OBJ_DIR = os.path.join(HERE, "build")
 HEADER = os.path.join(ROOT, "include", "yalps_hip.h")
 NAPI_SRC = os.path.join(HERE, "napi", "yalps_napi.cc")
@@ -119,7 +126,7 @@ def kernel_metadata(lib=LIB):
 # scratch and without accumulator registers, or not at all.  (Two instantiations that broke this rule computed wrong
 # rows on the GPU -- DESIGN.md 4.7 -- so the rule is part of the build, not of an optional test.)
 # ("batch_kernel" also matches libyalps_lpbatch.so's lp_batch_kernel.)
-NO_SCRATCH = ("lp_sens", "lp_dense", "lp_variants", "lp_warm", "milp_node_kernel", "milp_tree_kernel", "dshard_kernel", "dshard_select_kernel", "dshard_sweep_kernel", "small_kernel", "batch_kernel", "assemble", "resident_kernel", "resident2_kernel", "stream_kernel", "stream2_kernel", "stream3_kernel", "sweep_kernel")
+NO_SCRATCH = ("lp_sens", "lp_dense", "milp_dense_root_kernel", "milp_dense_solution_kernel", "lp_variants", "lp_warm", "milp_node_kernel", "milp_tree_kernel", "dshard_kernel", "dshard_select_kernel", "dshard_sweep_kernel", "small_kernel", "batch_kernel", "assemble", "resident_kernel", "resident2_kernel", "stream_kernel", "stream2_kernel", "stream3_kernel", "sweep_kernel")
 
 
 # resident2_kernel<T, J, R>: scalar registers spilled to lanes of vector registers (sgpr_spill_count), at most what each
@@ -153,7 +160,7 @@ def check_register_budgets(lib=LIB, min_resident=15):
                 bad.append("%s: sgpr_spill_count %s, bound %d" % (name, md.get("sgpr_spill_count"), RESIDENT2_SGPR_SPILLS[shape]))
         if any(tag in name for tag in NO_SCRATCH) and int(md["private_segment_fixed_size"]) != 0:
             bad.append("%s: private_segment_fixed_size %s (scratch)" % (name, md["private_segment_fixed_size"]))
-        queue = "lp_batch_kernel" in name or "milp_node_kernel" in name or "lp_variants_kernel" in name or "lp_sens_kernel" in name or "lp_warm_kernel" in name or "milp_tree_kernel" in name or "lp_dense_kernel" in name
+        queue = "lp_batch_kernel" in name or "milp_node_kernel" in name or "lp_variants_kernel" in name or "lp_sens_kernel" in name or "lp_warm_kernel" in name or "milp_tree_kernel" in name or "lp_dense_kernel" in name or "milp_dense_root_kernel" in name
         if queue and int(md["agpr_count"]) != 0:
             bad.append("%s: agpr_count %s" % (name, md["agpr_count"]))
         # its dynamic LDS block (tableau and pivot row, swept 16 bytes at a time) starts where the static LDS ends
@@ -264,6 +271,12 @@ def build_lpdense(force=False, verbose=False):
                              ("lp_dense_kernel",), force, verbose)
 
 
+def build_milpdense(force=False, verbose=False):
+    """libyalps_milpdense.so: milp_dense.hip alone."""
+    return build_single_unit(MILPDENSE_SRC, LIB_MILPDENSE, MILPDENSE_DEPS, MILPDENSE_HEADER,
+                             ("milp_dense_root_kernel", "milp_dense_solution_kernel", "milp_tree_kernel"), force, verbose)
+
+
 def build_napi(force=False, verbose=False):
     """The Node addon; skipped (returns None) where node's headers are absent."""
     inc = "/usr/include/node"
@@ -292,4 +305,5 @@ if __name__ == "__main__":
     print(build_lpwarm(force=True, verbose=True))
     print(build_milptree(force=True, verbose=True))
     print(build_lpdense(force=True, verbose=True))
+    print(build_milpdense(force=True, verbose=True))
     print(build_napi(force=True, verbose=True))

@@ -33,33 +33,19 @@ namespace {
 #include "lp_batch_host.inc"
 
 static_assert(YALPS_MILPTREE_MAX_BYTES == QUEUE_MAX_BYTES, "include/yalps_milptree.h");
-static_assert(MT_TIMEDOUT == YALPS_MILPTREE_TIMEDOUT && MT_HIST_FULL == WG_HISTORY_FULL && MT_OPTIMAL == YALPS_OPTIMAL &&
-                  MT_INFEASIBLE == YALPS_INFEASIBLE && sizeof(MtState) % sizeof(double) == 0 && NCLASS == 5,
-              "milp_tree_rules.cuh");
-const KernelTable<TreeLaunch> kTreeKernels = QUEUE_KERNEL_TABLE(milp_tree_kernel);
-constexpr int ARENA_FIRST = 128, ARENA_MAX = 1 << 16;
-constexpr long long ARENA_BYTES = 1ll << 31; // bound on the arena buffer of a pass that runs trees again (grid x stride)
+#include "milp_tree_host.inc"
+static_assert(TREE_TIMEDOUT == YALPS_MILPTREE_TIMEDOUT && TREE_OVERFLOW == YALPS_MILPTREE_OVERFLOW, "include/yalps_milptree.h");
 } // namespace
 
 #include "lp_batch_lib.inc"
 
-struct yalps_milptree {
+struct yalps_milptree : TreePass {
     yalps_lpbatch *lp = nullptr; // the root pass: device, stream, events, the kept root tableaux
-    QueueBufs q;
-    DevBuf tdesc, ints, globals, arena, nodebuf, d_used, d_best_h, d_trace;
-    int arena_first = ARENA_FIRST, arena_max = ARENA_MAX, grid = 0;
-    long long arena_bytes = ARENA_BYTES;
     // the last solve
-    std::vector<TreeDesc> trees;
     std::vector<int32_t> status, best_h, h_pos, h_var;
     std::vector<double> result, h_col0, h_trace;
     std::vector<long long> used, pivots;
-    int32_t trace_cap = 0;
-    // info
-    std::string info, lines;
-    std::vector<int32_t> rerun_ids;
-    int64_t launches = 0, overflows = 0;
-    double gpu_ms = 0.0;
+    std::string info;
 };
 
 namespace {
@@ -92,143 +78,6 @@ void info_close(yalps_milptree *b) {
     std::snprintf(head, sizeof head, "launches=%lld reruns=%zu overflows=%lld gpu_us=%lld rerun_trees=[", (long long)b->launches,
                   b->rerun_ids.size(), (long long)b->overflows, (long long)std::llround(b->gpu_ms * 1000.0));
     b->info = head + join_ids(b->rerun_ids) + "]\n" + b->lines;
-}
-
-// The tree pass: passes over the trees left until none ends with an internal code.  One pass is the launches of
-// plan_launches -- a tree counts as its largest possible node -- over the workgroups' arenas; a tree whose arena or whose
-// node's history was too short runs again, alone with the others of its kind, from its root with four times that room.
-int trees_impl(yalps_milptree *b, size_t n, const int32_t *checkCycles) {
-    yalps_lpbatch *lp = b->lp;
-    hipStream_t s = lp->stream;
-    const std::vector<TreeDesc> &D = b->trees;
-    const std::vector<LpDesc> &R = lp->descs;
-    QueueDevice dev = *lp; // (the class table as this handle runs it; the stream and the events are the root pass's)
-    if (b->grid > 0) {
-        dev.num_cus = 1;
-        for (int k = 0; k < NCLASS; k++) dev.per_cu[k] = b->grid;
-    }
-    std::vector<int32_t> todo(n);
-    for (size_t i = 0; i < n; i++) todo[i] = (int32_t)i;
-    std::vector<Launch> launches;
-    std::vector<int32_t> overflowed;
-    long long hist_cap = b->q.hist_first, arena_cap = std::max(2, b->arena_first);
-    bool grew = false; // this pass runs with an arena four times the last one's
-    // the trees of `todo` that ended with a full arena get the public status and leave the pass; the arena shrinks back
-    auto give_up_arena = [&]() {
-        std::vector<int32_t> keep;
-        for (int32_t i : todo) (b->q.h_status[(size_t)i] == MT_ARENA_FULL ? overflowed : keep).push_back(i);
-        todo.swap(keep);
-        arena_cap /= 4, grew = false;
-    };
-    for (int pass = 0; !todo.empty(); pass++) {
-        TreeGlobals G{};
-        size_t arena_doubles = 0, node_doubles = 0;
-        for (;;) { // the pass's launches and what they need; a grown arena beyond the byte bound is given up like one above the cap
-            if (int rc = plan_launches(dev, b->q, todo, [&](int32_t i, int *w, int *h) {
-                    return *w = R[(size_t)i].w, *h = R[(size_t)i].h + 2 * D[(size_t)i].nints, checkCycles[i] != 0;
-                }, hist_cap, launches))
-                return rc;
-            G = TreeGlobals{};
-            for (int32_t i : todo) {
-                const TreeDesc &d = D[(size_t)i];
-                const LpDesc &r = R[(size_t)i];
-                G.arena_stride[d.cls] = std::max<long long>(G.arena_stride[d.cls], (long long)mt_arena_doubles((int32_t)arena_cap, d.maxcuts));
-                if (d.cls == HBM_CLASS) {
-                    const long long hmax = r.h + 2 * d.nints;
-                    G.nodebuf_stride = std::max(G.nodebuf_stride, ((hmax + 1) & ~1ll) + ((r.w + hmax + 1) & ~1ll));
-                }
-            }
-            arena_doubles = node_doubles = 0;
-            for (const Launch &L : launches) {
-                if (!find_form(kTreeKernels, L.lanes, L.check, L.cls != HBM_CLASS))
-                    return fail(YALPS_E_ARG, "yalps_milptree: no kernel of " + std::to_string(L.lanes) + " lanes");
-                arena_doubles = std::max(arena_doubles, (size_t)L.grid * (size_t)G.arena_stride[L.cls]);
-                if (L.cls == HBM_CLASS) node_doubles = std::max(node_doubles, (size_t)L.grid * (size_t)G.nodebuf_stride);
-            }
-            if (!grew || sizeof(double) * arena_doubles <= (size_t)b->arena_bytes) break;
-            give_up_arena();
-            if (todo.empty()) break;
-        }
-        if (todo.empty()) break;
-        if (pass > 0) b->rerun_ids.insert(b->rerun_ids.end(), todo.begin(), todo.end());
-        if (int rc = ensure(b->arena, sizeof(double) * arena_doubles)) return rc;
-        if (int rc = ensure(b->nodebuf, sizeof(double) * node_doubles)) return rc;
-        G.roots = lp->desc.as<const LpDesc>();
-        G.root_tab = lp->q.tab.as<const double>();
-        G.root_col0 = lp->q.col0.as<const double>();
-        G.root_result = lp->q.result.as<const double>();
-        G.root_pos = lp->q.pos.as<const int32_t>();
-        G.root_var = lp->q.var.as<const int32_t>();
-        G.root_status = lp->q.status.as<const int32_t>();
-        G.tree = b->tdesc.as<const TreeDesc>();
-        G.ints = b->ints.as<const int32_t>();
-        G.status = b->q.status.as<int32_t>();
-        G.result = b->q.result.as<double>();
-        G.used = b->d_used.as<long long>();
-        G.pivots = b->q.pivots.as<long long>();
-        G.best_h = b->d_best_h.as<int32_t>();
-        G.col0 = b->q.col0.as<double>();
-        G.pos = b->q.pos.as<int32_t>();
-        G.var = b->q.var.as<int32_t>();
-        G.trace = b->trace_cap > 0 ? b->d_trace.as<double>() : nullptr;
-        G.arena = b->arena.as<double>();
-        G.nodebuf = b->nodebuf.as<double>();
-        G.trace_cap = b->trace_cap;
-        G.arena_cap = (int32_t)arena_cap;
-        std::vector<TreeGlobals> per(launches.size(), G); // (one per launch: its part of the order, its counter, its stride)
-        for (size_t nl = 0; nl < launches.size(); nl++) {
-            const Launch &L = launches[nl];
-            per[nl].order = b->q.order.as<const int32_t>() + L.at;
-            per[nl].count = (int32_t)L.items.size();
-            per[nl].counter = b->q.counters.as<unsigned int>() + nl;
-            per[nl].ws = b->q.ws.as<double>();
-            per[nl].ws_stride = (long long)L.stride;
-            per[nl].hist = b->q.hist.as<int32_t>();
-            per[nl].hist_cap = hist_cap;
-        }
-        if (int rc = ensure(b->globals, sizeof(TreeGlobals) * per.size())) return rc;
-        HIP_TRY(hipMemcpyAsync(b->globals.p, per.data(), sizeof(TreeGlobals) * per.size(), hipMemcpyHostToDevice, s));
-        HIP_TRY(hipStreamSynchronize(s)); // (`per` is on this frame)
-        HIP_TRY(hipEventRecord(lp->ev0, s));
-        for (size_t nl = 0; nl < launches.size(); nl++) {
-            const Launch &L = launches[nl];
-            const KernelForm<TreeLaunch> *form = find_form(kTreeKernels, L.lanes, L.check, L.cls != HBM_CLASS);
-            TreeLaunch a{b->globals.as<const TreeGlobals>() + nl};
-            form->fn<<<dim3(L.grid), dim3(form->lanes), L.shmem, s>>>(a);
-            HIP_TRY(hipGetLastError());
-            char line[288];
-            std::snprintf(line, sizeof line, "launch=%lld pass=%d kernel=%s class=%d trees=%zu grid=%d lds=%zu hist_cap=%lld arena=%lld\n",
-                          (long long)b->launches++, pass, form_name(kTreeKernels, *form).c_str(), L.cls, L.items.size(), L.grid, L.shmem,
-                          L.check ? hist_cap : 0ll, arena_cap);
-            if (b->lines.size() < ((size_t)1 << 20)) b->lines += line;
-        }
-        HIP_TRY(hipEventRecord(lp->ev1, s));
-        HIP_TRY(hipMemcpyAsync(b->q.h_status.data(), b->q.status.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, lp->ev0, lp->ev1));
-        b->gpu_ms += ms;
-        std::vector<int32_t> again;
-        bool arena_full = false, hist_full = false;
-        for (int32_t i : todo) {
-            const int32_t st = b->q.h_status[(size_t)i];
-            if (st == MT_ARENA_FULL)
-                arena_full = true, again.push_back(i);
-            else if (st == MT_HIST_FULL)
-                hist_full = true, again.push_back(i);
-            else if (st < 0 || st > YALPS_MILPTREE_TIMEDOUT)
-                return fail(YALPS_E_DEVICE, "milp_tree_kernel did not report a result for tree " + std::to_string(i));
-        }
-        if (hist_full) hist_cap *= 4;
-        if (hist_full && hist_cap > (1ll << 28)) return fail(YALPS_E_NOMEM, "yalps_milptree_solve: checkCycles history beyond 2^28 pivots");
-        todo.swap(again);
-        grew = arena_full;
-        if (arena_full) arena_cap *= 4;
-        if (arena_full && arena_cap > b->arena_max) give_up_arena(); // above the cap
-    }
-    for (int32_t i : overflowed) b->q.h_status[(size_t)i] = YALPS_MILPTREE_OVERFLOW; // (the device's word for it is internal)
-    b->overflows = (int64_t)overflowed.size();
-    return 0;
 }
 
 int solve_trees(yalps_milptree *b, int32_t count, const int32_t *width, const int32_t *height, const int64_t *off, const int32_t *row,
@@ -294,7 +143,8 @@ int solve_trees(yalps_milptree *b, int32_t count, const int32_t *width, const in
     if (int rc = reset_status(b->q, s, n)) return rc;
     HIP_TRY(hipStreamSynchronize(s)); // (D is on this frame until it moves into the handle)
     b->trees = std::move(D);
-    if (int rc = trees_impl(b, n, checkCycles)) return rc;
+    const TreeRoots roots{b->lp, b->lp->descs.data(), b->lp->desc.as<const LpDesc>(), &b->lp->q};
+    if (int rc = trees_impl(b, roots, n, [&](int32_t i) { return checkCycles[i] != 0; }, "yalps_milptree")) return rc;
 
     b->status = b->q.h_status;
     b->result.assign(n, NAN);
@@ -357,8 +207,7 @@ void yalps_milptree_destroy(yalps_milptree *b) {
     if (!b) return;
     (void)hipSetDevice(b->lp->device);
     if (b->lp->stream) (void)hipStreamSynchronize(b->lp->stream);
-    release(b->q);
-    release({&b->tdesc, &b->ints, &b->globals, &b->arena, &b->nodebuf, &b->d_used, &b->d_best_h, &b->d_trace});
+    release(*b);
     lp_destroy(b->lp);
     delete b;
 }
@@ -411,26 +260,7 @@ int32_t yalps_milptree_trace(yalps_milptree *b, int32_t i, int32_t *count_out, d
     const bool gone = b->status[(size_t)i] == YALPS_MILPTREE_OVERFLOW;
     const int32_t cnt = gone ? 0 : (int32_t)std::min<long long>(b->used[(size_t)i], b->trace_cap);
     if (count_out) *count_out = cnt;
-    size_t c = 0;
-    for (int32_t k = 0; k < cnt; k++) {
-        const double *e = b->h_trace.data() + d.trace_off + (size_t)k * (4 + 2 * (size_t)d.maxcuts);
-        int32_t sh[2];
-        int64_t piv;
-        std::memcpy(&piv, e + 2, sizeof piv);
-        std::memcpy(sh, e + 3, sizeof sh);
-        if (eval) eval[k] = e[0];
-        if (result) result[k] = e[1];
-        if (pivots) pivots[k] = piv;
-        if (status) status[k] = sh[0];
-        if (height) height[k] = sh[1];
-        for (int32_t q = 0; q < sh[1] - h0; q++, c++) {
-            int32_t sv[2];
-            std::memcpy(sv, e + 5 + 2 * q, sizeof sv);
-            if (cut_sign) cut_sign[c] = sv[0];
-            if (cut_var) cut_var[c] = sv[1];
-            if (cut_val) cut_val[c] = e[4 + 2 * q];
-        }
-    }
+    tree_trace_out(b->h_trace.data() + d.trace_off, d.maxcuts, cnt, h0, eval, status, result, pivots, height, cut_sign, cut_var, cut_val);
     return 0;
 }
 

@@ -1,5 +1,6 @@
 """linprog_batch: batches of small dense LPs straight from torch tensors on the GPU (libyalps_lpdense.so), with their dual
-solutions on request, and linprog_objective: the optimal value as a differentiable torch function.
+solutions on request; linprog_objective: the optimal value as a differentiable torch function; milp_batch: batches of small
+dense MILPs the same way, every branch-and-cut tree walked on the device (libyalps_milpdense.so).
 
 This module imports torch; `import yalps_amd` does not.  linprog_batch computes nothing with torch: it supplies the device
 pointers, the strides and the stream, and allocates the outputs.  linprog_objective's backward is a handful of torch
@@ -20,16 +21,19 @@ from . import _native
 
 LinprogBatch = namedtuple("LinprogBatch", ("x", "objective", "status", "pivots"))
 LinprogDuals = namedtuple("LinprogDuals", LinprogBatch._fields + ("ineqlin", "eqlin", "reduced_costs"))
+MilpBatchResult = namedtuple("MilpBatchResult", ("x", "objective", "status", "nodes", "node_pivots", "root_pivots"))
 
-STATUS_NAMES = _native.STATUS[:4]  # the YALPS_* codes 0..3 as solve() spells them
+STATUS_NAMES = _native.STATUS[:5]  # the YALPS_* codes 0..3 as solve() spells them, and 4, "timedout", which only a MILP ends with
 
 _handles = {}  # (device index, stream) -> LpDense: stream, events and device buffers are kept and grown between calls
+_milp_handles = {}  # (device index, stream) -> MilpDense, kept likewise
+_fallbacks = {}  # device index -> MilpBatch: the lockstep driver, for trees that overflowed on the device
 _lock = threading.Lock()  # (a handle belongs to one thread at a time)
 
 
 def status_names(status):
-    """The strings solve() uses -- "optimal", "infeasible", "unbounded", "cycled" -- for a status tensor (or any iterable
-    of the codes)."""
+    """The strings solve() uses -- "optimal", "infeasible", "unbounded", "cycled", and for milp_batch "timedout" -- for a
+    status tensor (or any iterable of the codes)."""
     codes = status.tolist() if hasattr(status, "tolist") else list(status)
     return [STATUS_NAMES[int(k)] for k in codes]
 
@@ -37,19 +41,20 @@ def status_names(status):
 @atexit.register
 def _close_handles():
     with _lock:
-        for h in _handles.values():
-            h.close()
-        _handles.clear()
+        for table in (_handles, _milp_handles, _fallbacks):
+            for h in table.values():
+                h.close()
+            table.clear()
 
 
-def _operand(name, t, ndim):
+def _operand(name, t, ndim, who="linprog_batch"):
     """A float64 tensor of `ndim` dimensions or one more (the batch in front): (tensor, B or None, its own shape)."""
     if not isinstance(t, torch.Tensor):
-        raise TypeError("linprog_batch: %s must be a torch.Tensor, not %s" % (name, type(t).__name__))
+        raise TypeError("%s: %s must be a torch.Tensor, not %s" % (who, name, type(t).__name__))
     if t.dtype != torch.float64:
-        raise TypeError("linprog_batch: %s is %s; only torch.float64 is solved" % (name, t.dtype))
+        raise TypeError("%s: %s is %s; only torch.float64 is solved" % (who, name, t.dtype))
     if t.dim() not in (ndim, ndim + 1):
-        raise ValueError("linprog_batch: %s has %d dimensions, expected %d or %d (with the batch in front)" % (name, t.dim(), ndim, ndim + 1))
+        raise ValueError("%s: %s has %d dimensions, expected %d or %d (with the batch in front)" % (who, name, t.dim(), ndim, ndim + 1))
     batched = t.dim() == ndim + 1
     return t, (t.shape[0] if batched else None), tuple(t.shape[1:] if batched else t.shape)
 
@@ -60,6 +65,46 @@ def _strides(t, batched, matrix):
         return None
     s = t.stride()
     return (t.data_ptr(), s[0] if batched else 0, s[-2] if matrix else s[-1], s[-1] if matrix else 0)
+
+
+def _call_operands(who, c, A_ub, b_ub, A_eq, b_eq, check_size):
+    """The five operands of a call, checked: (B, n, m_ub, m_eq, device, the five (ptr, batch, row, col) tuples, the tensors in
+    that order with None where a side has no rows, which of them carry the batch dimension).  check_size(n, m_ub, m_eq)
+    raises where the shape is above the call's limit; it runs after the shapes are known to agree and before the devices are
+    looked at."""
+    c, cB, (n,) = _operand("c", c, 1, who)
+    batch = {"c": cB}
+    sides = []
+    for tag, A, b in (("ub", A_ub, b_ub), ("eq", A_eq, b_eq)):
+        if (A is None) != (b is None):
+            raise ValueError("%s: A_%s and b_%s come together" % (who, tag, tag))
+        if A is None:
+            sides.append((None, None, 0))
+            continue
+        A, batch["A_" + tag], (m, An) = _operand("A_" + tag, A, 2, who)
+        b, batch["b_" + tag], (bm,) = _operand("b_" + tag, b, 1, who)
+        if An != n:
+            raise ValueError("%s: A_%s has %d columns, c has %d variables" % (who, tag, An, n))
+        if bm != m:
+            raise ValueError("%s: A_%s has %d rows, b_%s has %d" % (who, tag, m, tag, bm))
+        sides.append((A, b, m))
+    sizes = {k: v for k, v in batch.items() if v is not None}
+    if len(set(sizes.values())) > 1:
+        raise ValueError("%s: the operands disagree about B: %s" % (who, ", ".join("%s has %d" % kv for kv in sizes.items())))
+    B = next(iter(sizes.values()), 1)
+    (A_ub, b_ub, m_ub), (A_eq, b_eq, m_eq) = sides
+    check_size(n, m_ub, m_eq)
+    given = (c, A_ub, b_ub, A_eq, b_eq)
+    tensors = [t for t in given if t is not None]
+    if any(not t.is_cuda for t in tensors):
+        raise ValueError("%s: the operands are read on the GPU where they lie: a CPU tensor was given "
+                         "(move it with .cuda(), or use solve_many for models in host memory)" % who)
+    device = c.device
+    if any(t.device != device for t in tensors):
+        raise ValueError("%s: the operands lie on different devices: %s" % (who, sorted({str(t.device) for t in tensors})))
+    batched = tuple(batch.get(k) is not None for k in ("c", "A_ub", "b_ub", "A_eq", "b_eq"))
+    operands = tuple(_strides(t, batched[k], k in (1, 3)) for k, t in enumerate(given))
+    return B, n, m_ub, m_eq, device, operands, given, batched
 
 
 def linprog_batch(c, A_ub=None, b_ub=None, A_eq=None, b_eq=None, *, maximize=False, precision=1e-8, max_pivots=8192,
@@ -103,42 +148,13 @@ def linprog_batch(c, A_ub=None, b_ub=None, A_eq=None, b_eq=None, *, maximize=Fal
     bit, the "dual" and "reduced_cost" sensitivity() reports for the equivalent model.
 
     See the module's docstring for the loading rule: torch first."""
-    c, cB, (n,) = _operand("c", c, 1)
-    batch = {"c": cB}
-    sides = []
-    for tag, A, b in (("ub", A_ub, b_ub), ("eq", A_eq, b_eq)):
-        if (A is None) != (b is None):
-            raise ValueError("linprog_batch: A_%s and b_%s come together" % (tag, tag))
-        if A is None:
-            sides.append((None, None, 0))
-            continue
-        A, batch["A_" + tag], (m, An) = _operand("A_" + tag, A, 2)
-        b, batch["b_" + tag], (bm,) = _operand("b_" + tag, b, 1)
-        if An != n:
-            raise ValueError("linprog_batch: A_%s has %d columns, c has %d variables" % (tag, An, n))
-        if bm != m:
-            raise ValueError("linprog_batch: A_%s has %d rows, b_%s has %d" % (tag, m, tag, bm))
-        sides.append((A, b, m))
-    sizes = {k: v for k, v in batch.items() if v is not None}
-    if len(set(sizes.values())) > 1:
-        raise ValueError("linprog_batch: the operands disagree about B: %s" % ", ".join("%s has %d" % kv for kv in sizes.items()))
-    B = next(iter(sizes.values()), 1)
-    (A_ub, b_ub, m_ub), (A_eq, b_eq, m_eq) = sides
-    w, h = n + 1, 1 + m_ub + 2 * m_eq
-    if 8 * w * h > _native.LPDENSE_MAX_BYTES:
-        raise ValueError("linprog_batch: a tableau of %d x %d doubles (%d bytes) is above the batch limit of %d bytes; "
-                         "solve() is the route for such models" % (h, w, 8 * w * h, _native.LPDENSE_MAX_BYTES))
-    tensors = [t for t in (c, A_ub, b_ub, A_eq, b_eq) if t is not None]
-    if any(not t.is_cuda for t in tensors):
-        raise ValueError("linprog_batch: the operands are read on the GPU where they lie: a CPU tensor was given "
-                         "(move it with .cuda(), or use solve_many for models in host memory)")
-    device = c.device
-    if any(t.device != device for t in tensors):
-        raise ValueError("linprog_batch: the operands lie on different devices: %s" % sorted({str(t.device) for t in tensors}))
+    def size(n, m_ub, m_eq):
+        w, h = n + 1, 1 + m_ub + 2 * m_eq
+        if 8 * w * h > _native.LPDENSE_MAX_BYTES:
+            raise ValueError("linprog_batch: a tableau of %d x %d doubles (%d bytes) is above the batch limit of %d bytes; "
+                             "solve() is the route for such models" % (h, w, 8 * w * h, _native.LPDENSE_MAX_BYTES))
 
-    operands = (_strides(c, batch["c"] is not None, False),
-                _strides(A_ub, batch.get("A_ub") is not None, True), _strides(b_ub, batch.get("b_ub") is not None, False),
-                _strides(A_eq, batch.get("A_eq") is not None, True), _strides(b_eq, batch.get("b_eq") is not None, False))
+    B, n, m_ub, m_eq, device, operands = _call_operands("linprog_batch", c, A_ub, b_ub, A_eq, b_eq, size)[:6]
     x = torch.empty((B, n), dtype=torch.float64, device=device)
     objective = torch.empty((B,), dtype=torch.float64, device=device)
     status = torch.empty((B,), dtype=torch.int32, device=device)
@@ -232,3 +248,123 @@ def linprog_objective(c, A_ub=None, b_ub=None, A_eq=None, b_eq=None, *, maximize
     expanded = [None if t is None else (t if name in sizes else t.unsqueeze(0).expand(B, *t.shape)) for name, t in given.items()]
     objective, *rest = _Objective.apply(options, *expanded)
     return objective, LinprogDuals(rest[0], objective.detach(), *rest[1:])
+
+
+def _solve_on_host(device, rows, given, batched, B, ints, bins, maximize, options, out):
+    """The trees `rows` of a milp_batch call through the lockstep driver (_native.MilpBatch.solve), as solve.milptree_solve
+    sends its overflows: their operands are gathered on the device and copied to the host, their tableaux built there
+    (milp_dense.packed_milp), and x / objective / status / nodes written into the output tensors `out`.  node_pivots of such
+    a row is -1: the lockstep driver does not count the pivots of the nodes it consumes."""
+    from . import milp_dense
+    idx = torch.tensor(rows, dtype=torch.int64, device=device)
+    host = []
+    for t, has_batch in zip(given, batched):
+        if t is None:
+            host.append(None)
+        else:
+            host.append((t.index_select(0, idx) if has_batch else t).cpu().numpy())
+    pick = lambda k, a, has_batch: None if a is None else (a[k] if has_batch else a)
+    milps = [milp_dense.packed_milp(tuple(pick(k, a, hb) for a, hb in zip(host, batched)), ints, bins, maximize, options)
+             for k in range(len(rows))]
+    batch = _fallbacks.get(device.index)
+    if batch is None:
+        batch = _fallbacks[device.index] = _native.MilpBatch(device.index)
+    statuses, results, used, _, _ = batch.solve(milps)
+    n = out.x.shape[1]
+    sign = 1.0 if maximize else -1.0
+    xs, objs = [], []
+    for k, (st, res) in enumerate(zip(statuses, results)):
+        _, col0, pos, var = batch.solution(k)
+        x, obj = milp_dense.dense_solution(col0, pos, var, st, float(res), sign, options["precision"], n)
+        xs.append(x)
+        objs.append(obj)
+    dev = lambda a, dtype: torch.as_tensor(a, dtype=dtype).to(device)
+    import numpy as np
+    out.x.index_copy_(0, idx, dev(np.stack(xs), torch.float64))
+    out.objective.index_copy_(0, idx, dev(np.array(objs, np.float64), torch.float64))
+    out.status.index_copy_(0, idx, dev(np.array([_native.STATUS.index(s) for s in statuses], np.int32), torch.int32))
+    out.nodes.index_copy_(0, idx, dev(np.asarray(used, np.int64), torch.int64))
+    out.node_pivots.index_fill_(0, idx, -1)
+
+
+def milp_batch(c, A_ub=None, b_ub=None, A_eq=None, b_eq=None, *, integers=(), binaries=(), maximize=False, precision=1e-8,
+               max_pivots=8192, check_cycles=False, tolerance=0.0, max_iterations=32768, stats=None):
+    """Solves B dense MILPs of one shape in one call, from device tensors to device tensors, every branch-and-cut tree walked
+    on the device:
+
+        minimize (or maximize=True: maximize)  c . x   subject to   A_ub x <= b_ub,   A_eq x = b_eq,   x >= 0,
+        x[j] integer for j in integers,   x[j] in {0, 1} for j in binaries
+
+    The operands -- shapes, broadcasting (an operand without the batch dimension is read with a batch stride of 0), strides,
+    dtype, device -- the stream ("torch's current stream") and the loading rule ("torch first") are linprog_batch's.
+    integers and binaries are HOST sequences of 0-based variable indices, or True for all variables, shared by the whole
+    batch: binaries changes the tableau's height, and one call has one shape.  A variable named in both counts once.
+    precision, max_pivots, check_cycles, tolerance and max_iterations are the reference's options, for the whole call.  The
+    device reads no clock, so there is no timeout: it is the reference's default, +inf.
+
+    Returns MilpBatchResult(x [B, n] float64, objective [B] float64, status [B] int32, nodes [B] int64, node_pivots [B]
+    int64, root_pivots [B] int64) on the inputs' device: nodes is the number of branch-and-cut nodes the search consumed,
+    node_pivots the sum of their pivots, root_pivots the root LP's.  status_names(status) spells the codes as solve() does;
+    code 4 is "timedout" (max_iterations ran out with nodes left).
+
+    The contract.  For finite data, row i is what solve() returns for the equivalent model -- linprog_batch's, plus
+    "integers" / "binaries" naming those variables -- with includeZeroVariables read off the dense x: "optimal", and
+    "timedout" with a solution, give the values of the best tableau (those not above precision are +0.0) and objective =
+    solve()'s result; "unbounded" gives +0.0 but +inf at the unbounded variable and objective = +-inf; "infeasible",
+    "cycled" and "timedout" without a solution give NaN everywhere.  For any data it is what the reference's `simplex`,
+    `branchAndCut` and `solution` give on the tableau as built: tableauModel's -- linprog_batch's rows, then one row per
+    binary variable in ascending index (column 0 and the variable's column 1.0), so width n + 1 and height
+    1 + m_ub + 2 m_eq + len(binaries).
+
+    With no integer variable at all solve() never enters branchAndCut, and neither does this call: x, objective, status and
+    root_pivots are linprog_batch's x, objective, status and pivots bit for bit, and nodes = node_pivots = 0.
+
+    What crosses PCIe per call: upwards the call's description, the two index lists and 152 bytes of descriptors per
+    MILP; downwards one int32 per MILP per pass (a pass: the root LPs, the trees, and once more for those trees whose
+    frontier or cycle history outgrew its first allocation and run again with four times the room).  A tree whose frontier
+    outgrows the largest arena (65536 open nodes) cannot finish on the device: those rows, and only those, are gathered on
+    the device, copied to the host and solved by the lockstep driver (_native.MilpBatch), and their x, objective, status and
+    nodes are written into the output tensors; their node_pivots is -1, which that driver does not count.
+
+    Raises TypeError / ValueError, before the library is touched, for what linprog_batch refuses, for a duplicate or an
+    out-of-range index in integers or binaries, and for a largest possible node -- 8 (n + 1) (height + 2 n_integers) bytes,
+    two cuts per integer variable -- above 4 MiB (solve() is the route for such models).  stats (a dict, optional) receives
+    "launches", "reruns", "overflows", "kernels" and "gpu_ms" of the call (and "root_ms", "tree_ms", "epilogue_ms", its parts).
+
+    See the module's docstring for the loading rule: torch first."""
+    from . import milp_dense
+    sets = {}
+
+    def size(n, m_ub, m_eq):
+        ints, bins = sets["ints"], sets["bins"] = milp_dense.integer_sets(n, integers, binaries)
+        nbytes = milp_dense.largest_node_bytes(n, m_ub, m_eq, len(ints), len(bins))
+        if nbytes > _native.MILPDENSE_MAX_BYTES:
+            raise ValueError("milp_batch: the largest possible node, %d x %d doubles (%d bytes: %d rows and two cuts for each of %d "
+                             "integer variables), is above the batch limit of %d bytes; solve() is the route for such models"
+                             % (nbytes // (8 * (n + 1)), n + 1, nbytes, 1 + m_ub + 2 * m_eq + len(bins), len(ints), _native.MILPDENSE_MAX_BYTES))
+
+    B, n, m_ub, m_eq, device, operands, given, batched = _call_operands("milp_batch", c, A_ub, b_ub, A_eq, b_eq, size)
+    ints, bins = sets["ints"], sets["bins"]
+    out = MilpBatchResult(torch.empty((B, n), dtype=torch.float64, device=device), torch.empty((B,), dtype=torch.float64, device=device),
+                          torch.empty((B,), dtype=torch.int32, device=device), *(torch.empty((B,), dtype=torch.int64, device=device) for _ in range(3)))
+    ptr = lambda t: t.data_ptr() if t.numel() else None
+    with torch.cuda.device(device), _lock:  # (the library selects the handle's device; torch's choice comes back afterwards)
+        stream = torch.cuda.current_stream(device).cuda_stream or 1  # (the default stream's handle is 0: hipStreamLegacy names it)
+        key = (device.index, stream)
+        handle = _milp_handles.get(key)
+        if handle is None:
+            handle = _milp_handles[key] = _native.MilpDense(device.index, stream=stream)
+        call = handle.solve(B, n, m_ub, m_eq, operands, integers=ints, binaries=bins, maximize=maximize, precision=precision,
+                            max_pivots=max_pivots, check_cycles=check_cycles, tolerance=tolerance, max_iterations=max_iterations,
+                            x=ptr(out.x), objective=ptr(out.objective), status=ptr(out.status), nodes=ptr(out.nodes),
+                            node_pivots=ptr(out.node_pivots), root_pivots=ptr(out.root_pivots))
+        over = handle.overflowed() if call["overflows"] else []
+        if stats is not None:
+            info = handle.info()
+            stats.update(launches=info["launches"], reruns=info["reruns"], overflows=len(over), kernels=info["kernels"],
+                         gpu_ms=call["gpu_ms"], root_ms=call["root_ms"], tree_ms=call["tree_ms"], epilogue_ms=call["epilogue_ms"])
+        if over:
+            options = {"precision": float(precision), "maxPivots": float(max_pivots), "checkCycles": bool(check_cycles),
+                       "tolerance": float(tolerance), "timeout": float("inf"), "maxIterations": float(max_iterations)}
+            _solve_on_host(device, over, given, batched, B, ints, bins, bool(maximize), options, out)
+    return out
