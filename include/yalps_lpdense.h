@@ -25,6 +25,23 @@
  * Pointers and streams belong to the HIP runtime that made them.  A process that holds two HIP runtimes (a framework
  * that brings its own, loaded after this library) must hand over only what THIS library's runtime knows:
  * yalps_lpdense_solve asks it about every operand and output pointer and refuses what it does not know.
+ *
+ * Bounds (yalps_lpdense_solve_bounds).  lb, a vector operand of n elements per LP, means x >= lb and REPLACES x >= 0 for the
+ * call (negative entries are legal; every entry is read); ub, read only at the n_upper variables upper_idx names (host memory,
+ * ascending, shared by the call), means x[j] <= ub[j].  Either may be absent (a NULL descriptor).  The tableau as built, with
+ * x = lb + x' substituted on the device:
+ *   shift_sum(a, l) = sum of a[j] * l[j], every product rounded on its own, added in ONE order that depends on nothing but a
+ *     and l: 64 partial sums p[k], each +0.0 plus the products of the columns j = k (mod 64) in ascending j; then
+ *     p[k] += p[k + s] for k < s, s = 32, 16, 8, 4, 2, 1; the value is p[0].
+ *   row 1 + i, column 0:  b_ub[i] - shift_sum(A_ub[i], lb); equality k: b_eq[k] - shift_sum(A_eq[k], lb) and, in the second row of
+ *     the pair, its IEEE negation.  One subtraction; without lb none at all (not b - 0.0).  Coefficients, row 0 and cell (0, 0)
+ *     are untouched.
+ *   n_upper bound rows below the equality rows, in ascending variable index: column 0 = ub[j] - lb[j] (ub[j] without lb), 1.0 in
+ *     the variable's column, +0.0 elsewhere: tableauModel's row of a constraint {"max": ...} in which variable j alone has a
+ *     coefficient, 1.  Width n + 1, height 1 + m_ub + 2 m_eq + n_upper, which is what YALPS_LPDENSE_MAX_BYTES bounds.
+ *   read-out: x = x' + lb, one addition per element whatever the status (NaN stays NaN, +inf stays +inf);
+ *     objective = objective' + shift_sum(c, lb) with the caller's c, one addition after the rounding.
+ * Free variables are out of scope: an lb entry of -inf is taken as it lies in memory, like every other value.
  */
 #ifndef YALPS_LPDENSE_H
 #define YALPS_LPDENSE_H
@@ -68,6 +85,15 @@ void yalps_lpdense_destroy(yalps_lpdense *d);
 int32_t yalps_lpdense_validate(int32_t count, int32_t n, int32_t m_ub, int32_t m_eq, const yalps_lpdense_operand *c,
                                const yalps_lpdense_operand *A_ub, const yalps_lpdense_operand *b_ub,
                                const yalps_lpdense_operand *A_eq, const yalps_lpdense_operand *b_eq);
+
+/* yalps_lpdense_validate with the bounds of yalps_lpdense_solve_bounds, host only: the size limit with the height that counts
+ * the n_upper bound rows, a negative stride of lb / ub (NULL descriptor: absent), a NULL pointer of one that has elements,
+ * n_upper > 0 without ub, an index of upper_idx (host memory) outside 0 .. n-1 or not ascending. */
+int32_t yalps_lpdense_validate_bounds(int32_t count, int32_t n, int32_t m_ub, int32_t m_eq, const yalps_lpdense_operand *c,
+                                      const yalps_lpdense_operand *A_ub, const yalps_lpdense_operand *b_ub,
+                                      const yalps_lpdense_operand *A_eq, const yalps_lpdense_operand *b_eq,
+                                      const yalps_lpdense_operand *lb, const yalps_lpdense_operand *ub, int32_t n_upper,
+                                      const int32_t *upper_idx);
 
 /* Solves LPs 0 .. count-1.  maximize != 0: maximise c . x, else minimise.  precision / maxPivots (may be +Infinity) /
  * checkCycles hold for the whole call.  keep_tableaux != 0 also keeps every final matrix on the device for
@@ -113,6 +139,25 @@ int32_t yalps_lpdense_solve_duals(yalps_lpdense *d, int32_t count, int32_t n, in
                                   int32_t checkCycles, int32_t keep_tableaux, double *x_out, double *objective_out,
                                   int32_t *status_out, int64_t *pivots_out, double *ineqlin_out, double *eqlin_out,
                                   double *reduced_out, float *gpu_ms_out);
+
+/* yalps_lpdense_solve_duals (which is this call with lb, ub and upper_out NULL and n_upper 0, and writes the bits it wrote
+ * before) with bounds; see "Bounds" at the top for the tableau and the read-out.  lb / ub: operand descriptors or NULL;
+ * upper_idx: HOST memory, n_upper ascending indices (copied before the call returns); lb, ub and upper_out are DEVICE pointers,
+ * looked up and refused by name like the others.  With either descriptor given the call runs lp_dense_bounds_kernel
+ * (libyalps_lpdense_bounds.so, which this library links); with neither, the boundless kernels.
+ *   upper_out[count][n_upper]  optimal: s * y(1 + m_ub + 2 m_eq + t) + 0.0, ineqlin's formula on bound row t; else NaN
+ * reduced_out is then the marginal of x >= lb (scipy's lower.marginals), upper_out that of x <= ub (upper.marginals).  For
+ * every optimal LP, up to rounding, reduced = c - A_ub^T ineqlin - A_eq^T eqlin - scatter(upper) and
+ * objective = ineqlin . b_ub + eqlin . b_eq + upper . ub + reduced . lb.  yalps_lpdense_solution and yalps_lpdense_tableau give
+ * the taller tableau: height 1 + m_ub + 2 m_eq + n_upper. */
+int32_t yalps_lpdense_solve_bounds(yalps_lpdense *d, int32_t count, int32_t n, int32_t m_ub, int32_t m_eq,
+                                   const yalps_lpdense_operand *c, const yalps_lpdense_operand *A_ub,
+                                   const yalps_lpdense_operand *b_ub, const yalps_lpdense_operand *A_eq,
+                                   const yalps_lpdense_operand *b_eq, const yalps_lpdense_operand *lb,
+                                   const yalps_lpdense_operand *ub, int32_t n_upper, const int32_t *upper_idx, int32_t maximize,
+                                   double precision, double maxPivots, int32_t checkCycles, int32_t keep_tableaux, double *x_out,
+                                   double *objective_out, int32_t *status_out, int64_t *pivots_out, double *ineqlin_out,
+                                   double *eqlin_out, double *reduced_out, double *upper_out, float *gpu_ms_out);
 
 /* LP i of the last solve, copied to the HOST (for tests and debugging): what solution() reads -- column 0 (height
  * doubles) and both permutations (width + height int32 each).  NULL pointers are skipped. */

@@ -1,0 +1,156 @@
+"""Helpers of tests/test_lp_dense_bounds_model.py and tests/test_lp_dense_bounds.py (TEST INFRASTRUCTURE): the bounds of
+linprog_batch(lb=, ub=, upper=) restated in plain numpy, beside tests/_np_dense.py, whose restatement of the boundless call
+they extend.
+
+  shift_sum          sum of a[j] * l[j] in THE canonical order: every product rounded on its own; 64 partial sums p[k], each
+                     starting from +0.0 and adding the products of the columns j = k (mod 64) in ascending j; then
+                     p[k] += p[k + s] for k < s, s = 32, 16, 8, 4, 2, 1; the value is p[0].  It depends on nothing but a and l.
+  upper_set          `upper` (True: all n; else 0-based indices) as the ascending tuple of the call, refusing what the call refuses
+  bounded_tableau    what DenseJob<true>::fill writes: dense_tableau with column 0 of every operand row moved by the row's
+                     shift_sum with lb (one subtraction; none at all without lb), and below the equality rows one row per
+                     listed variable, ascending: ub[j] - lb[j] (or ub[j]) in column 0, 1.0 in the variable's column, +0.0 elsewhere
+  explicit_operands  the route a caller had: the unit rows stacked under A_ub, b shifted with shift_sum
+  explicit_rows      the row order of explicit_operands' dense_tableau that gives bounded_tableau (the unit rows go last)
+  equivalent_model   the model in x' = x - lb: u0.. {"max"}, e0.. {"equal"}, then h<j> {"max": ub[j] - lb[j]} in which variable j
+                     alone has a coefficient, 1
+  bounded_solution   what DenseJob<true>::after writes: dense_solution, then x = x' + lb and objective = objective' +
+                     shift_sum(c, lb), one addition each, whatever the status
+  bounded_marginals  (ineqlin, eqlin, reduced, upper): dense_marginals' formulas, `upper` being ineqlin's on the bound rows
+  identity_residuals how far an optimal answer is from
+                         reduced = c - A_ub^T ineqlin - A_eq^T eqlin - scatter(upper)
+                         objective = ineqlin . b_ub + eqlin . b_eq + upper . ub + reduced . lb
+Shares no code with the product.
+"""
+import numpy as np
+
+from tests import _np_dense as ND
+from tests import _np_dense_duals as DD
+
+NAN = float("nan")
+LANES = 64
+
+
+def shift_sum(a, l):
+    a, l = np.asarray(a, np.float64).reshape(-1), np.asarray(l, np.float64).reshape(-1)
+    assert a.size == l.size
+    p = [np.float64(0.0)] * LANES
+    with np.errstate(all="ignore"):
+        for j in range(a.size):
+            p[j % LANES] = p[j % LANES] + a[j] * l[j]
+        s = LANES // 2
+        while s:
+            for k in range(s):
+                p[k] = p[k] + p[k + s]
+            s //= 2
+    return np.float64(p[0])
+
+
+def upper_set(n, upper, has_ub=True):
+    if upper is True:
+        return tuple(range(n)) if has_ub else ()
+    idx = tuple(int(j) for j in upper)
+    if len(set(idx)) != len(idx) or any(not 0 <= j < n for j in idx):
+        raise ValueError("upper: duplicate or out-of-range index")
+    return tuple(sorted(idx))
+
+
+def bounded_tableau(c, A_ub=None, b_ub=None, A_eq=None, b_eq=None, lb=None, ub=None, upper=True, maximize=False):
+    n, m_ub, m_eq = ND.shape_of(c, A_ub, b_ub, A_eq, b_eq)
+    idx = upper_set(n, upper, ub is not None)
+    w, h0 = n + 1, 1 + m_ub + 2 * m_eq
+    m = np.zeros((h0 + len(idx), w), np.float64)
+    m[:h0] = ND.dense_tableau(c, A_ub, b_ub, A_eq, b_eq, maximize).reshape(h0, w)
+    with np.errstate(all="ignore"):
+        if lb is not None:
+            for i in range(m_ub):
+                m[1 + i, 0] = np.float64(b_ub[i]) - shift_sum(np.asarray(A_ub, np.float64).reshape(m_ub, n)[i], lb)
+            for k in range(m_eq):
+                v = np.float64(b_eq[k]) - shift_sum(np.asarray(A_eq, np.float64).reshape(m_eq, n)[k], lb)
+                m[1 + m_ub + 2 * k, 0], m[2 + m_ub + 2 * k, 0] = v, -v
+        for t, j in enumerate(idx):
+            m[h0 + t, 0] = np.float64(ub[j]) - np.float64(lb[j]) if lb is not None else np.float64(ub[j])
+            m[h0 + t, 1 + j] = 1.0
+    return m.ravel()
+
+
+def explicit_operands(c, A_ub=None, b_ub=None, A_eq=None, b_eq=None, lb=None, ub=None, upper=True):
+    """(c, A_ub', b_ub', A_eq, b_eq') of the boundless LP in x' = x - lb that a caller had to build: len(upper) unit rows under
+    A_ub, every right-hand side moved by shift_sum."""
+    n, m_ub, m_eq = ND.shape_of(c, A_ub, b_ub, A_eq, b_eq)
+    idx = upper_set(n, upper, ub is not None)
+    A = np.zeros((m_ub + len(idx), n), np.float64)
+    b = np.zeros(m_ub + len(idx), np.float64)
+    with np.errstate(all="ignore"):
+        for i in range(m_ub):
+            A[i] = np.asarray(A_ub, np.float64).reshape(m_ub, n)[i]
+            b[i] = np.float64(b_ub[i]) - shift_sum(A[i], lb) if lb is not None else b_ub[i]
+        for t, j in enumerate(idx):
+            A[m_ub + t, j] = 1.0
+            b[m_ub + t] = np.float64(ub[j]) - np.float64(lb[j]) if lb is not None else ub[j]
+        be = None
+        if m_eq:
+            Ae = np.asarray(A_eq, np.float64).reshape(m_eq, n)
+            be = np.array([np.float64(b_eq[k]) - shift_sum(Ae[k], lb) if lb is not None else b_eq[k] for k in range(m_eq)], np.float64)
+    rows = len(idx) + m_ub
+    return np.asarray(c, np.float64), (A if rows else None), (b if rows else None), A_eq, be
+
+
+def explicit_rows(m_ub, m_eq, k):
+    """Row r of bounded_tableau is row explicit_rows(...)[r] of dense_tableau(*explicit_operands(...))."""
+    return [0] + list(range(1, 1 + m_ub)) + list(range(1 + m_ub + k, 1 + m_ub + k + 2 * m_eq)) + list(range(1 + m_ub, 1 + m_ub + k))
+
+
+def equivalent_model(c, A_ub=None, b_ub=None, A_eq=None, b_eq=None, lb=None, ub=None, upper=True, maximize=False):
+    n, m_ub, m_eq = ND.shape_of(c, A_ub, b_ub, A_eq, b_eq)
+    idx = upper_set(n, upper, ub is not None)
+    ec, eA, eb, _, ebe = explicit_operands(c, A_ub, b_ub, A_eq, b_eq, lb, ub, upper)
+    model = ND.equivalent_model(ec, None if not m_ub else eA[:m_ub], None if not m_ub else eb[:m_ub], A_eq, ebe, maximize)
+    for t, j in enumerate(idx):
+        model["constraints"]["h%d" % j] = {"max": float(eb[m_ub + t])}
+        model["variables"]["x%d" % j]["h%d" % j] = 1.0
+    return model
+
+
+def bounded_solution(col0, pos, var, status, result, sign, precision, c, lb=None):
+    n = len(c)
+    x, objective = ND.dense_solution(col0, pos, var, status, result, sign, precision, n)
+    if lb is not None:
+        with np.errstate(all="ignore"):
+            x = x + np.asarray(lb, np.float64)
+            objective = float(np.float64(objective) + shift_sum(c, lb))
+    return x, objective
+
+
+def bounded_marginals(matrix, pos, status, n, m_ub, m_eq, k, sign):
+    """(ineqlin[m_ub], eqlin[m_eq], reduced[n], upper[k]) from the final (1 + m_ub + 2 m_eq + k) x (n + 1) matrix; NaN rows unless
+    the LP ended optimal."""
+    if status != "optimal":
+        return tuple(np.full(s, NAN) for s in (m_ub, m_eq, n, k))
+    ineqlin, eqlin, reduced = DD.dense_marginals(matrix, pos, n, m_ub, m_eq, sign)
+    w, first = n + 1, 1 + m_ub + 2 * m_eq
+    row0, s = np.asarray(matrix, np.float64)[:w], np.float64(sign)
+    upper = np.zeros(k, np.float64)
+    for t in range(k):
+        p = int(pos[w + first + t])
+        upper[t] = s * np.float64(-DD.cost(row0, p) if p < w else 0.0) + 0.0
+    return ineqlin, eqlin, reduced, upper
+
+
+def identity_residuals(lp, lb, ub, idx, objective, ineqlin, eqlin, reduced, upper):
+    """(|objective - (ineqlin . b_ub + eqlin . b_eq + upper . ub + reduced . lb)|,
+    max |reduced - (c - A_ub^T ineqlin - A_eq^T eqlin - scatter(upper))|) of one optimal LP."""
+    c, A_ub, b_ub, A_eq, b_eq = lp
+    n, m_ub, m_eq = ND.shape_of(*lp)
+    value, rc = 0.0, np.asarray(c, np.float64).copy()
+    if m_ub:
+        value += float(np.dot(ineqlin, b_ub))
+        rc -= np.asarray(A_ub, np.float64).reshape(m_ub, n).T @ ineqlin
+    if m_eq:
+        value += float(np.dot(eqlin, b_eq))
+        rc -= np.asarray(A_eq, np.float64).reshape(m_eq, n).T @ eqlin
+    for t, j in enumerate(idx):
+        value += float(upper[t] * ub[j])
+        rc[j] -= upper[t]
+    if lb is not None:
+        value += float(np.dot(reduced, lb))
+    return abs(objective - value), float(np.abs(reduced - rc).max()) if n else 0.0

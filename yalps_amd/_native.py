@@ -76,6 +76,7 @@ LPDENSE_LIB_PATH = os.environ.get("YALPS_LPDENSE_LIB") or os.path.join(HERE, "li
 SYMBOLS_LPDENSE = (
     "yalps_lpdense_last_error", "yalps_lpdense_create", "yalps_lpdense_destroy", "yalps_lpdense_validate", "yalps_lpdense_solve",
     "yalps_lpdense_solve_duals", "yalps_lpdense_solution", "yalps_lpdense_tableau", "yalps_lpdense_info",
+    "yalps_lpdense_validate_bounds", "yalps_lpdense_solve_bounds",
 )
 LPDENSE_MAX_BYTES = 4 << 20  # YALPS_LPDENSE_MAX_BYTES
 MILPDENSE_LIB_PATH = os.environ.get("YALPS_MILPDENSE_LIB") or os.path.join(HERE, "libyalps_milpdense.so")
@@ -973,6 +974,9 @@ _BATCH_LIBS["yalps_lpdense"] = (LPDENSE_LIB_PATH, {
                          _VP, _VP, _VP, _VP, C.POINTER(C.c_float)]),
         "solve_duals": (_I32, [_VP, _I32, _I32, _I32, _I32, _DOP, _DOP, _DOP, _DOP, _DOP, _I32, C.c_double, C.c_double, _I32, _I32,
                                _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.POINTER(C.c_float)]),
+        "validate_bounds": (_I32, [_I32, _I32, _I32, _I32, _DOP, _DOP, _DOP, _DOP, _DOP, _DOP, _DOP, _I32, _VP]),
+        "solve_bounds": (_I32, [_VP, _I32, _I32, _I32, _I32, _DOP, _DOP, _DOP, _DOP, _DOP, _DOP, _DOP, _I32, _VP, _I32, C.c_double,
+                                C.c_double, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.POINTER(C.c_float)]),
         "solution": (_I32, [_VP, _I32, _VP, _VP, _VP]), "tableau": (_I32, [_VP, _I32, _VP])})
 
 
@@ -997,6 +1001,21 @@ def lpdense_validate(count, n, m_ub, m_eq, operands):
     lpdense_check(lpdense_lib().yalps_lpdense_validate(int(count), int(n), int(m_ub), int(m_eq), *(C.byref(o) for o in ops)))
 
 
+def _dense_bounds(lb, ub, upper):
+    """(lb descriptor or None, ub descriptor or None, n_upper, the int32 index array) of the bounds arguments."""
+    idx = np.ascontiguousarray(upper, np.int32).reshape(-1)
+    return (None if lb is None else C.byref(DenseOperand(*lb)), None if ub is None else C.byref(DenseOperand(*ub)), int(idx.size), idx)
+
+
+def lpdense_validate_bounds(count, n, m_ub, m_eq, operands, lb=None, ub=None, upper=()):
+    """The host-only argument checks of yalps_lpdense_solve_bounds: lpdense_validate's with the height that counts the
+    len(upper) bound rows, plus lb / ub ((ptr, batch, row, col) or None: absent) and the index list."""
+    ops = _dense_operands(operands)
+    lbp, ubp, k, idx = _dense_bounds(lb, ub, upper)
+    lpdense_check(lpdense_lib().yalps_lpdense_validate_bounds(int(count), int(n), int(m_ub), int(m_eq), *(C.byref(o) for o in ops),
+                                                              lbp, ubp, k, idx.ctypes.data))
+
+
 class LpDense:
     """Batches of dense LPs of one shape, operands and answers in device memory (yalps_lpdense_*).  Pointers are plain
     integers (a tensor's data_ptr()); nothing here imports torch.  Belongs to one thread at a time."""
@@ -1008,22 +1027,33 @@ class LpDense:
         self.shape = None  # (count, width, height) of the last solve
 
     def solve(self, count, n, m_ub, m_eq, operands, maximize=False, precision=1e-8, max_pivots=8192.0, check_cycles=False,
-              keep_tableaux=False, x=None, objective=None, status=None, pivots=None, ineqlin=None, eqlin=None, reduced=None):
+              keep_tableaux=False, x=None, objective=None, status=None, pivots=None, ineqlin=None, eqlin=None, reduced=None,
+              lb=None, ub=None, upper=(), upper_out=None):
         """operands = (c, A_ub, b_ub, A_eq, b_eq), each (device pointer, batch, row, col strides in doubles) or None where it
         has no element; x / objective / status / pivots: device pointers of contiguous float64 [count][n], float64 [count],
         int32 [count], int64 [count], or None; ineqlin / eqlin / reduced: the marginals (yalps_lpdense_solve_duals), device
         pointers of contiguous float64 [count][m_ub], [count][m_eq], [count][n], or None -- with all three None the call is
-        yalps_lpdense_solve.  The outputs are complete on return.  Returns gpu_ms."""
+        yalps_lpdense_solve.  lb / ub: (device pointer, batch, row, col) of the bounds x >= lb and x[j] <= ub[j] for the
+        ascending indices j of `upper` (a host sequence), or None; upper_out: device pointer of contiguous float64
+        [count][len(upper)], the bound rows' marginals, or None -- with lb or ub given the call is yalps_lpdense_solve_bounds, and
+        the tableau is len(upper) rows taller.  The outputs are complete on return.  Returns gpu_ms."""
         ops = _dense_operands(operands)
         ms = C.c_float()
         self.shape = None
         head = (self.handle, int(count), int(n), int(m_ub), int(m_eq), *(C.byref(o) for o in ops), int(bool(maximize)), float(precision),
                 float(max_pivots), int(bool(check_cycles)), int(bool(keep_tableaux)), x, objective, status, pivots)
-        if ineqlin is None and eqlin is None and reduced is None:
+        k = 0
+        if lb is not None or ub is not None:
+            lbp, ubp, k, idx = _dense_bounds(lb, ub, upper)
+            lpdense_check(lpdense_lib().yalps_lpdense_solve_bounds(*head[:10], lbp, ubp, k, idx.ctypes.data, *head[10:], ineqlin, eqlin,
+                                                                   reduced, upper_out, C.byref(ms)))
+        elif len(upper) or upper_out is not None:
+            raise NativeError("LpDense.solve: upper / upper_out without lb or ub")
+        elif ineqlin is None and eqlin is None and reduced is None:
             lpdense_check(lpdense_lib().yalps_lpdense_solve(*head, C.byref(ms)))
         else:
             lpdense_check(lpdense_lib().yalps_lpdense_solve_duals(*head, ineqlin, eqlin, reduced, C.byref(ms)))
-        self.shape = (int(count), int(n) + 1, 1 + int(m_ub) + 2 * int(m_eq))
+        self.shape = (int(count), int(n) + 1, 1 + int(m_ub) + 2 * int(m_eq) + k)
         return ms.value
 
     def _check(self, i):

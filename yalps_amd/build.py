@@ -64,6 +64,9 @@ MILPTREE_HEADER = os.path.join(ROOT, "include", "yalps_milptree.h")
 LIB_LPDENSE = os.path.join(HERE, "libyalps_lpdense.so")
 LPDENSE_SRC = os.path.join(CSRC, "lp_dense.hip")
 LPDENSE_DEPS = [os.path.join(CSRC, "lp_dense_kernel.cuh")] + QUEUE_DEPS
+# its kernels with bounds, a code object of their own that libyalps_lpdense.so links: the boundless library's holds the six forms it always held
+LIB_LPDENSE_BOUNDS = os.path.join(HERE, "libyalps_lpdense_bounds.so")
+LPDENSE_BOUNDS_SRC = os.path.join(CSRC, "lp_dense_bounds.hip")
 LPDENSE_HEADER = os.path.join(ROOT, "include", "yalps_lpdense.h")
 # the dense MILP library: a dense root pass, milp_tree_kernel compiled again on the tree pass both libraries share, and solution() on the device
 LIB_MILPDENSE = os.path.join(HERE, "libyalps_milpdense.so")
@@ -160,7 +163,7 @@ def check_register_budgets(lib=LIB, min_resident=15):
                 bad.append("%s: sgpr_spill_count %s, bound %d" % (name, md.get("sgpr_spill_count"), RESIDENT2_SGPR_SPILLS[shape]))
         if any(tag in name for tag in NO_SCRATCH) and int(md["private_segment_fixed_size"]) != 0:
             bad.append("%s: private_segment_fixed_size %s (scratch)" % (name, md["private_segment_fixed_size"]))
-        queue = "lp_batch_kernel" in name or "milp_node_kernel" in name or "lp_variants_kernel" in name or "lp_sens_kernel" in name or "lp_warm_kernel" in name or "milp_tree_kernel" in name or "lp_dense_kernel" in name or "milp_dense_root_kernel" in name
+        queue = "lp_dense_bounds_kernel" in name or "lp_batch_kernel" in name or "milp_node_kernel" in name or "lp_variants_kernel" in name or "lp_sens_kernel" in name or "lp_warm_kernel" in name or "milp_tree_kernel" in name or "lp_dense_kernel" in name or "milp_dense_root_kernel" in name
         if queue and int(md["agpr_count"]) != 0:
             bad.append("%s: agpr_count %s" % (name, md["agpr_count"]))
         # its dynamic LDS block (tableau and pivot row, swept 16 bytes at a time) starts where the static LDS ends
@@ -208,16 +211,18 @@ def build_hip(force=False, verbose=False, stamps=False):
     return lib_out
 
 
-def build_single_unit(src, out, deps, header, kernels, force=False, verbose=False):
+def build_single_unit(src, out, deps, header, kernels, force=False, verbose=False, link=()):
     """A library of one translation unit (it includes common.cuh / wg_simplex.cuh itself), same flags as the main library;
-    `kernels`: the kernel names its code object must hold."""
+    `kernels`: the kernel names its code object must hold; `link`: libraries beside `out` that it links (found again through
+    an rpath of $ORIGIN)."""
     if not force and not _stale(out, header, src, *deps):
         return out
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     os.makedirs(OBJ_DIR, exist_ok=True)
     obj = os.path.join(OBJ_DIR, os.path.basename(src)[:-4] + ".o")
     for cmd in ([hipcc, *HIPCC_FLAGS, "-c", "-o", obj, src],
-                [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out + ".tmp", obj]):
+                [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out + ".tmp", obj,
+                 *(["-L" + os.path.dirname(out), "-Wl,-rpath,$ORIGIN"] if link else []), *("-l:" + os.path.basename(l) for l in link)]):
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.run(cmd, check=True)
@@ -266,9 +271,12 @@ def build_milptree(force=False, verbose=False):
 
 
 def build_lpdense(force=False, verbose=False):
-    """libyalps_lpdense.so: lp_dense.hip alone."""
-    return build_single_unit(LPDENSE_SRC, LIB_LPDENSE, LPDENSE_DEPS, LPDENSE_HEADER,
-                             ("lp_dense_kernel",), force, verbose)
+    """libyalps_lpdense_bounds.so: lp_dense_bounds.hip alone, the six lp_dense_bounds_kernel forms (they pass the same register
+    budget: "lp_dense" is under NO_SCRATCH); then libyalps_lpdense.so: lp_dense.hip alone, linking it."""
+    bounds = build_single_unit(LPDENSE_BOUNDS_SRC, LIB_LPDENSE_BOUNDS, LPDENSE_DEPS, LPDENSE_HEADER,
+                               ("lp_dense_bounds_kernel",), force, verbose)
+    return build_single_unit(LPDENSE_SRC, LIB_LPDENSE, LPDENSE_DEPS + [bounds], LPDENSE_HEADER,
+                             ("lp_dense_kernel",), force, verbose, link=(bounds,))
 
 
 def build_milpdense(force=False, verbose=False):

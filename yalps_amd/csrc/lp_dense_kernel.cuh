@@ -22,6 +22,21 @@
 // In between: the same work queue (wg_queue.cuh), wg_simplex unchanged, the same outputs.
 // The call's description lies in device memory (one DenseCall per call), not in the kernel's arguments: five operands with
 // three 64-bit strides each would sit in scalar registers through the solve.
+//
+// Bounds (DenseJob<true>, lp_dense_bounds_kernel; the boundless job and its six kernels are compiled without a line of this):
+// x >= lb replaces x >= 0 by the substitution x = lb + x', and x[j] <= ub[j] for the n_upper listed variables adds n_upper rows
+// below the equality rows, so h = 1 + m_ub + 2 * m_eq + n_upper.
+//   shift_sum(a, l), THE order: every product a[j] * l[j] rounded on its own; lane k of ONE wave adds the products of the
+//          columns j = k (mod 64) in ascending j to +0.0; then p += shfl_down(p, s) for s = 32, 16, 8, 4, 2, 1; lane 0 holds it.
+//          It depends on nothing but a and l: not on T, the LDS / HBM / aux form, wg_unit_lanes, strides or the batch.
+//   fill   with lb: a pass of its own in front of the row loop, one wave per operand row, parks the row's shift_sum in the
+//          row's rhs slot (both slots of an equality); one barrier; the row loop's column-0 lane then writes b - rhs[r], one
+//          subtraction (its negation in the second row of an equality).  Without lb nothing is subtracted.  Coefficients and
+//          row 0 are untouched.  Bound row t: ub[j] - lb[j] (or ub[j]) in column 0, 1.0 in column j = upper_idx[t], else +0.0:
+//          generated, not read.
+//   after  x = x' + lb, one addition per element whatever the status; objective = objective' + shift_sum(c, lb), recomputed
+//          here by wave 0 (lane 0 of the workgroup writes it), one addition after the rounding; upper[t] = ineqlin's
+//          formula on bound row t.
 // ------------------------------------------------------------------------------------------
 struct DenseOperand {
     const double *p;              // element (i, r, c) at p[i * sb + r * sr + c * sc]; a vector has sc = 0 and is indexed by r
@@ -38,6 +53,11 @@ struct DenseCall {
     double *ineqlin;              // [count][m_ub]  the marginals: nullptr where the call does not ask for them
     double *eqlin;                // [count][m_eq]
     double *reduced;              // [count][n]
+    // bounds: read by DenseJob<true> only (behind everything the boundless kernels read, whose offsets stay)
+    DenseOperand lb, ub;          // (batch, row) = (i, j), sc unused; p = nullptr: absent
+    int32_t n_upper;              // bound rows; ub is read at upper_idx[0 .. n_upper) only
+    const int32_t *upper_idx;     // device, ascending
+    double *upper;                // [count][n_upper]  the bound rows' marginals, or nullptr
 };
 
 struct DenseLaunch : QueueLaunch {
@@ -93,6 +113,25 @@ __device__ __forceinline__ void dense_marginals(const DenseCall *d, const int32_
     }
 }
 
+// shift_sum(a, l) over n columns, the canonical order (above): every lane of a wave calls it, lane 0's value is the sum
+__device__ __forceinline__ double dense_shift_sum(const double *a, long long sa, const double *l, long long sl, int n) {
+    double p = 0.0;
+    for (int j = threadIdx.x & 63; j < n; j += 64) p = p + a[(long long)j * sa] * l[(long long)j * sl];
+    for (int s = 32; s > 0; s >>= 1) p = p + __shfl_down(p, s, 64);
+    return p;
+}
+
+// Row i of the bound rows' marginals: upper[t] = s * y(1 + m_ub + 2 m_eq + t) + 0.0, ineqlin's formula; not optimal: NaN
+template <int T>
+__device__ __forceinline__ void dense_upper_marginals(const DenseCall *d, const int32_t *pos, const double *mat, long long i,
+                                                      int w, bool optimal) {
+    const int k = d->n_upper, first = 1 + d->m_ub + 2 * d->m_eq;
+    const double sign = d->sign, nan = __longlong_as_double(0x7ff8000000000000ll);
+    double *out = d->upper + i * k;
+    for (int t = threadIdx.x; t < k; t += T) out[t] = optimal ? sign * dense_row_dual(mat, pos, w, first + t) + 0.0 : nan;
+}
+
+template <bool BOUNDS>
 struct DenseJob : QueueJobBase {
     const DenseLaunch &L;
     const DenseCall *d;
@@ -100,7 +139,7 @@ struct DenseJob : QueueJobBase {
     __device__ __forceinline__ explicit DenseJob(const DenseLaunch &launch) : L(launch), d(launch.call), idx(0) {}
     __device__ __forceinline__ QueueItem item(int i) {
         idx = i;
-        const int w = d->n + 1, h = 1 + d->m_ub + 2 * d->m_eq, heven = (h + 1) & ~1;
+        const int w = d->n + 1, h = 1 + d->m_ub + 2 * d->m_eq + (BOUNDS ? d->n_upper : 0), heven = (h + 1) & ~1;
         return QueueItem{w, h, (long long)((size_t)i * heven), (long long)((size_t)i * ((size_t)w + h)), d->aux_hbm};
     }
     __device__ __forceinline__ double precision() const { return d->precision; }
@@ -114,10 +153,48 @@ struct DenseJob : QueueJobBase {
         const double sign = d->sign;
         // a group of Uc lanes per row, the lanes along its columns (lane `lp` of a row, where it exists, writes column 0)
         const int Uc = wg_unit_lanes(lp + 1, T), cu0 = tid % Uc, cg0 = tid / Uc, CG = T / Uc;
+        const double *lb = nullptr, *ub = nullptr;
+        long long lbs = 0, ubs = 0;
+        int h0 = h; // the first bound row
+        if constexpr (BOUNDS) {
+            h0 = h - d->n_upper;
+            lbs = d->lb.sr, ubs = d->ub.sr;
+            if (d->lb.p) lb = d->lb.p + i * d->lb.sb;
+            if (d->ub.p) ub = d->ub.p + i * d->ub.sb;
+            if (lb) { // the shifts: one wave per operand row, parked in the row's rhs slot
+                const int m_eq = d->m_eq;
+                for (int q = tid >> 6; q < m_ub + m_eq; q += T >> 6) {
+                    const bool eq = q >= m_ub;
+                    const DenseOperand &A = eq ? d->A_eq : d->A_ub;
+                    const int k = eq ? q - m_ub : q;
+                    const double v = dense_shift_sum(A.p + i * A.sb + (long long)k * A.sr, A.sc, lb, lbs, n);
+                    if ((tid & 63) == 0) {
+                        if (eq) rhs[1 + m_ub + 2 * k] = rhs[2 + m_ub + 2 * k] = v;
+                        else rhs[1 + q] = v;
+                    }
+                }
+                __syncthreads();
+            }
+        }
         for (int r = cg0; r < h; r += CG) {
             const double *a, *b; // the row's coefficients, and its right-hand side
             long long sc;
             bool neg = false;
+            if constexpr (BOUNDS) {
+                if (r >= h0) { // a bound row: nothing but column 0 is read
+                    const int j = d->upper_idx[r - h0];
+                    double *dst = mat + (size_t)r * lp;
+                    for (int c = cu0; c <= lp; c += Uc) {
+                        if (c == lp) {
+                            const double u = ub[(long long)j * ubs];
+                            rhs[r] = lb ? u - lb[(long long)j * lbs] : u;
+                        } else {
+                            dst[c] = c == j ? 1.0 : 0.0;
+                        }
+                    }
+                    continue;
+                }
+            }
             if (r == 0) {
                 a = d->c.p + i * d->c.sb;
                 sc = d->c.sr;
@@ -136,6 +213,13 @@ struct DenseJob : QueueJobBase {
             double *dst = mat + (size_t)r * lp;
             for (int c = cu0; c <= lp; c += Uc) {
                 if (c == lp) {
+                    if constexpr (BOUNDS) {
+                        if (lb && r != 0) {
+                            const double v = *b - rhs[r];
+                            rhs[r] = neg ? -v : v;
+                            continue;
+                        }
+                    }
                     rhs[r] = r == 0 ? 0.0 : (neg ? -*b : *b);
                 } else if (c >= n) {
                     dst[c] = 0.0;
@@ -162,29 +246,60 @@ struct DenseJob : QueueJobBase {
         const double sign = d->sign, p = d->precision;
         const double nan = __longlong_as_double(0x7ff8000000000000ll);
         double objective = nan;
+        const double *lb = nullptr; // x = x' + lb, whatever the status
+        long long lbs = 0;
+        if constexpr (BOUNDS) {
+            lbs = d->lb.sr;
+            if (d->lb.p) lb = d->lb.p + i * d->lb.sb;
+        }
         if (status == YALPS_OPTIMAL) {
             const int32_t *pos = L.pos + it.perm_off;
             for (int j = tid; j < n; j += T) {
                 const int row = pos[j + 1] - w;
                 const double v = row >= 0 ? rhs[row] : 0.0;
-                x[j] = v > p ? round_to_precision(v, p) : 0.0;
+                const double xv = v > p ? round_to_precision(v, p) : 0.0;
+                if constexpr (BOUNDS) {
+                    x[j] = lb ? xv + lb[(long long)j * lbs] : xv;
+                } else {
+                    x[j] = xv;
+                }
             }
             objective = -sign * L.result[i];
         } else if (status == YALPS_UNBOUNDED) {
             const int32_t *var = L.var + it.perm_off;
             const int at = (int)L.result[i];
             const int v = (unsigned)at < (unsigned)(w + it.h) ? var[at] - 1 : -1;
-            for (int j = tid; j < n; j += T) x[j] = j == v ? INFINITY : 0.0;
+            if constexpr (BOUNDS) {
+                for (int j = tid; j < n; j += T) {
+                    const double xv = j == v ? INFINITY : 0.0;
+                    x[j] = lb ? xv + lb[(long long)j * lbs] : xv;
+                }
+            } else {
+                for (int j = tid; j < n; j += T) x[j] = j == v ? INFINITY : 0.0;
+            }
             objective = sign * INFINITY;
         } else {
-            for (int j = tid; j < n; j += T) x[j] = nan;
+            for (int j = tid; j < n; j += T) x[j] = nan; // (NaN + lb[j] is NaN)
+        }
+        if constexpr (BOUNDS) {
+            // (wave 0 alone computes the constant, whole: the condition is the same for all lanes of a wave; the caller's c, not sign * c)
+            if (lb && tid < 64) objective = objective + dense_shift_sum(d->c.p + i * d->c.sb, d->c.sr, lb, lbs, n);
         }
         if (tid == 0) d->objective[i] = objective;
         if (d->ineqlin || d->eqlin || d->reduced) dense_marginals<T>(d, L.pos + it.perm_off, mat, i, w, status == YALPS_OPTIMAL);
+        if constexpr (BOUNDS) {
+            if (d->upper) dense_upper_marginals<T>(d, L.pos + it.perm_off, mat, i, w, status == YALPS_OPTIMAL);
+        }
     }
 };
 
 template <int T, bool CHECK, bool LDS>
 __global__ __launch_bounds__(T) void lp_dense_kernel(DenseLaunch L) {
-    wg_queue<T, CHECK, LDS>(L, DenseJob(L));
+    wg_queue<T, CHECK, LDS>(L, DenseJob<false>(L));
+}
+
+// the same queue with bounds; instantiated by lp_dense_bounds.hip alone (libyalps_lpdense_bounds.so)
+template <int T, bool CHECK, bool LDS>
+__global__ __launch_bounds__(T) void lp_dense_bounds_kernel(DenseLaunch L) {
+    wg_queue<T, CHECK, LDS>(L, DenseJob<true>(L));
 }

@@ -1,5 +1,5 @@
-"""linprog_batch: batches of small dense LPs straight from torch tensors on the GPU (libyalps_lpdense.so), with their dual
-solutions on request; linprog_objective: the optimal value as a differentiable torch function; milp_batch: batches of small
+"""linprog_batch: batches of small dense LPs straight from torch tensors on the GPU (libyalps_lpdense.so), with variable
+bounds lb <= x <= ub shifted and built on the device, and with their dual solutions on request; linprog_objective: the optimal value as a differentiable torch function; milp_batch: batches of small
 dense MILPs the same way, every branch-and-cut tree walked on the device (libyalps_milpdense.so).
 
 This module imports torch; `import yalps_amd` does not.  linprog_batch computes nothing with torch: it supplies the device
@@ -21,6 +21,7 @@ from . import _native
 
 LinprogBatch = namedtuple("LinprogBatch", ("x", "objective", "status", "pivots"))
 LinprogDuals = namedtuple("LinprogDuals", LinprogBatch._fields + ("ineqlin", "eqlin", "reduced_costs"))
+LinprogBoundDuals = namedtuple("LinprogBoundDuals", LinprogDuals._fields + ("upper",))  # duals=True with ub given
 MilpBatchResult = namedtuple("MilpBatchResult", ("x", "objective", "status", "nodes", "node_pivots", "root_pivots"))
 
 STATUS_NAMES = _native.STATUS[:5]  # the YALPS_* codes 0..3 as solve() spells them, and 4, "timedout", which only a MILP ends with
@@ -67,13 +68,20 @@ def _strides(t, batched, matrix):
     return (t.data_ptr(), s[0] if batched else 0, s[-2] if matrix else s[-1], s[-1] if matrix else 0)
 
 
-def _call_operands(who, c, A_ub, b_ub, A_eq, b_eq, check_size):
+def _call_operands(who, c, A_ub, b_ub, A_eq, b_eq, check_size, vectors=None):
     """The five operands of a call, checked: (B, n, m_ub, m_eq, device, the five (ptr, batch, row, col) tuples, the tensors in
     that order with None where a side has no rows, which of them carry the batch dimension).  check_size(n, m_ub, m_eq)
     raises where the shape is above the call's limit; it runs after the shapes are known to agree and before the devices are
-    looked at."""
+    looked at.  vectors: {name: tensor or None} of further [B, n] / [n] operands (lb, ub), checked like the others and
+    returned as a ninth element, {name: (ptr, batch, row, col) or None}."""
     c, cB, (n,) = _operand("c", c, 1, who)
     batch = {"c": cB}
+    more = {}
+    for name, t in (vectors or {}).items():
+        if t is not None:
+            more[name], batch[name], (tn,) = _operand(name, t, 1, who)
+            if tn != n:
+                raise ValueError("%s: %s has %d entries, c has %d variables" % (who, name, tn, n))
     sides = []
     for tag, A, b in (("ub", A_ub, b_ub), ("eq", A_eq, b_eq)):
         if (A is None) != (b is None):
@@ -95,7 +103,7 @@ def _call_operands(who, c, A_ub, b_ub, A_eq, b_eq, check_size):
     (A_ub, b_ub, m_ub), (A_eq, b_eq, m_eq) = sides
     check_size(n, m_ub, m_eq)
     given = (c, A_ub, b_ub, A_eq, b_eq)
-    tensors = [t for t in given if t is not None]
+    tensors = [t for t in given if t is not None] + list(more.values())
     if any(not t.is_cuda for t in tensors):
         raise ValueError("%s: the operands are read on the GPU where they lie: a CPU tensor was given "
                          "(move it with .cuda(), or use solve_many for models in host memory)" % who)
@@ -104,11 +112,38 @@ def _call_operands(who, c, A_ub, b_ub, A_eq, b_eq, check_size):
         raise ValueError("%s: the operands lie on different devices: %s" % (who, sorted({str(t.device) for t in tensors})))
     batched = tuple(batch.get(k) is not None for k in ("c", "A_ub", "b_ub", "A_eq", "b_eq"))
     operands = tuple(_strides(t, batched[k], k in (1, 3)) for k, t in enumerate(given))
+    if vectors is not None:
+        extra = {name: _strides(more.get(name), batch.get(name) is not None, False) for name in vectors}
+        return B, n, m_ub, m_eq, device, operands, given, batched, extra
     return B, n, m_ub, m_eq, device, operands, given, batched
 
 
-def linprog_batch(c, A_ub=None, b_ub=None, A_eq=None, b_eq=None, *, maximize=False, precision=1e-8, max_pivots=8192,
-                  check_cycles=False, stats=None, duals=False):
+def _upper_set(n, upper, has_ub, who="linprog_batch"):
+    """`upper` as the ascending list of 0-based variable indices whose ub entry the call reads (True: all n, where ub is given);
+    raises ValueError for a duplicate, an index outside 0 .. n - 1, or a set given without ub, as milp_dense.integer_sets does."""
+    if upper is True:
+        return list(range(n)) if has_ub else []
+    if not has_ub:
+        raise ValueError("%s: upper names the variables whose ub entry is read, and no ub was given" % who)
+    if upper is False or upper is None:
+        upper = ()
+    if isinstance(upper, (str, bytes)) or not hasattr(upper, "__iter__"):
+        raise TypeError("%s: upper must be a sequence of variable indices or True, not %r" % (who, upper))
+    idx = []
+    for j in upper:
+        if isinstance(j, bool) or int(j) != j:
+            raise TypeError("%s: upper holds %r; variable indices are integers" % (who, j))
+        idx.append(int(j))
+    bad = [j for j in idx if not 0 <= j < n]
+    if bad:
+        raise ValueError("%s: upper names variable %d, outside 0 .. %d" % (who, bad[0], n - 1))
+    if len(set(idx)) != len(idx):
+        raise ValueError("%s: upper names variable %d twice" % (who, next(j for k, j in enumerate(idx) if j in idx[:k])))
+    return sorted(idx)
+
+
+def linprog_batch(c, A_ub=None, b_ub=None, A_eq=None, b_eq=None, *, lb=None, ub=None, upper=True, maximize=False, precision=1e-8,
+                  max_pivots=8192, check_cycles=False, stats=None, duals=False):
     """Solves B dense LPs of one shape in one call, from device tensors to device tensors:
 
         minimize (or maximize=True: maximize)  c . x   subject to   A_ub x <= b_ub,   A_eq x = b_eq,   x >= 0
@@ -147,20 +182,53 @@ def linprog_batch(c, A_ub=None, b_ub=None, A_eq=None, b_eq=None, *, maximize=Fal
     Any other status -- "unbounded" too, which has no dual solution -- gives NaN in all three rows.  They equal, bit for
     bit, the "dual" and "reduced_cost" sensitivity() reports for the equivalent model.
 
+    Bounds.  lb ([B, n] or [n], float64, read through its strides where it lies, every entry) means x >= lb and REPLACES
+    x >= 0 for the call, so negative entries are legal.  ub ([B, n] or [n]) means x[j] <= ub[j] for the variables `upper` names: a
+    HOST sequence of 0-based indices, or True for all n, shared by the batch -- what changes the tableau's height is host data,
+    and one call has one shape.  Entries of ub at unlisted variables are never read.  A duplicate or out-of-range index, and
+    an `upper` other than True without ub, raise ValueError before the library is touched.  Nothing is materialised: lb is a
+    substitution x = lb + x' made on the device, which moves every right-hand side by the row's shift_sum(A[i], lb) -- a sum of
+    individually rounded products in one fixed order (64 partial sums over the columns j = k mod 64 in ascending j, then folded
+    by 32, 16, .. 1) -- with one subtraction, and x and the objective back with one addition each (objective += shift_sum(c, lb));
+    ub adds k = len(upper) generated rows below the equality rows, in ascending index: ub[j] - lb[j] in column 0 and 1.0 in
+    the variable's column.  The tableau is (n + 1) x (1 + m_ub + 2 m_eq + k), and the 4 MiB limit holds for that height.  For
+    finite data row i is solve() of the equivalent model in x': linprog_batch's constraints with the shifted right-hand
+    sides, then h<j> {"max": ub[j] - lb[j]} in which variable j alone has a coefficient, 1.  Without lb and ub the call is
+    what it was, bit for bit, and launches the same kernels.
+    With duals=True and ub given the result is LinprogBoundDuals: LinprogDuals' seven fields plus upper [B, k], the marginals
+    of x[j] <= ub[j] in ascending index (scipy's upper.marginals); reduced_costs keeps its name and is the marginal of x >= lb
+    (scipy's lower.marginals).  Every "optimal" row satisfies, up to rounding,
+        reduced_costs = c - A_ub^T ineqlin - A_eq^T eqlin - scatter(upper)    and
+        objective = ineqlin . b_ub + eqlin . b_eq + upper . ub + reduced_costs . lb.
+    Out of scope: free variables (an lb entry of -inf is taken as it lies in memory, like every other value), per-LP `upper`
+    sets, and bounds in milp_batch (where the bound rows will come before the binary rows).
+
     See the module's docstring for the loading rule: torch first."""
+    sets = {}
+
     def size(n, m_ub, m_eq):
-        w, h = n + 1, 1 + m_ub + 2 * m_eq
+        k = len(sets.setdefault("upper", _upper_set(n, upper, ub is not None)))
+        w, h = n + 1, 1 + m_ub + 2 * m_eq + k
         if 8 * w * h > _native.LPDENSE_MAX_BYTES:
             raise ValueError("linprog_batch: a tableau of %d x %d doubles (%d bytes) is above the batch limit of %d bytes; "
                              "solve() is the route for such models" % (h, w, 8 * w * h, _native.LPDENSE_MAX_BYTES))
 
-    B, n, m_ub, m_eq, device, operands = _call_operands("linprog_batch", c, A_ub, b_ub, A_eq, b_eq, size)[:6]
+    B, n, m_ub, m_eq, device, operands, _, _, bounds = _call_operands("linprog_batch", c, A_ub, b_ub, A_eq, b_eq, size,
+                                                                      vectors={"lb": lb, "ub": ub})
+    idx = sets["upper"]
+    bounded = lb is not None or ub is not None
+    ptr = lambda t: t.data_ptr() if t.numel() else None
     x = torch.empty((B, n), dtype=torch.float64, device=device)
     objective = torch.empty((B,), dtype=torch.float64, device=device)
     status = torch.empty((B,), dtype=torch.int32, device=device)
     pivots = torch.empty((B,), dtype=torch.int64, device=device)
     marginals = [torch.empty((B, k), dtype=torch.float64, device=device) for k in (m_ub, m_eq, n)] if duals else []
-    ptr = lambda t: t.data_ptr() if t.numel() else None
+    upper_out = torch.empty((B, len(idx)), dtype=torch.float64, device=device) if duals and ub is not None else None
+    more = {}
+    if bounded:
+        # (a bound tensor without an element -- n = 0 -- stays a descriptor, so that the call still is the bounded one)
+        more = dict(lb=None if lb is None else bounds["lb"] or (None, 0, 0, 0), ub=None if ub is None else bounds["ub"] or (None, 0, 0, 0),
+                    upper=idx, upper_out=None if upper_out is None else ptr(upper_out))
     with torch.cuda.device(device), _lock:  # (the library selects the handle's device; torch's choice comes back afterwards)
         stream = torch.cuda.current_stream(device).cuda_stream or 1  # (the default stream's handle is 0: hipStreamLegacy names it)
         key = (device.index, stream)
@@ -169,10 +237,12 @@ def linprog_batch(c, A_ub=None, b_ub=None, A_eq=None, b_eq=None, *, maximize=Fal
             handle = _handles[key] = _native.LpDense(device.index, stream=stream)
         ms = handle.solve(B, n, m_ub, m_eq, operands, maximize=maximize, precision=precision, max_pivots=max_pivots,
                           check_cycles=check_cycles, x=ptr(x), objective=ptr(objective), status=ptr(status), pivots=ptr(pivots),
-                          **{k: ptr(t) for k, t in zip(("ineqlin", "eqlin", "reduced"), marginals)})
+                          **{k: ptr(t) for k, t in zip(("ineqlin", "eqlin", "reduced"), marginals)}, **more)
         if stats is not None:
             info = handle.info()
             stats.update(launches=info["launches"], reruns=info["reruns"], kernels=info["kernels"], gpu_ms=ms)
+    if upper_out is not None:
+        return LinprogBoundDuals(x, objective, status, pivots, *marginals, upper_out)
     if duals:
         return LinprogDuals(x, objective, status, pivots, *marginals)
     return LinprogBatch(x, objective, status, pivots)
@@ -208,6 +278,70 @@ class _Objective(torch.autograd.Function):
         return tuple(grads)
 
 
+class _BoundedObjective(torch.autograd.Function):
+    """_Objective for a call with lb or ub (None: absent): the same forward and the same five gradients with the full x, plus
+    d lb = g reduced_costs and d ub = g upper scattered into a [B, n] zero tensor."""
+
+    @staticmethod
+    def forward(ctx, options, upper, c, A_ub, b_ub, A_eq, b_eq, lb, ub):
+        out = linprog_batch(c, A_ub, b_ub, A_eq, b_eq, lb=lb, ub=ub, upper=upper, duals=True, **options)
+        ctx.sides = (A_ub is not None, A_eq is not None)
+        ctx.bounds = (lb is not None, ub is not None)
+        ctx.upper = _upper_set(c.shape[-1], upper, ub is not None)
+        ctx.save_for_backward(out.x, out.status, out.ineqlin, out.eqlin, out.reduced_costs, *out[7:])
+        rest = out[:1] + out[2:]
+        ctx.mark_non_differentiable(*rest)
+        return (out.objective, *rest)
+
+    @staticmethod
+    def backward(ctx, g, *_):
+        x, status, ineqlin, eqlin, reduced, *upper = ctx.saved_tensors
+        ok = (status == 0).unsqueeze(1)
+        zero = torch.zeros((), dtype=x.dtype, device=x.device)
+        g = torch.where(ok, g.unsqueeze(1), zero)
+        x, ineqlin, eqlin, reduced = (torch.where(ok, t, zero) for t in (x, ineqlin, eqlin, reduced))
+        need = ctx.needs_input_grad
+        grads = [None, None, g * x if need[2] else None]
+        for k, (has, y) in enumerate(zip(ctx.sides, (ineqlin, eqlin))):
+            gy = g * y
+            grads.append(-gy.unsqueeze(2) * x.unsqueeze(1) if has and need[3 + 2 * k] else None)
+            grads.append(gy if has and need[4 + 2 * k] else None)
+        grads.append(g * reduced if ctx.bounds[0] and need[7] else None)
+        d_ub = None
+        if ctx.bounds[1] and need[8]:
+            d_ub = torch.zeros_like(x)
+            d_ub[:, ctx.upper] = g * torch.where(ok, upper[0], zero)
+        grads.append(d_ub)
+        return tuple(grads)
+
+
+def _objective_call(who, options, given, upper=True):
+    """linprog_objective and linprog_objective_bounds behind their argument lists: given = {name: tensor or None} of the five
+    operands, and of lb / ub where the call has bounds."""
+    for tag in ("ub", "eq"):
+        if (given["A_" + tag] is None) != (given["b_" + tag] is None):
+            raise ValueError("%s: A_%s and b_%s come together" % (who, tag, tag))
+    ndim = {"c": 1, "A_ub": 2, "b_ub": 1, "A_eq": 2, "b_eq": 1, "lb": 1, "ub": 1}
+    sizes = {}
+    for name, t in given.items():
+        if t is not None:
+            batched = _operand(name, t, ndim[name], who)[1]
+            if batched is not None:
+                sizes[name] = batched
+    if len(set(sizes.values())) > 1:
+        raise ValueError("%s: the operands disagree about B: %s" % (who, ", ".join("%s has %d" % kv for kv in sizes.items())))
+    B = next(iter(sizes.values()), 1)
+    # a shared operand as a view with a batch stride of 0, in front of the Function: autograd sums its gradient over the batch
+    expanded = [None if t is None else (t if name in sizes else t.unsqueeze(0).expand(B, *t.shape)) for name, t in given.items()]
+    if "lb" in given:
+        has_ub = given["ub"] is not None
+        _upper_set(given["c"].shape[-1], upper, has_ub, who)
+        objective, *rest = _BoundedObjective.apply(options, upper, *expanded)
+        return objective, (LinprogBoundDuals if has_ub else LinprogDuals)(rest[0], objective.detach(), *rest[1:])
+    objective, *rest = _Objective.apply(options, *expanded)
+    return objective, LinprogDuals(rest[0], objective.detach(), *rest[1:])
+
+
 def linprog_objective(c, A_ub=None, b_ub=None, A_eq=None, b_eq=None, *, maximize=False, precision=1e-8, max_pivots=8192,
                       check_cycles=False):
     """The optimal value of B dense LPs as a differentiable function of their data: (objective [B], LinprogDuals).
@@ -228,26 +362,26 @@ def linprog_objective(c, A_ub=None, b_ub=None, A_eq=None, b_eq=None, *, maximize
     The optimal value is piecewise linear in b and c.  Inside a piece these are its derivatives; at a degenerate vertex,
     where pieces meet, they are one subgradient -- the one of the basis the solve ended in.  `objective` is rounded to
     `precision` as solve() rounds its result, so finite differences of it are only good to precision / step.  x itself is
-    piecewise constant and is returned without a gradient."""
+    piecewise constant and is returned without a gradient.
+
+    linprog_objective_bounds is this function for LPs with variable bounds."""
     options = dict(maximize=maximize, precision=precision, max_pivots=max_pivots, check_cycles=check_cycles)
-    given = {"c": c, "A_ub": A_ub, "b_ub": b_ub, "A_eq": A_eq, "b_eq": b_eq}
-    for tag in ("ub", "eq"):
-        if (given["A_" + tag] is None) != (given["b_" + tag] is None):
-            raise ValueError("linprog_objective: A_%s and b_%s come together" % (tag, tag))
-    ndim = {"c": 1, "A_ub": 2, "b_ub": 1, "A_eq": 2, "b_eq": 1}
-    sizes = {}
-    for name, t in given.items():
-        if t is not None:
-            batched = _operand(name, t, ndim[name])[1]
-            if batched is not None:
-                sizes[name] = batched
-    if len(set(sizes.values())) > 1:
-        raise ValueError("linprog_objective: the operands disagree about B: %s" % ", ".join("%s has %d" % kv for kv in sizes.items()))
-    B = next(iter(sizes.values()), 1)
-    # a shared operand as a view with a batch stride of 0, in front of the Function: autograd sums its gradient over the batch
-    expanded = [None if t is None else (t if name in sizes else t.unsqueeze(0).expand(B, *t.shape)) for name, t in given.items()]
-    objective, *rest = _Objective.apply(options, *expanded)
-    return objective, LinprogDuals(rest[0], objective.detach(), *rest[1:])
+    return _objective_call("linprog_objective", options, {"c": c, "A_ub": A_ub, "b_ub": b_ub, "A_eq": A_eq, "b_eq": b_eq})
+
+
+def linprog_objective_bounds(c, A_ub=None, b_ub=None, A_eq=None, b_eq=None, *, lb=None, ub=None, upper=True, maximize=False,
+                             precision=1e-8, max_pivots=8192, check_cycles=False):
+    """linprog_objective with linprog_batch's bounds lb, ub and upper (a function of its own: linprog_objective keeps the
+    argument list it has): (objective [B], what linprog_batch(..., lb=, ub=, upper=, duals=True) returns -- LinprogBoundDuals
+    where ub is given, else LinprogDuals).  linprog_objective's five formulas hold unchanged with the full x, and
+
+        dlb = g reduced_costs      dub = g upper, scattered into a [B, n] zero tensor (a variable `upper` does not list: 0)
+
+    A shared lb or ub receives the sum over the batch; a row that is not "optimal" contributes exact zeros.  Free variables,
+    per-LP `upper` sets and bounds in milp_batch are out of scope, as in linprog_batch."""
+    options = dict(maximize=maximize, precision=precision, max_pivots=max_pivots, check_cycles=check_cycles)
+    given = {"c": c, "A_ub": A_ub, "b_ub": b_ub, "A_eq": A_eq, "b_eq": b_eq, "lb": lb, "ub": ub}
+    return _objective_call("linprog_objective_bounds", options, given, upper)
 
 
 def _solve_on_host(device, rows, given, batched, B, ints, bins, maximize, options, out):
