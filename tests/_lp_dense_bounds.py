@@ -1,5 +1,5 @@
 """Helpers of tests/test_lp_dense_bounds_model.py and tests/test_lp_dense_bounds.py (TEST INFRASTRUCTURE): the calls the tests
-of yalps_lpdense_solve_bounds / linprog_batch(lb=, ub=, upper=) / linprog_objective_bounds make, and the two child processes that
+of yalps_lpdense_solve_bounds / linprog_batch(lb=, ub=, upper=) / linprog_objective_bounds make, and the three child processes that
 make them on the GPU (tests/_lp_dense.py says why children: torch first).  Each child writes everything its calls left behind to
 one .npz; the tests compare those files with the C oracle on tests/_np_dense_bounds.py's restatement.
 
@@ -7,6 +7,8 @@ one .npz; the tests compare those files with the C oracle on tests/_np_dense_bou
   table(oracle)   [BCall]: every call of the child "table" through _native.LpDense with kept tableaux and all eight outputs
   child "table"   the table; none / some / all output pointers; then the plumbing through linprog_batch and linprog_objective_bounds
   child "hist"    under YALPS_LPDENSE_HIST=4: the rerun writes x, the objective and the bound rows' marginals
+  hard_table(oracle)  [BCall]: data whose rounding shows (HARD) and hand-made pins, for the order of shift_sum and the read-out
+  child "hard"    the hard table, every call at max_pivots = 0 (the start tableau) and with its own options; the public route; views
 """
 import math
 import sys
@@ -43,16 +45,17 @@ class BCall(LD.Call):
         return (np.stack([np.asarray(a, np.float64) for a in self.lbs]) if self.has_lb else None,
                 np.stack([np.asarray(a, np.float64) for a in self.ubs]) if self.has_ub else None)
 
-    def oracle_answer(self, oracle, i):
+    def oracle_answer(self, oracle, i, flaw=None):
+        """flaw: None, or one of BD.FLAWS: the answer of a kernel that had that flaw (WRONG on purpose)."""
         lp, lb, ub = self.lps[i], self.lbs[i], self.ubs[i]
-        m = BD.bounded_tableau(*lp, lb=lb, ub=ub, upper=self.idx, maximize=self.maximize)
+        m = BD.bounded_tableau(*lp, lb=lb, ub=ub, upper=self.idx, maximize=self.maximize, flaw=flaw)
         start = m.copy()
         pos, var = np.arange(self.w + self.h, dtype=np.int32), np.arange(self.w + self.h, dtype=np.int32)
         status, result, npiv, _ = oracle.simplex(m, self.w, self.h, pos, var, precision=self.precision, max_pivots=self.max_pivots,
                                                  check_cycles=self.check)
         col0 = m.reshape(self.h, self.w)[:, 0].copy()
         sign = 1.0 if self.maximize else -1.0
-        x, objective = BD.bounded_solution(col0, pos, var, status, result, sign, self.precision, lp[0], lb)
+        x, objective = BD.bounded_solution(col0, pos, var, status, result, sign, self.precision, lp[0], lb, flaw=flaw)
         marg = BD.bounded_marginals(m, pos, status, self.n, self.m_ub, self.m_eq, self.k, sign)
         return dict(status=status, result=result, n_pivots=npiv, matrix=m, start=start, col0=col0, pos=pos, var=var, x=x, objective=objective,
                     **dict(zip(OUTPUTS, marg)))
@@ -207,6 +210,183 @@ def difference_call():
                 moved[op][j] += d
                 out.append(tuple(moved))
     return BCall("differences", out, precision=GRAD_PRECISION)
+
+
+# ------------------------------------------------------------------------------------------------ the hard calls
+# Data whose rounding shows: no product a[j] * lb[j] is exact and no two orders of adding them agree for long, so the bits of a
+# right-hand side tell THE order of shift_sum from BD.SUM_FLAWS, and the bits of x and of the objective tell the read-out from
+# BD.READ_FLAWS.  tests/test_lp_dense_bounds_model.py holds the floors (by call and flaw) that the seeds below were picked for, with
+# the oracle alone.
+# name: (B, n, m_ub, m_eq, upper or None: no ub, seed, chain, depth, options)
+HARD = {
+    # class 0: seven operand rows over the four waves of 256 lanes, two trips, the last one partial; lanes 0 and 1 hold three columns
+    "hard <256,lds>": (6, 129, 5, 2, (1, 128), 0, 0, 1.0, dict(maximize=True)),
+    "hard <256,check,lds>": (6, 129, 5, 2, (1, 128), 0, 0, 1.0, dict(maximize=True, check=True)),
+    # one lane with two columns, 64 full lanes, one lane short
+    "hard n=65": (6, 65, 5, 2, (1, 64), 5, 0, 1.0, dict(maximize=True)),
+    "hard n=64": (6, 64, 5, 2, (1, 63), 0, 0, 1.0, dict(maximize=True)),
+    "hard n=63": (6, 63, 5, 2, (1, 62), 0, 0, 1.0, dict(maximize=True)),
+    # class 3: seventeen operand rows over the sixteen waves of 1024 lanes
+    "hard <1024,lds>": (4, 449, 15, 2, (1, 448), 0, 0, 1.0, dict(maximize=True)),
+    "hard <1024,check,lds>": (4, 449, 15, 2, (1, 448), 0, 0, 1.0, dict(maximize=True, check=True)),
+    # class 4 without aux: rhs lies in HBM
+    "hard <1024> HBM": (3, 1025, 20, 1, (1, 1024), 0, 0, 1.0, dict(maximize=True)),
+    "hard <1024,check>": (3, 1025, 20, 1, (1, 1024), 0, 0, 1.0, dict(maximize=True, check=True)),
+    # the aux form: every lane holds 128 or 129 columns, the tableau is 4 x 8194.  Three rows end after a few pivots: the chain.  A sum
+    # of 8193 products of mean 1 is some 30 times its shift, and the subtraction would round most one-ulp changes away: x0 lies near lb
+    "hard aux wide": (3, 8193, 2, 0, (8192,), 0, 12, 2.0 ** -6, dict(maximize=True)),
+    # the other sign, and no bound rows
+    "hard minimize, lb only": (6, 129, 5, 2, None, 1, 0, 1.0, dict()),
+}
+HARD_FORMS = {"hard <256,lds>": (0, 0), "hard <256,check,lds>": (0, 0), "hard n=65": (0, 0), "hard n=64": (0, 0), "hard n=63": (0, 0),
+              "hard <1024,lds>": (3, 0), "hard <1024,check,lds>": (3, 0), "hard <1024> HBM": (4, 0), "hard <1024,check>": (4, 0),
+              "hard aux wide": (4, 1), "hard minimize, lb only": (0, 0)}  # name: (LB.size_class, BS.aux_hbm)
+PUBLIC_HARD = ("hard <256,lds>", "hard aux wide")  # once more through linprog_batch(duals=True): only the objective carries the shift there
+VIEWS_HARD = "hard <256,lds>"                      # the n = 129 call whose operands are also given as views
+PIN_NAMES = ("pins n=65", "pins n=64", "pin -0 objective, lb=0", "pin -0 objective, no lb")
+PIN_SHAPE = (30, 29)  # (M, N) of the _rounding family's LP
+
+
+def hard_lp(rng, n, m_ub, m_eq, has_ub, maximize, chain=0, depth=1.0):
+    """lb ~ N(0, 1), ub = lb + 0.25 + 3 U, a point x0 of the box, A = 6 U - 2, b_ub = A_ub x0 + slack, b_eq = A_eq x0.  The first
+    row of A_ub is positive (0.5 + U): together with x >= lb it bounds every variable, so the LP is bounded whatever c's signs.
+    c = that row * (1 + N(0, 1) / 8), negated for a minimising call: the quotients c[j] / A_ub[0, j] lie close together, and the
+    pivot rule (largest reduced cost first, not largest quotient) changes its mind many times.
+    chain: that many columns, spread at random, whose first-row entries fall by thirds while their quotients rise, and whose
+    other entries are negative: they enter one after the other, whatever else the LP holds (a tableau of three rows is
+    otherwise done after a handful of pivots)."""
+    lb = rng.standard_normal(n)
+    ub = lb + 0.25 + 3.0 * rng.random(n)  # (depth: how far into the box x0 may lie; the right-hand sides shrink with it)
+    x0 = lb + (ub - lb) * depth * rng.random(n)
+    A_ub, A_eq = rng.random((m_ub, n)) * 6.0 - 2.0, rng.random((m_eq, n)) * 6.0 - 2.0
+    A_ub[0] = 0.5 + rng.random(n)
+    c = A_ub[0] * (1.0 + rng.standard_normal(n) / 8.0)
+    if chain:
+        cols, t = np.sort(rng.choice(n - 1, chain, replace=False)), np.arange(1, chain + 1)
+        A_ub[0, cols] = 3.0 ** -t * (1.0 + 0.01 * rng.random(chain))
+        A_ub[1:, cols] = -(1.0 + rng.random((m_ub - 1, chain)))
+        c[cols] = A_ub[0, cols] * (2.0 + 0.1 * t)
+    b_ub = A_ub @ x0 + 0.125 * rng.random(m_ub)
+    return (c if maximize else -c, A_ub, b_ub, A_eq if m_eq else None, A_eq @ x0 if m_eq else None, lb, ub if has_ub else None)
+
+
+def hard_call(name, B, n, m_ub, m_eq, upper, seed=0, chain=0, depth=1.0, **options):
+    rng = np.random.default_rng([20261201, n, m_ub, m_eq, seed])
+    lps = [hard_lp(rng, n, m_ub, m_eq, upper is not None, bool(options.get("maximize")), chain, depth) for _ in range(B)]
+    call = BCall(name, lps, upper if upper is not None else True, **options)
+    if name in HARD_FORMS:
+        assert (LB.size_class(call.w, call.h), int(BS.aux_hbm(call.w, call.h))) == HARD_FORMS[name], (name, call.w, call.h)
+    return call
+
+
+def pin_lp(n, a, lb, b):
+    """One A_ub row `a` {column: value} over zeros with the right-hand side b; minimise the sum of x over x >= lb."""
+    row = np.zeros((1, n))
+    for j, v in a.items():
+        row[0, j] = v
+    return (np.ones(n), row, np.array([b], np.float64), None, None, np.asarray(lb, np.float64), None)
+
+
+# what the pins' right-hand side (cell (1, 0) of the start tableau) is, and what the flaw named beside it makes of it
+PINS_65 = ((0.5, "left to right", -0.5), (0.0, "fused", -2.0 ** -60), (-INF, "left to right", 0.25 - 1.5e308), (-0.0, None, None),
+           (0.0, "lanes of 32", -1.0))
+PINS_64 = ((-1.0, "fold upward", 0.0), (0.0, "fold upward", -1.0))
+
+
+def pin_calls(oracle):
+    """Hand-made rows whose shift has one known canonical value and one known wrong one (PINS_65, PINS_64, in order), lb given:
+      n = 65  1e16 at column 0, -1e16 at column 1, 1 at column 64, lb = 1, b = 0.5: lane 0 loses the 1, the shift is 0.0
+              1 * -(1 + 2^-29) at column 0 and (1 + 2^-30)^2 at column 64: the rounded product cancels exactly, the fused one not
+              1.5e308 at columns 0 and 64, -1.5e308 at column 1, lb = 1: lane 0 overflows, the shift is +inf; b = 0.25
+              a = 1, lb all -0.0, b = -0.0: every product is -0.0, but the sums start from +0.0: -0.0 - +0.0 stays -0.0
+              1e16, -1e16, 1 at columns 0, 32, 64: lane 0 adds columns 0 and 64 first, the 1 is lost; 32 lanes would keep it
+      n = 64  1e16, -1e16, 1 at columns 0, 32, 16: lanes 0 and 32 meet first, the 1 survives; and 1e16, 1, -1e16: it does not
+    and one LP of tests/_rounding.py's family R1, minimised: its objective is -0.0 without lb and, through the one addition of
+    shift_sum(c, 0) = +0.0, +0.0 with lb = 0."""
+    from tests import _rounding as RD
+    one, e = np.ones(65), 1.0 + 2.0 ** -30
+    l = one.copy()
+    l[0], l[64] = -(1.0 + 2.0 ** -29), e
+    p65 = [pin_lp(65, {0: 1e16, 1: -1e16, 64: 1.0}, one, 0.5), pin_lp(65, {0: 1.0, 64: e}, l, 0.0),
+           pin_lp(65, {0: 1.5e308, 1: -1.5e308, 64: 1.5e308}, one, 0.25), pin_lp(65, dict(enumerate(one)), -0.0 * one, -0.0),
+           pin_lp(65, {0: 1e16, 32: -1e16, 64: 1.0}, one, 0.0)]
+    p64 = [pin_lp(64, {0: 1e16, 32: -1e16, 16: 1.0}, np.ones(64), 0.0), pin_lp(64, {0: 1e16, 32: 1.0, 16: -1e16}, np.ones(64), 0.0)]
+    M, N = PIN_SHAPE
+    m = RD.r_make("R1", M, N, RD.R_SEED, dense_lp=oracle.dense_lp).reshape(M + 1, N + 1)
+    assert m[0:1, 0].view(np.int64)[0] == 0
+    lp = (-m[0, 1:], m[1:, 1:].copy(), m[1:, 0].copy(), None, None)  # (minimised: row 0 is -1 * c, the same words)
+    assert np.array_equal(ND.dense_tableau(*lp).view(np.int64), m.ravel().view(np.int64))
+    out = [BCall(PIN_NAMES[0], p65), BCall(PIN_NAMES[1], p64), BCall(PIN_NAMES[2], [(*lp, np.zeros(N), None)]),
+           BCall(PIN_NAMES[3], [(*lp, None, np.full(N, 64.0))], upper=())]
+    return out
+
+
+def hard_names():
+    return list(HARD) + list(PIN_NAMES)
+
+
+def hard_table(oracle):
+    T = [hard_call(name, *shape[:-1], **shape[-1]) for name, shape in HARD.items()]
+    T += pin_calls(oracle)
+    assert [c.name for c in T] == hard_names()
+    return T
+
+
+def at_budget_0(call):
+    """The same call with max_pivots = 0: simplex stops in front of the first pivot ("cycled"), the kept tableau is the start tableau."""
+    import copy
+    out = copy.copy(call)
+    out.name, out.max_pivots = call.name + " @0", 0.0
+    return out
+
+
+_answers = {}
+
+
+def hard_answers(oracle, call, flaw=None):
+    """[oracle_answer(i, flaw)] of a call of the hard table, computed once per process (both test modules ask for them)."""
+    key = (call.name, call.max_pivots, flaw)
+    if key not in _answers:
+        _answers[key] = [call.oracle_answer(oracle, i, flaw) for i in range(len(call.lps))]
+    return _answers[key]
+
+
+def differing(a, b):
+    """How many words of two float64 arrays differ, all NaNs counted as one value."""
+    from tests import _golden as G
+    return int(np.count_nonzero(G.canon(np.atleast_1d(a)).view(np.int64) != G.canon(np.atleast_1d(b)).view(np.int64)))
+
+
+def discrimination(oracle, call):
+    """{flaw: (cells, shifts, words)} of a call of the hard table, the oracle's answer under each of BD.FLAWS against the canonical
+    one: how many right-hand-side cells (column 0) of the start tableaux differ, for how many LPs shift_sum(c, lb) differs, and how
+    many words of x and of the objective differ."""
+    refs = hard_answers(oracle, call)
+    out = {}
+    for flaw in BD.FLAWS:
+        bad = hard_answers(oracle, call, flaw)
+        col0 = lambda r: r["start"].reshape(call.h, call.w)[:, 0]
+        cells = sum(differing(col0(a), col0(b)) for a, b in zip(refs, bad))
+        shifts = sum(differing(BD.shift_sum(lp[0], lb), BD.shift_sum_as(lp[0], lb, flaw)) for lp, lb in zip(call.lps, call.lbs)) if call.has_lb else 0
+        answer = sum(differing(a["x"], b["x"]) + differing(a["objective"], b["objective"]) for a, b in zip(refs, bad))
+        out[flaw] = (cells, shifts, answer)
+    return out
+
+
+def hard_views(torch, call):
+    """The n = 129 call's operands as views: A_ub and A_eq transposed (a column stride that is not 1), lb every other element of a
+    wider tensor; (views, copies), each (c, A_ub, b_ub, A_eq, b_eq, lb, ub)."""
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    c, A_ub, b_ub, A_eq, b_eq = call.stacked()
+    lb, ub = call.bounds_stacked()
+    B, n = lb.shape
+    A_ub_t, A_eq_t = dev(A_ub.transpose(0, 2, 1)), dev(A_eq.transpose(0, 2, 1))
+    lb_wide = torch.full((B, 2 * n), -9.0, dtype=torch.float64, device="cuda")
+    lb_wide[:, ::2] = dev(lb)
+    views = (dev(c), A_ub_t.transpose(1, 2), dev(b_ub), A_eq_t.transpose(1, 2), dev(b_eq), lb_wide[:, ::2], dev(ub))
+    assert views[1].stride()[1:] == (1, call.m_ub) and views[3].stride()[1:] == (1, call.m_eq) and views[5].stride() == (2 * n, 2)
+    copies = tuple(dev(a) for a in (c, A_ub, b_ub, A_eq, b_eq, lb, ub))
+    return views, copies
 
 
 # ------------------------------------------------------------------------------------------------ the children
@@ -417,5 +597,41 @@ def child_hist(path):
     np.savez(path, **out)
 
 
+def child_hard(path):
+    """Every call of hard_table twice through _native.LpDense with kept tableaux -- with max_pivots = 0 ("<name> @0": the kept
+    tableau is the start tableau) and with its own options -- then two of them through linprog_batch(duals=True), and the n = 129
+    call through views."""
+    assert "libamdhip64" not in open("/proc/self/maps").read(), "a HIP runtime was loaded before torch"
+    import torch
+    torch.cuda.init()
+    from tests import _oracle
+    from yalps_amd import _native as nat
+    from yalps_amd import tensors
+    out = {}
+    T = hard_table(_oracle.load())
+    handle = nat.LpDense(0, stream=torch.cuda.current_stream().cuda_stream or 1)
+    try:
+        for call in T:
+            for c in (at_budget_0(call), call):
+                out.update({"%s/%s" % (c.name, k): v for k, v in run_call(torch, handle, c).items()})
+    finally:
+        handle.close()
+    by_name = {c.name: c for c in T}
+    dev = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    for name in PUBLIC_HARD:
+        call, stats = by_name[name], {}
+        lb, ub = call.bounds_stacked()
+        got = tensors.linprog_batch(*[dev(a) for a in call.stacked()], lb=dev(lb), ub=dev(ub), upper=call.upper, maximize=call.maximize,
+                                    check_cycles=call.check, duals=True, stats=stats)
+        out.update({"%s public/%s" % (name, k): v for k, v in answer(got).items()})
+        out["%s public/kernels" % name] = np.array(" ".join(k["kernel"] for k in stats["kernels"]))
+    call = by_name[VIEWS_HARD]
+    views, copies = hard_views(torch, call)
+    for tag, ops in (("hard views", views), ("hard views copies", copies)):
+        got = tensors.linprog_batch(*ops[:5], lb=ops[5], ub=ops[6], upper=call.upper, maximize=call.maximize, duals=True)
+        out.update({"%s/%s" % (tag, k): v for k, v in answer(got).items()})
+    np.savez(path, **out)
+
+
 if __name__ == "__main__":
-    {"table": child_table, "hist": child_hist}[sys.argv[1]](sys.argv[2])
+    {"table": child_table, "hist": child_hist, "hard": child_hard}[sys.argv[1]](sys.argv[2])

@@ -5,6 +5,9 @@ they extend.
   shift_sum          sum of a[j] * l[j] in THE canonical order: every product rounded on its own; 64 partial sums p[k], each
                      starting from +0.0 and adding the products of the columns j = k (mod 64) in ascending j; then
                      p[k] += p[k + s] for k < s, s = 32, 16, 8, 4, 2, 1; the value is p[0].  It depends on nothing but a and l.
+  shift_sum_lanes    the same order stated a second time, lane by lane; fma: a * b + c rounded once, in rationals
+  flawed_shift_sum   WRONG on purpose, by the names of SUM_FLAWS; bounded_tableau(flaw=) and bounded_solution(flaw=) take those and
+                     READ_FLAWS: the mutants the hard calls of tests/_lp_dense_bounds.py are shown to reject
   upper_set          `upper` (True: all n; else 0-based indices) as the ascending tuple of the call, refusing what the call refuses
   bounded_tableau    what DenseJob<true>::fill writes: dense_tableau with column 0 of every operand row moved by the row's
                      shift_sum with lb (one subtraction; none at all without lb), and below the equality rows one row per
@@ -21,6 +24,9 @@ they extend.
                          objective = ineqlin . b_ub + eqlin . b_eq + upper . ub + reduced . lb
 Shares no code with the product.
 """
+import math
+from fractions import Fraction
+
 import numpy as np
 
 from tests import _np_dense as ND
@@ -45,6 +51,81 @@ def shift_sum(a, l):
     return np.float64(p[0])
 
 
+def shift_sum_lanes(a, l):
+    """THE order once more, sharing no line with shift_sum: lane k's list of columns k, k + 64, .. summed on its own, then the
+    list of 64 halved until one value is left."""
+    a, l = [float(v) for v in np.asarray(a, np.float64).reshape(-1)], [float(v) for v in np.asarray(l, np.float64).reshape(-1)]
+    assert len(a) == len(l)
+    with np.errstate(all="ignore"):
+        v = []
+        for k in range(LANES):
+            p = np.float64(0.0)
+            for j in range(k, len(a), LANES):
+                p = p + np.float64(a[j]) * np.float64(l[j])
+            v.append(p)
+        while len(v) > 1:
+            half = len(v) // 2
+            v = [v[k] + v[k + half] for k in range(half)]
+    return np.float64(v[0])
+
+
+def fma(a, b, c):
+    """a * b + c rounded once, in rationals (CPython's int / int is correctly rounded); IEEE's rules where they are not enough:
+    anything that is not finite, an exact zero, an overflow."""
+    a, b, c = float(a), float(b), float(c)
+    with np.errstate(all="ignore"):
+        if not (math.isfinite(a) and math.isfinite(b) and math.isfinite(c)):
+            return float(np.float64(a) * np.float64(b) + np.float64(c))
+        if a == 0.0 or b == 0.0:
+            return float(np.float64(a) * np.float64(b) + np.float64(c))  # (+-0 + c: exact, and the zero's sign is the addition's)
+    exact = Fraction(a) * Fraction(b) + Fraction(c)
+    if exact == 0:
+        return 0.0  # (two non-zero terms that cancel: +0.0 under round-to-nearest)
+    try:
+        return float(exact)
+    except OverflowError:
+        return math.inf if exact > 0 else -math.inf
+
+
+# Wrong on purpose (TEST INFRASTRUCTURE, as tests/_sens_table.py's FLAWS): what a kernel that misses the documented order, or the
+# documented read-out, would compute.  tests/test_lp_dense_bounds_model.py shows that the hard calls of tests/_lp_dense_bounds.py
+# tell every one of them from the canonical statement.
+SUM_FLAWS = ("left to right", "fused", "fold upward", "lanes of 32")
+READ_FLAWS = ("round after add", "objective rounded last", "dot")
+FLAWS = SUM_FLAWS + READ_FLAWS
+
+
+def flawed_shift_sum(a, l, flaw):
+    """shift_sum WRONG on purpose, by name:
+      "left to right"  one running sum from +0.0 in ascending j
+      "fused"          THE order with every p + a[j] * l[j] as one fused multiply-add (the product is not rounded on its own)
+      "fold upward"    THE lanes folded by 1, 2, 4, .. 32 (p += shfl_down(p, s) in every lane at once)
+      "lanes of 32"    32 partial sums over j = k (mod 32), folded by 16, .. 1"""
+    assert flaw in SUM_FLAWS, flaw
+    a, l = np.asarray(a, np.float64).reshape(-1), np.asarray(l, np.float64).reshape(-1)
+    assert a.size == l.size
+    with np.errstate(all="ignore"):
+        if flaw == "left to right":
+            s = np.float64(0.0)
+            for j in range(a.size):
+                s = s + a[j] * l[j]
+            return np.float64(s)
+        lanes = 32 if flaw == "lanes of 32" else LANES
+        p = [np.float64(0.0)] * lanes
+        for j in range(a.size):
+            p[j % lanes] = np.float64(fma(a[j], l[j], p[j % lanes])) if flaw == "fused" else p[j % lanes] + a[j] * l[j]
+        steps = [1 << t for t in range(lanes.bit_length() - 1)]
+        for s in (steps if flaw == "fold upward" else steps[::-1]):
+            p = [p[k] + p[k + s] if k + s < lanes else p[k] for k in range(lanes)]
+    return np.float64(p[0])
+
+
+def shift_sum_as(a, l, flaw=None):
+    """shift_sum, or its flawed form where `flaw` names one of SUM_FLAWS (a read-out flaw leaves the sums alone)."""
+    assert flaw is None or flaw in FLAWS, flaw
+    return flawed_shift_sum(a, l, flaw) if flaw in SUM_FLAWS else shift_sum(a, l)
+
+
 def upper_set(n, upper, has_ub=True):
     if upper is True:
         return tuple(range(n)) if has_ub else ()
@@ -54,7 +135,8 @@ def upper_set(n, upper, has_ub=True):
     return tuple(sorted(idx))
 
 
-def bounded_tableau(c, A_ub=None, b_ub=None, A_eq=None, b_eq=None, lb=None, ub=None, upper=True, maximize=False):
+def bounded_tableau(c, A_ub=None, b_ub=None, A_eq=None, b_eq=None, lb=None, ub=None, upper=True, maximize=False, flaw=None):
+    """flaw: None, or one of FLAWS -- a sum flaw replaces every shift_sum, a read-out flaw changes nothing here."""
     n, m_ub, m_eq = ND.shape_of(c, A_ub, b_ub, A_eq, b_eq)
     idx = upper_set(n, upper, ub is not None)
     w, h0 = n + 1, 1 + m_ub + 2 * m_eq
@@ -63,9 +145,9 @@ def bounded_tableau(c, A_ub=None, b_ub=None, A_eq=None, b_eq=None, lb=None, ub=N
     with np.errstate(all="ignore"):
         if lb is not None:
             for i in range(m_ub):
-                m[1 + i, 0] = np.float64(b_ub[i]) - shift_sum(np.asarray(A_ub, np.float64).reshape(m_ub, n)[i], lb)
+                m[1 + i, 0] = np.float64(b_ub[i]) - shift_sum_as(np.asarray(A_ub, np.float64).reshape(m_ub, n)[i], lb, flaw)
             for k in range(m_eq):
-                v = np.float64(b_eq[k]) - shift_sum(np.asarray(A_eq, np.float64).reshape(m_eq, n)[k], lb)
+                v = np.float64(b_eq[k]) - shift_sum_as(np.asarray(A_eq, np.float64).reshape(m_eq, n)[k], lb, flaw)
                 m[1 + m_ub + 2 * k, 0], m[2 + m_ub + 2 * k, 0] = v, -v
         for t, j in enumerate(idx):
             m[h0 + t, 0] = np.float64(ub[j]) - np.float64(lb[j]) if lb is not None else np.float64(ub[j])
@@ -111,13 +193,31 @@ def equivalent_model(c, A_ub=None, b_ub=None, A_eq=None, b_eq=None, lb=None, ub=
     return model
 
 
-def bounded_solution(col0, pos, var, status, result, sign, precision, c, lb=None):
+def bounded_solution(col0, pos, var, status, result, sign, precision, c, lb=None, flaw=None):
+    """flaw: None, or one of FLAWS -- WRONG on purpose then: a sum flaw replaces shift_sum(c, lb);
+      "round after add"         x[j] = roundToPrecision(value + lb[j]) where the reference rounds `value`
+      "objective rounded last"  roundToPrecision(objective' + shift_sum(c, lb))
+      "dot"                     the objective as np.dot(c, x) of the shifted x
+    (the last three on "optimal" alone, and with lb: nothing is added without it)."""
+    assert flaw is None or flaw in FLAWS, flaw
     n = len(c)
     x, objective = ND.dense_solution(col0, pos, var, status, result, sign, precision, n)
     if lb is not None:
+        low = np.asarray(lb, np.float64)
         with np.errstate(all="ignore"):
-            x = x + np.asarray(lb, np.float64)
-            objective = float(np.float64(objective) + shift_sum(c, lb))
+            shifted = float(np.float64(objective) + shift_sum_as(c, lb, flaw))
+            if flaw == "round after add" and status == "optimal":
+                for j in range(n):
+                    row = int(pos[j + 1]) - (n + 1)
+                    value = np.float64(col0[row]) if row >= 0 else np.float64(0.0)
+                    x[j] = ND.round_to_precision(float(value + low[j]), precision) if value > precision else 0.0 + low[j]
+            else:
+                x = x + low
+            if flaw == "objective rounded last" and status == "optimal":
+                shifted = ND.round_to_precision(shifted, precision)
+            if flaw == "dot" and status == "optimal":
+                shifted = float(np.dot(np.asarray(c, np.float64), x))
+            objective = shifted
     return x, objective
 
 

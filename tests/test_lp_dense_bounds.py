@@ -1,4 +1,4 @@
-"""yalps_lpdense_solve_bounds, linprog_batch(lb=, ub=, upper=) and linprog_objective_bounds on the GPU.  The work runs in two child
+"""yalps_lpdense_solve_bounds, linprog_batch(lb=, ub=, upper=) and linprog_objective_bounds on the GPU.  The work runs in three child
 processes that import torch first (tests/_lp_dense.py says why); every test compares what a child wrote with the C oracle on the
 numpy restatement of the bounded tableau and of its read-out (tests/_np_dense_bounds.py), bit for bit, all NaNs counted as one
 value.
@@ -9,9 +9,11 @@ there is: the marginal rows reach lane 722 of 1024."""
 import numpy as np
 import pytest
 
+from tests import _golden as G
 from tests import _lp_batch as LB
 from tests import _lp_dense as LD
 from tests import _lp_dense_bounds as LBD
+from tests import _np_dense_bounds as BD
 from tests.test_lp_dense import check_answers, of, same
 
 pytestmark = pytest.mark.gpu
@@ -194,3 +196,112 @@ def test_objective_gradients_for_the_bounds(ran, oracle):
     numeric = np.array([(d["objective"][1 + 2 * e] - d["objective"][2 + 2 * e]) / (2.0 * LBD.GRAD_H) for e in range(6)])
     formulas = np.concatenate([got["reduced"][0], got["upper"][0]])
     assert (np.abs(numeric - formulas) <= LBD.GRAD_PRECISION / LBD.GRAD_H).all(), (numeric, formulas)
+
+
+# ------------------------------------------------------------------------------------------------------- the hard calls
+# Data whose rounding shows (tests/_lp_dense_bounds.py, HARD and the pins): the order of shift_sum is in the bits of the start
+# tableau's column 0 and of the objective, the read-out in the bits of x and of the objective, and nowhere else.
+
+@pytest.fixture(scope="module")
+def hard_ran(tmp_path_factory):
+    return run_child(tmp_path_factory, "hard")
+
+
+@pytest.fixture(scope="module")
+def hard_calls(oracle):
+    return {c.name: c for c in LBD.hard_table(oracle)}
+
+
+@pytest.mark.parametrize("name", LBD.hard_names())
+def test_hard_start_tableau(hard_ran, hard_calls, oracle, name):
+    """max_pivots = 0: simplex stops in front of the first pivot, and the kept tableau is what fill wrote, every word of it."""
+    call = LBD.at_budget_0(hard_calls[name])
+    got = of(hard_ran, call.name)
+    assert (got["status"] == LD.STATUS.index("cycled")).all() and (got["pivots"] == 0).all(), (name, got["status"], got["pivots"])
+    for i, (lp, lb, ub) in enumerate(zip(call.lps, call.lbs, call.ubs)):
+        want = BD.bounded_tableau(*lp, lb=lb, ub=ub, upper=call.idx, maximize=call.maximize)
+        bad = np.flatnonzero(G.canon(got["tableau"][i]).view(np.int64) != G.canon(want).view(np.int64))
+        assert not bad.size, ("%s LP %d" % (name, i), "(row, column) of the first words that differ", [divmod(int(p), call.w) for p in bad[:8]],
+                              got["tableau"][i][bad[:8]], want[bad[:8]])
+        assert same(got["col0"][i], want.reshape(call.h, call.w)[:, 0])
+    assert all(np.isnan(got[key]).all() for key in ("x", "objective") + LBD.OUTPUTS), name
+    refs = check_answers(got, call, oracle, call.name)
+    check_marginals(got, call, refs, call.name)
+    assert str(got["kernels"]) == kernel_of(call)[1] and int(got["launches"]) == 1 and int(got["reruns"]) == 0 and bool(got["unchanged"])
+
+
+@pytest.mark.parametrize("name", LBD.hard_names())
+def test_hard_call_against_the_oracle(hard_ran, hard_calls, oracle, name):
+    call, got = hard_calls[name], of(hard_ran, name)
+    refs = check_answers(got, call, oracle, name)
+    check_marginals(got, call, refs, name)
+    assert bool(got["unchanged"]), "the call wrote into its operands"
+    cls, kernel = kernel_of(call)
+    assert str(got["kernels"]) == kernel and int(got["launches"]) == 1 and int(got["reruns"]) == 0, (name, got["kernels"])
+    if name in LBD.HARD:
+        assert (cls, int(got["aux"][0])) == LBD.HARD_FORMS[name] and got["classes"].tolist() == [cls]
+        form = name[5:name.index(">") + 1] if "<" in name else "<1024>" if LBD.HARD_FORMS[name][1] else "<256,lds>"
+        assert kernel == "lp_dense_bounds_kernel" + form, (name, kernel)
+        assert 2 * [r["status"] for r in refs].count("optimal") >= len(refs) and max(r["n_pivots"] for r in refs) >= 8
+    if name == LBD.PIN_NAMES[2]:
+        assert got["objective"].view(np.int64).tolist() == [0]  # +0.0: -0.0 + shift_sum(c, 0)
+    if name == LBD.PIN_NAMES[3]:
+        assert got["objective"].view(np.int64).tolist() == [-2 ** 63]  # -0.0: nothing is added without lb
+
+
+def flawed_words(oracle, call, flaw):
+    """(start column 0, x, objective) of every LP as one array, under a flaw (None: the canonical ones)."""
+    full, at0 = LBD.hard_answers(oracle, call, flaw), LBD.hard_answers(oracle, LBD.at_budget_0(call), flaw)
+    return np.concatenate([np.concatenate([a["start"].reshape(call.h, call.w)[:, 0], r["x"], [r["objective"]]]) for r, a in zip(full, at0)])
+
+
+# the flaws a pins call is made for (the last pin has no lb: nothing is summed, nothing added)
+PIN_TELLS = {LBD.PIN_NAMES[0]: {"left to right", "fused", "lanes of 32"}, LBD.PIN_NAMES[1]: {"fold upward"}, LBD.PIN_NAMES[2]: set()}
+
+
+@pytest.mark.parametrize("name", list(LBD.HARD) + list(PIN_TELLS))
+def test_the_device_has_none_of_the_flaws(hard_ran, hard_calls, oracle, name):
+    """The words that carry the order and the read-out -- column 0 of the start tableau, x, the objective -- are the canonical
+    ones and differ from those of every flawed restatement (tests/test_lp_dense_bounds_model.py: which flaws a call can tell)."""
+    call = hard_calls[name]
+    got, at0 = of(hard_ran, name), of(hard_ran, LBD.at_budget_0(call).name)
+    device = np.concatenate([np.concatenate([at0["tableau"][i].reshape(call.h, call.w)[:, 0], got["x"][i], got["objective"][i:i + 1]])
+                             for i in range(len(call.lps))])
+    told = []
+    for flaw in BD.FLAWS:
+        wrong = flawed_words(oracle, call, flaw)
+        if LBD.differing(wrong, flawed_words(oracle, call, None)):
+            told.append(flaw)
+            assert LBD.differing(device, wrong), "%s: the device computes what the flaw %r computes" % (name, flaw)
+    assert not LBD.differing(device, flawed_words(oracle, call, None)), (name, "the device differs from the canonical words; it equals",
+                                                                           [f for f in BD.FLAWS if not LBD.differing(device, flawed_words(oracle, call, f))])
+    must = PIN_TELLS[name] if name in PIN_TELLS else set(BD.FLAWS) - ({"fused", "lanes of 32"} if call.n <= 64 else set())
+    assert set(told) >= must, (name, told)
+
+
+@pytest.mark.parametrize("name", LBD.PUBLIC_HARD)
+def test_hard_calls_through_linprog_batch(hard_ran, hard_calls, oracle, name):
+    """The public route keeps no tableau: the objective alone carries shift_sum(c, lb).  Its words, and the flaws it tells."""
+    call, got = hard_calls[name], of(hard_ran, name + " public")
+    kernels = str(got.pop("kernels"))
+    refs = check_public(got, call, oracle, name + " public")
+    assert kernels == kernel_of(call)[1]
+    objective = np.array([r["objective"] for r in refs])
+    told = []
+    for flaw in BD.SUM_FLAWS + BD.READ_FLAWS[1:]:
+        wrong = np.array([r["objective"] for r in LBD.hard_answers(oracle, call, flaw)])
+        if LBD.differing(wrong, objective):  # (one addition to a larger number rounds many a one-ulp change of the shift away)
+            told.append(flaw)
+            assert LBD.differing(got["objective"], wrong), "%s: the objective is what the flaw %r computes" % (name, flaw)
+    assert set(told) >= set(BD.READ_FLAWS[1:]) and len(told) > 2, (name, told)
+    inner = of(hard_ran, name)
+    assert all(same(got[k], inner[k]) for k in ("x", "objective") + LBD.OUTPUTS)
+
+
+def test_hard_views_give_the_words_of_copies_and_of_the_oracle(hard_ran, hard_calls, oracle):
+    """A_ub and A_eq as transposed views (a column stride that is not 1), lb every other element of a wider tensor."""
+    call = hard_calls[LBD.VIEWS_HARD]
+    assert call.n == 129
+    views, copies = of(hard_ran, "hard views"), of(hard_ran, "hard views copies")
+    check_public(views, call, oracle, "hard views")
+    assert set(views) == set(copies) and all(same(views[k], copies[k]) if views[k].dtype == np.float64 else np.array_equal(views[k], copies[k]) for k in views)

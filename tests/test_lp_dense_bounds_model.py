@@ -1,4 +1,5 @@
-"""The bounds of linprog_batch / yalps_lpdense_solve_bounds without a GPU: the canonical shift_sum, the numpy restatement of the
+"""The bounds of linprog_batch / yalps_lpdense_solve_bounds without a GPU: the canonical shift_sum, its second statement and its
+named flawed forms, the floors by which the hard calls of tests/_lp_dense_bounds.py tell every flaw, the numpy restatement of the
 bounded tableau (tests/_np_dense_bounds.py) against the explicitly built operands and against tableau_model of the equivalent
 model, the oracle's solves of it (feasibility, the two identities, the three endings bounds add), the lb / ub gradient formulas
 against central differences of the oracle's objective, and what the new entries and the new Python arguments refuse without a
@@ -10,6 +11,8 @@ import re
 import numpy as np
 import pytest
 
+from tests import _batch_shapes as BS
+from tests import _lp_batch as LB
 from tests import _lp_dense_bounds as LBD
 from tests import _np_dense as ND
 from tests import _np_dense_bounds as BD
@@ -59,8 +62,54 @@ def test_shift_sum_order_is_pinned():
     assert BD.shift_sum(b, np.ones(64)) == 0.0
     # every product is rounded on its own: (1 + 2^-30)^2 rounds to 1 + 2^-29, and the sum with -1 - 2^-29 is exactly 0
     e = 1.0 + 2.0 ** -30
-    assert BD.shift_sum([e, 1.0], [e, -(1.0 + 2.0 ** -29)]) == 0.0 and math.fma(e, e, -(1.0 + 2.0 ** -29)) != 0.0 if hasattr(math, "fma") else True
+    assert BD.shift_sum([e, 1.0], [e, -(1.0 + 2.0 ** -29)]) == 0.0
+    assert BD.fma(e, e, -(1.0 + 2.0 ** -29)) == 2.0 ** -60  # (in rationals: this Python may have no math.fma)
+    if hasattr(math, "fma"):
+        assert math.fma(e, e, -(1.0 + 2.0 ** -29)) == 2.0 ** -60
+    # with n = 2 every lane holds one product, and 0.0 + a * l fused is still the rounded product: a fused kernel shows only
+    # where one lane holds two columns, j and j + 64
+    assert BD.flawed_shift_sum([e, 1.0], [e, -(1.0 + 2.0 ** -29)], "fused") == 0.0
+    a, l = np.zeros(65), np.ones(65)
+    a[0], l[0], a[64], l[64] = 1.0, -(1.0 + 2.0 ** -29), e, e
+    assert words([BD.shift_sum(a, l)])[0] == 0 and BD.flawed_shift_sum(a, l, "fused") == 2.0 ** -60
     assert words([BD.shift_sum([], [])])[0] == 0 and words([BD.shift_sum([-0.0], [1.0])])[0] == 0  # starts from +0.0
+
+
+def test_fma_in_rationals_rounds_once():
+    """BD.fma against cases whose single rounding is known, and against the two-step value where both agree."""
+    e = 1.0 + 2.0 ** -30
+    assert BD.fma(e, e, 0.0) == 1.0 + 2.0 ** -29 == e * e  # one rounding of 1 + 2^-29 + 2^-60
+    assert BD.fma(1.0 + 2.0 ** -52, 1.0 - 2.0 ** -53, -1.0) == 2.0 ** -53 - 2.0 ** -105  # the product alone would round to 1 + 2^-53 -> 1.0
+    assert BD.fma(3.0, 5.0, 7.0) == 22.0 and BD.fma(1e308, 10.0, 0.0) == math.inf and BD.fma(-1e308, 10.0, 0.0) == -math.inf
+    assert words([BD.fma(0.0, -1.0, 0.0)])[0] == 0 and words([BD.fma(0.0, -1.0, -0.0)])[0] == words([-0.0])[0]  # -0 + +0, -0 + -0
+    assert words([BD.fma(2.0, 3.0, -6.0)])[0] == 0 and math.isnan(BD.fma(math.inf, 0.0, 1.0)) and BD.fma(math.inf, 1.0, 1.0) == math.inf
+    rng = np.random.default_rng(20261202)
+    for a, b, c in rng.standard_normal((200, 3)):
+        exact = BD.Fraction(float(a)) * BD.Fraction(float(b)) + BD.Fraction(float(c))
+        got = BD.fma(a, b, c)
+        assert abs(BD.Fraction(got) - exact) <= min(abs(BD.Fraction(float(np.nextafter(got, s))) - exact) for s in (-math.inf, math.inf))
+
+
+def test_flawed_sums_are_what_their_names_say():
+    """Each of BD.SUM_FLAWS on a row where its value is known, beside THE order's."""
+    one = np.ones(65)
+    a = np.zeros(65)
+    a[0], a[64], a[1] = 1e16, 1.0, -1e16
+    assert BD.flawed_shift_sum(a, one, "left to right") == 1.0 and BD.shift_sum(a, one) == 0.0
+    b = np.zeros(64)
+    b[0], b[32], b[16] = 1e16, -1e16, 1.0  # THE order: lanes 0 and 32 meet first; upward, lanes 0 .. 15 swallow lane 16 first
+    assert BD.shift_sum(b, np.ones(64)) == 1.0 and BD.flawed_shift_sum(b, np.ones(64), "fold upward") == 0.0
+    b[0], b[32], b[16] = 1e16, 1.0, -1e16
+    assert BD.shift_sum(b, np.ones(64)) == 0.0 and BD.flawed_shift_sum(b, np.ones(64), "fold upward") == 1.0
+    # 32 lanes: up to n = 64 they ARE the order (lane k of 32 is p[k] + p[k + 32], the first fold of 64), so random rows of 64 columns
+    # agree bit for bit; with column 64 the orders part: (a[0] + a[64]) + a[32] against (a[0] + a[32]) + a[64]
+    rng = np.random.default_rng(20261203)
+    for n in (1, 33, 63, 64):
+        r, l = rng.standard_normal(n) * 1e3, rng.standard_normal(n)
+        assert words([BD.shift_sum(r, l)])[0] == words([BD.flawed_shift_sum(r, l, "lanes of 32")])[0]
+    d = np.zeros(65)
+    d[0], d[32], d[64] = 1e16, -1e16, 1.0
+    assert BD.shift_sum(d, one) == 0.0 and BD.flawed_shift_sum(d, one, "lanes of 32") == 1.0
 
 
 @pytest.mark.parametrize("n", (1, 63, 64, 65, 129))
@@ -78,6 +127,75 @@ def test_shift_sum_lengths(n):
         v = [v[k] + v[k + half] for k in range(half)]
     assert words([BD.shift_sum(a, l)])[0] == words([v[0]])[0]
     assert abs(BD.shift_sum(a, l) - float(np.dot(a, l))) <= 1e-9 * float(np.abs(a * l).sum())
+
+
+# ------------------------------------------------------------------------------------------------------- the hard calls
+
+@pytest.fixture(scope="module")
+def hard(oracle):
+    return {c.name: c for c in LBD.hard_table(oracle)}
+
+
+@pytest.mark.parametrize("name", list(LBD.HARD))
+def test_hard_calls_tell_every_flaw(oracle, hard, name):
+    """The floors the hard fixtures were picked for, with the oracle alone: at least half of the LPs end "optimal"; one takes 8
+    pivots or more; every sum flaw changes the bits of a right-hand-side cell of a start tableau, and for n >= 129 some LP's
+    shift_sum(c, lb); every read-out flaw changes a word of x or of the objective.  Two exemptions, both for n <= 64, where the
+    flawed sum IS the canonical one for every input: "fused" (every lane holds one product, and fma(a, l, +0.0) is the rounded
+    product) and "lanes of 32" (lane k of 32 holds p[k] + p[k + 32], which is the first fold of the 64)."""
+    call = hard[name]
+    assert (LB.size_class(call.w, call.h), int(BS.aux_hbm(call.w, call.h))) == LBD.HARD_FORMS[name]
+    refs = LBD.hard_answers(oracle, call)
+    statuses, pivots = [r["status"] for r in refs], [r["n_pivots"] for r in refs]
+    counts = LBD.discrimination(oracle, call)
+    rhs = len(call.lps) * (call.m_ub + 2 * call.m_eq)
+    print("%s: %s, pivots %s" % (name, statuses, pivots))
+    for flaw, (cells, shifts, answer) in counts.items():
+        print("    %-24s %3d of %d right-hand-side cells, shift_sum(c, lb) of %d of %d LPs, %d words of x / objective"
+              % (flaw, cells, rhs, shifts, len(call.lps), answer))
+    assert 2 * statuses.count("optimal") >= len(statuses) and max(pivots) >= 8, (name, statuses, pivots)
+    for flaw in BD.SUM_FLAWS:
+        same_function = call.n <= 64 and flaw in ("fused", "lanes of 32")
+        assert counts[flaw][0] >= (0 if same_function else 1), (name, flaw, counts[flaw])
+        assert not same_function or counts[flaw] == (0, 0, 0), (name, flaw, counts[flaw])
+        assert call.n < 129 or counts[flaw][1] >= 1, (name, flaw, counts[flaw])
+    for flaw in BD.READ_FLAWS:
+        assert counts[flaw][2] >= 1 and counts[flaw][:2] == (0, 0), (name, flaw, counts[flaw])
+
+
+def test_both_statements_of_the_order_agree_on_every_hard_row(oracle, hard):
+    rows = 0
+    for call in hard.values():
+        if not call.has_lb:
+            continue
+        for lp, lb in zip(call.lps, call.lbs):
+            c, A_ub, _, A_eq, _ = lp
+            for a in [c] + list(np.asarray(A_ub).reshape(call.m_ub, call.n)) + ([] if A_eq is None else list(np.asarray(A_eq).reshape(call.m_eq, call.n))):
+                assert words([BD.shift_sum(a, lb)])[0] == words([BD.shift_sum_lanes(a, lb)])[0], call.name
+                rows += 1
+    assert rows > 400, rows
+
+
+def test_pins_hold_their_known_values(oracle, hard):
+    """Cell (1, 0) of every pin's start tableau: the canonical word, and the wrong one under the flaw the pin is for."""
+    for name, pins in ((LBD.PIN_NAMES[0], LBD.PINS_65), (LBD.PIN_NAMES[1], LBD.PINS_64)):
+        call = hard[name]
+        assert len(pins) == len(call.lps) and call.has_lb and not call.has_ub and call.k == 0
+        for i, (want, flaw, wrong) in enumerate(pins):
+            start = LBD.hard_answers(oracle, call)[i]["start"]
+            assert words(start[call.w:call.w + 1])[0] == words([want])[0], (name, i, start[call.w], want)
+            if flaw is not None:
+                bad = LBD.hard_answers(oracle, call, flaw)[i]["start"]
+                assert words(bad[call.w:call.w + 1])[0] == words([wrong])[0], (name, i, flaw, bad[call.w], wrong)
+        at0 = LBD.at_budget_0(call)
+        assert all(r["status"] == "cycled" and r["n_pivots"] == 0 for r in LBD.hard_answers(oracle, at0))
+    # the one addition to the objective: -0.0 without lb, -0.0 + shift_sum(c, 0) = -0.0 + +0.0 = +0.0 with lb = 0
+    with_lb, without = hard[LBD.PIN_NAMES[2]], hard[LBD.PIN_NAMES[3]]
+    a, b = LBD.hard_answers(oracle, with_lb)[0], LBD.hard_answers(oracle, without)[0]
+    assert a["status"] == b["status"] == "optimal" and a["n_pivots"] == b["n_pivots"] == 1
+    assert np.array_equal(words(a["matrix"]), words(b["matrix"])) and with_lb.k == without.k == 0 and not without.has_lb
+    assert words([b["objective"]])[0] == words([-0.0])[0] and words([a["objective"]])[0] == 0, (a["objective"], b["objective"])
+    assert words([BD.shift_sum(with_lb.lps[0][0], with_lb.lbs[0])])[0] == 0
 
 
 # ---------------------------------------------------------------------------------------------------------- restatement
