@@ -17,6 +17,22 @@
  *               never enters branchAndCut then (src/YALPS.ts:81).
  *   epilogue    milp_dense_solution_kernel reads every best tableau as `solution()` does (src/YALPS.ts:8-50) into dense rows.
  * Values are taken as they lie in memory, NaN and infinities included.  The device reads no clock: the timeout is +Infinity.
+ *
+ * Variable bounds (yalps_milpdense_solve_bounds): lb <= x replaces x >= 0 and x[j] <= ub[j] for the n_upper listed variables,
+ * as yalps_lpdense_solve_bounds has them, with three rules that come from the variables being integer -- all three decided
+ * from the host lists, none costs the device anything:
+ *   1. the effective lower bound l_eff[j] is lb[j] at a continuous variable, ceil(lb[j]) at an integer one (IEEE ceil: -0.5
+ *      gives -0.0, NaN and the infinities pass through) and +0.0 at a binary one, where lb is not read.  x = l_eff + x' keeps
+ *      "x' integral <=> x integral": the tree pass branches on x' and knows nothing of bounds.  Everything
+ *      yalps_lpdense_solve_bounds does with lb is done with l_eff: every right-hand side is moved by shift_sum(row, l_eff) in
+ *      yalps_lpdense.h's order of summation (the product with +0.0 at a binary column is still formed), a bound row holds
+ *      ub[j] - l_eff[j], x = x' + l_eff, objective = objective' + shift_sum(c, l_eff).
+ *   2. a binary variable has no bound row of its own: ub is not read there, and upper_idx may not name one.
+ *   3. rows: yalps_lpdense.h's, then the n_upper bound rows in ascending index, then the binary rows; width n + 1, height
+ *      1 + m_ub + 2 m_eq + n_upper + n_binaries, and the largest node counts them.
+ * The root pass and the epilogue of such a call are milp_dense_bounds_root_kernel and milp_dense_bounds_solution_kernel, the
+ * code object of libyalps_milpdense_bounds.so, which this library links; a call without bounds launches the kernels, and
+ * returns the bits, it always did.  There are no duals: a node's duals are not the model's.
  * Per call the descriptors go up (one call description, the integer lists, 72 + 80 bytes per tree) and one int32 per tree
  * per pass comes back: the statuses the host needs to decide about a rerun.
  *
@@ -103,6 +119,35 @@ int32_t yalps_milpdense_solve(yalps_milpdense *d, int32_t count, int32_t n, int3
                               int32_t trace_cap, double *x_out, double *objective_out, int32_t *status_out,
                               int64_t *nodes_out, int64_t *node_pivots_out, int64_t *root_pivots_out,
                               int64_t *call_stats_out);
+
+/* yalps_milpdense_validate with bounds: the height counts the n_upper bound rows, and on top of its refusals come
+ * yalps_lpdense_validate_bounds', by the same words under this library's name -- a negative n_upper, a negative stride or a NULL
+ * pointer of lb / ub where they have elements, n_upper > 0 without ub, a NULL upper_idx, upper_idx[t] outside 0 .. n-1 or not
+ * ascending -- and "variable j is binary" for an upper_idx entry that is in `binaries`.  lb and ub may be NULL descriptors
+ * (absent); upper_idx is a HOST list. */
+int32_t yalps_milpdense_validate_bounds(int32_t count, int32_t n, int32_t m_ub, int32_t m_eq, const yalps_milpdense_operand *c,
+                                        const yalps_milpdense_operand *A_ub, const yalps_milpdense_operand *b_ub,
+                                        const yalps_milpdense_operand *A_eq, const yalps_milpdense_operand *b_eq,
+                                        const yalps_milpdense_operand *lb, const yalps_milpdense_operand *ub, int32_t n_upper,
+                                        const int32_t *upper_idx, int32_t n_integers, const int32_t *integers, int32_t n_binaries,
+                                        const int32_t *binaries);
+
+/* yalps_milpdense_solve with bounds (the rules above).  lb[count][n] and ub[count][n] are DEVICE operands read through
+ * (batch, row) strides -- col unused; lb at every variable that is not binary, ub at upper_idx[0 .. n_upper) only -- and are
+ * looked up and refused by name like the others.  With both descriptors NULL (and n_upper = 0) the call is
+ * yalps_milpdense_solve.  With n_integers = 0 the first three outputs and root_pivots_out are yalps_lpdense_solve_bounds' x,
+ * objective, status and pivots, bit for bit.  yalps_milpdense_solution / _trace speak of the tableau in x': heights count the
+ * bound rows, column 0 is not moved back. */
+int32_t yalps_milpdense_solve_bounds(yalps_milpdense *d, int32_t count, int32_t n, int32_t m_ub, int32_t m_eq,
+                                     const yalps_milpdense_operand *c, const yalps_milpdense_operand *A_ub,
+                                     const yalps_milpdense_operand *b_ub, const yalps_milpdense_operand *A_eq,
+                                     const yalps_milpdense_operand *b_eq, const yalps_milpdense_operand *lb,
+                                     const yalps_milpdense_operand *ub, int32_t n_upper, const int32_t *upper_idx,
+                                     int32_t n_integers, const int32_t *integers, int32_t n_binaries, const int32_t *binaries,
+                                     int32_t maximize, double precision, double maxPivots, int32_t checkCycles, double tolerance,
+                                     double maxIterations, int32_t trace_cap, double *x_out, double *objective_out,
+                                     int32_t *status_out, int64_t *nodes_out, int64_t *node_pivots_out, int64_t *root_pivots_out,
+                                     int64_t *call_stats_out);
 
 /* The trees of the last solve that ended YALPS_MILPDENSE_OVERFLOW, ascending: at most `cap` indices into ids (HOST, may be
  * NULL with cap = 0).  Returns their number. */

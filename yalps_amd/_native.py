@@ -83,7 +83,7 @@ MILPDENSE_LIB_PATH = os.environ.get("YALPS_MILPDENSE_LIB") or os.path.join(HERE,
 SYMBOLS_MILPDENSE = (
     "yalps_milpdense_create", "yalps_milpdense_destroy", "yalps_milpdense_validate", "yalps_milpdense_solve",
     "yalps_milpdense_overflowed", "yalps_milpdense_solution", "yalps_milpdense_trace", "yalps_milpdense_info",
-    "yalps_milpdense_last_error")
+    "yalps_milpdense_last_error", "yalps_milpdense_validate_bounds", "yalps_milpdense_solve_bounds")
 MILPDENSE_MAX_BYTES = 4 << 20  # YALPS_MILPDENSE_MAX_BYTES: the largest possible node, root height + 2 * n_integers rows
 LPBATCH_HBM_CLASS = 4        # yalps_lpbatch_class: 0..3 the LDS form, 4 the HBM form
 
@@ -1517,6 +1517,9 @@ _BATCH_LIBS["yalps_milpdense"] = (MILPDENSE_LIB_PATH, {
         "validate": (_I32, [_I32, _I32, _I32, _I32, _DOP, _DOP, _DOP, _DOP, _DOP, _I32, _VP, _I32, _VP]),
         "solve": (_I32, [_VP, _I32, _I32, _I32, _I32, _DOP, _DOP, _DOP, _DOP, _DOP, _I32, _VP, _I32, _VP, _I32, C.c_double, C.c_double,
                          _I32, C.c_double, C.c_double, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+        "validate_bounds": (_I32, [_I32, _I32, _I32, _I32, _DOP, _DOP, _DOP, _DOP, _DOP, _DOP, _DOP, _I32, _VP, _I32, _VP, _I32, _VP]),
+        "solve_bounds": (_I32, [_VP, _I32, _I32, _I32, _I32, _DOP, _DOP, _DOP, _DOP, _DOP, _DOP, _DOP, _I32, _VP, _I32, _VP, _I32, _VP, _I32,
+                                C.c_double, C.c_double, _I32, C.c_double, C.c_double, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
         "overflowed": (_I32, [_VP, _VP, _I32]),
         "solution": (_I32, [_VP, _I32, C.POINTER(_I32), C.POINTER(C.c_double), C.POINTER(_I32), _VP, _VP, _VP]),
         "trace": (_I32, [_VP, _I32, C.POINTER(_I32)] + [_VP] * 8)})
@@ -1543,6 +1546,17 @@ def milpdense_validate(count, n, m_ub, m_eq, operands, integers=(), binaries=())
                                                              ints.size, ints.ctypes.data, bins.size, bins.ctypes.data))
 
 
+def milpdense_validate_bounds(count, n, m_ub, m_eq, operands, integers=(), binaries=(), lb=None, ub=None, upper=()):
+    """The host-only argument checks of yalps_milpdense_solve_bounds: milpdense_validate's with the height that counts the
+    len(upper) bound rows, plus lb / ub ((ptr, batch, row, col) or None: absent) and the index list, which is ascending and
+    names no binary variable."""
+    ops, ints, bins = _dense_operands(operands), _index_list(integers), _index_list(binaries)
+    lbp, ubp, k, idx = _dense_bounds(lb, ub, _index_list(upper))
+    milpdense_check(milpdense_lib().yalps_milpdense_validate_bounds(
+        int(count), int(n), int(m_ub), int(m_eq), *(C.byref(o) for o in ops), lbp, ubp, k, idx.ctypes.data, ints.size, ints.ctypes.data,
+        bins.size, bins.ctypes.data))
+
+
 class MilpDense:
     """Batches of dense MILPs of one shape, operands and answers in device memory, every tree walked on the device
     (yalps_milpdense_*).  Pointers are plain integers (a tensor's data_ptr()); nothing here imports torch.  Belongs to one
@@ -1556,19 +1570,29 @@ class MilpDense:
 
     def solve(self, count, n, m_ub, m_eq, operands, integers=(), binaries=(), maximize=False, precision=1e-8, max_pivots=8192.0,
               check_cycles=False, tolerance=0.0, max_iterations=32768.0, trace_cap=0, x=None, objective=None, status=None,
-              nodes=None, node_pivots=None, root_pivots=None):
+              nodes=None, node_pivots=None, root_pivots=None, lb=None, ub=None, upper=()):
         """operands = (c, A_ub, b_ub, A_eq, b_eq) as LpDense.solve takes them; integers / binaries: ascending 0-based variable
-        indices, `integers` the union of both sets; x / objective / status / nodes / node_pivots / root_pivots: device pointers
+        indices, `integers` the union of both sets; lb / ub: (device pointer, batch, row, col) of the bounds x >= lb and
+        x[j] <= ub[j] for the ascending indices j of `upper` (a host sequence that names no binary variable), or None -- with lb
+        or ub given the call is yalps_milpdense_solve_bounds, and the root is len(upper) rows taller; x / objective / status / nodes / node_pivots / root_pivots: device pointers
         of contiguous float64 [count][n], float64 [count], int32 [count] and three int64 [count], or None.  The outputs are
         complete on return.  Returns {"reruns", "launches", "overflows", "root_ms", "tree_ms", "epilogue_ms", "gpu_ms"}."""
         ops, ints, bins = _dense_operands(operands), _index_list(integers), _index_list(binaries)
         call = np.zeros(6, np.int64)
         self.shape = None
-        milpdense_check(milpdense_lib().yalps_milpdense_solve(
-            self.handle, int(count), int(n), int(m_ub), int(m_eq), *(C.byref(o) for o in ops), ints.size, ints.ctypes.data, bins.size,
-            bins.ctypes.data, int(bool(maximize)), float(precision), float(max_pivots), int(bool(check_cycles)), float(tolerance),
-            float(max_iterations), int(trace_cap), x, objective, status, nodes, node_pivots, root_pivots, call.ctypes.data))
-        self.shape = (int(count), int(n) + 1, 1 + int(m_ub) + 2 * int(m_eq) + bins.size, ints.size)
+        head = (self.handle, int(count), int(n), int(m_ub), int(m_eq), *(C.byref(o) for o in ops))
+        tail = (ints.size, ints.ctypes.data, bins.size, bins.ctypes.data, int(bool(maximize)), float(precision), float(max_pivots),
+                int(bool(check_cycles)), float(tolerance), float(max_iterations), int(trace_cap), x, objective, status, nodes, node_pivots,
+                root_pivots, call.ctypes.data)
+        k = 0
+        if lb is not None or ub is not None:
+            lbp, ubp, k, idx = _dense_bounds(lb, ub, _index_list(upper))
+            milpdense_check(milpdense_lib().yalps_milpdense_solve_bounds(*head, lbp, ubp, k, idx.ctypes.data, *tail))
+        elif len(upper):
+            raise NativeError("MilpDense.solve: upper without lb or ub")
+        else:
+            milpdense_check(milpdense_lib().yalps_milpdense_solve(*head, *tail))
+        self.shape = (int(count), int(n) + 1, 1 + int(m_ub) + 2 * int(m_eq) + k + bins.size, ints.size)
         self.trace_cap = int(trace_cap)
         root, tree, epi = (call[k] / 1000.0 for k in (3, 4, 5))
         return {"reruns": int(call[0]), "launches": int(call[1]), "overflows": int(call[2]), "root_ms": root, "tree_ms": tree,

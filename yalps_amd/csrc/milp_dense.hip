@@ -6,6 +6,9 @@
 // A library of its own: nothing here is linked into the others.  Nothing of a MILP crosses PCIe but its status: the operands
 // are read where they lie, x / objective are written by the epilogue, status and counts are copied device to device, and the
 // best tableaux stay on the device until yalps_milpdense_solution asks for one.
+// A call with bounds (lb / ub) runs milp_dense_bounds_root_kernel and milp_dense_bounds_solution_kernel
+// (milp_dense_bounds_kernel.cuh), whose forms are libyalps_milpdense_bounds.so's: this library links it and takes the kernels'
+// pointers from yalps_milpdense_bounds_forms, so its own code object holds the boundless kernels alone.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -31,6 +34,7 @@ namespace {
 #include "lp_batch_kernel.cuh" // (LpDesc: what milp_tree_kernel reads of a root; lp_batch_kernel itself is not instantiated here)
 #include "milp_tree_kernel.cuh"
 #include "milp_dense_kernel.cuh"
+#include "milp_dense_bounds_kernel.cuh" // (the two structs of a bounded call; its kernels are not instantiated here)
 #include "wg_queue_host.inc"
 #include "milp_tree_host.inc"
 
@@ -38,6 +42,28 @@ static_assert(YALPS_MILPDENSE_MAX_BYTES == QUEUE_MAX_BYTES, "include/yalps_milpd
 static_assert(TREE_TIMEDOUT == YALPS_MILPDENSE_TIMEDOUT && TREE_OVERFLOW == YALPS_MILPDENSE_OVERFLOW, "include/yalps_milpdense.h");
 const KernelTable<MilpDenseLaunch> kRootKernels = QUEUE_KERNEL_TABLE(milp_dense_root_kernel);
 constexpr int SOLUTION_LANES = 256;
+} // namespace
+
+extern "C" void yalps_milpdense_bounds_forms(void *out[7]); // milp_dense_bounds.hip
+
+namespace {
+// libyalps_milpdense_bounds.so's kernels: the same table over its root forms, and its epilogue
+struct BoundsKernels {
+    KernelTable<MilpDenseLaunch> roots;
+    void (*solution)(MilpBoundsSolutionArgs);
+};
+const BoundsKernels &bounds_kernels() {
+    static const BoundsKernels kernels = [] {
+        BoundsKernels k{kRootKernels, nullptr};
+        k.roots.name = "milp_dense_bounds_root_kernel";
+        void *fn[7];
+        yalps_milpdense_bounds_forms(fn);
+        for (int f = 0; f < 6; f++) k.roots.forms[f].fn = reinterpret_cast<void (*)(MilpDenseLaunch)>(fn[f]);
+        k.solution = reinterpret_cast<void (*)(MilpBoundsSolutionArgs)>(fn[6]);
+        return k;
+    }();
+    return kernels;
+}
 } // namespace
 
 struct yalps_milpdense : QueueDevice {
@@ -76,9 +102,10 @@ int check_list(const char *name, int32_t len, const int32_t *list, int32_t n) {
 
 int validate(int32_t count, int32_t n, int32_t m_ub, int32_t m_eq, const yalps_milpdense_operand *c, const yalps_milpdense_operand *A_ub,
              const yalps_milpdense_operand *b_ub, const yalps_milpdense_operand *A_eq, const yalps_milpdense_operand *b_eq, int32_t nints,
-             const int32_t *ints, int32_t nbin, const int32_t *bin) {
+             const int32_t *ints, int32_t nbin, const int32_t *bin, int32_t n_upper = 0) {
     if (count < 0) return fail(YALPS_E_ARG, "yalps_milpdense: count < 0");
     if (n < 0 || m_ub < 0 || m_eq < 0) return fail(YALPS_E_ARG, "yalps_milpdense: n, m_ub and m_eq must be at least 0");
+    if (n_upper < 0) return fail(YALPS_E_ARG, "yalps_milpdense: n_upper < 0");
     if (int rc = check_list("integers", nints, ints, n)) return rc;
     if (int rc = check_list("binaries", nbin, bin, n)) return rc;
     for (int32_t k = 0, at = 0; k < nbin; k++) { // (both ascending: one walk)
@@ -86,7 +113,7 @@ int validate(int32_t count, int32_t n, int32_t m_ub, int32_t m_eq, const yalps_m
         if (at >= nints || ints[at] != bin[k])
             return fail(YALPS_E_ARG, "yalps_milpdense: binary variable " + std::to_string(bin[k]) + " is not in integers (the union of both sets)");
     }
-    const int64_t w = (int64_t)n + 1, h = 1 + (int64_t)m_ub + 2 * (int64_t)m_eq + nbin, hmax = h + 2 * (int64_t)nints;
+    const int64_t w = (int64_t)n + 1, h = 1 + (int64_t)m_ub + 2 * (int64_t)m_eq + (int64_t)n_upper + nbin, hmax = h + 2 * (int64_t)nints;
     if (w > INT32_MAX || hmax > INT32_MAX || 8 * w * hmax > YALPS_MILPDENSE_MAX_BYTES)
         return fail(YALPS_E_ARG, "yalps_milpdense: largest node of " + std::to_string(hmax) + " x " + std::to_string(w) + " doubles (" +
                                      std::to_string(h) + " rows and two cuts for each of " + std::to_string(nints) +
@@ -99,11 +126,37 @@ int validate(int32_t count, int32_t n, int32_t m_ub, int32_t m_eq, const yalps_m
     return 0;
 }
 
+// the bounds of a call: lb / ub may be NULL descriptors (absent); upper_idx is host memory, ascending, inside 0 .. n-1, and names
+// no binary variable (yalps_lpdense_validate_bounds' refusals, by the same words, and that one)
+int validate_bounds(int32_t count, int32_t n, int32_t m_ub, int32_t m_eq, const yalps_milpdense_operand *c, const yalps_milpdense_operand *A_ub,
+                    const yalps_milpdense_operand *b_ub, const yalps_milpdense_operand *A_eq, const yalps_milpdense_operand *b_eq,
+                    const yalps_milpdense_operand *lb, const yalps_milpdense_operand *ub, int32_t n_upper, const int32_t *upper_idx,
+                    int32_t nints, const int32_t *ints, int32_t nbin, const int32_t *bin) {
+    if (int rc = validate(count, n, m_ub, m_eq, c, A_ub, b_ub, A_eq, b_eq, nints, ints, nbin, bin, n_upper)) return rc;
+    if (lb)
+        if (int rc = check_operand("lb", lb, count, n, 1)) return rc;
+    if (ub)
+        if (int rc = check_operand("ub", ub, count, n_upper, 1)) return rc;
+    if (n_upper > 0 && !ub) return fail(YALPS_E_ARG, "yalps_milpdense: n_upper > 0 without ub");
+    if (n_upper > 0 && !upper_idx) return fail(YALPS_E_ARG, "yalps_milpdense: upper_idx is NULL");
+    for (int32_t t = 0, at = 0; t < n_upper; t++) {
+        if (upper_idx[t] < 0 || upper_idx[t] >= n)
+            return fail(YALPS_E_ARG, "yalps_milpdense: upper_idx[" + std::to_string(t) + "] = " + std::to_string(upper_idx[t]) + " is outside 0 .. n-1");
+        if (t && upper_idx[t] <= upper_idx[t - 1])
+            return fail(YALPS_E_ARG, "yalps_milpdense: upper_idx is not ascending at " + std::to_string(t));
+        while (at < nbin && bin[at] < upper_idx[t]) at++; // (both ascending: one walk)
+        if (at < nbin && bin[at] == upper_idx[t])
+            return fail(YALPS_E_ARG, "yalps_milpdense: upper_idx[" + std::to_string(t) + "]: variable " + std::to_string(upper_idx[t]) +
+                                         " is binary (a binary variable has no bound row)");
+    }
+    return 0;
+}
+
 // A pointer a kernel is to dereference: device (or managed) memory of the handle's device, known to THIS runtime
 // (as lp_dense.hip::check_pointer).
-int check_pointer(const yalps_milpdense *b, const char *name, const void *p) {
+int check_pointer(const yalps_milpdense *b, const char *entry, const char *name, const void *p) {
     if (!p) return 0;
-    const std::string who = std::string("yalps_milpdense_solve: ") + name;
+    const std::string who = std::string(entry) + ": " + name;
     hipPointerAttribute_t attr;
     std::memset(&attr, 0, sizeof attr);
     if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
@@ -133,6 +186,7 @@ int create_impl(int32_t device, void *hip_stream, yalps_milpdense **out) {
     b->t.grid = std::max(0, env_int("YALPS_MILPDENSE_GRID", 0));
     b->info = "launches=0 reruns=0 overflows=0 gpu_us=0 root_us=0 tree_us=0 epilogue_us=0 rerun_lps=[] rerun_trees=[]\n";
     if (int rc = raise_lds_limit(kRootKernels)) return rc;
+    if (int rc = raise_lds_limit(bounds_kernels().roots)) return rc;
     return raise_lds_limit(kTreeKernels);
 }
 
@@ -143,13 +197,15 @@ struct Times {
     std::string root_lines, epilogue_line;
 };
 
-int solve_impl(yalps_milpdense *b, int32_t count, int32_t n, int32_t m_ub, int32_t m_eq, const yalps_milpdense_operand *c,
+int solve_impl(yalps_milpdense *b, const char *entry, int32_t count, int32_t n, int32_t m_ub, int32_t m_eq, const yalps_milpdense_operand *c,
                const yalps_milpdense_operand *A_ub, const yalps_milpdense_operand *b_ub, const yalps_milpdense_operand *A_eq,
                const yalps_milpdense_operand *b_eq, int32_t nints, const int32_t *ints, int32_t nbin, const int32_t *bin,
                int32_t maximize, double precision, double maxPivots, int32_t checkCycles, double tolerance, double maxIter,
                int32_t trace_cap, double *x_out, double *objective_out, int32_t *status_out, int64_t *nodes_out,
-               int64_t *node_pivots_out, int64_t *root_pivots_out, Times &tm) {
+               int64_t *node_pivots_out, int64_t *root_pivots_out, Times &tm, const yalps_milpdense_operand *lb = nullptr,
+               const yalps_milpdense_operand *ub = nullptr, int32_t n_upper = 0, const int32_t *upper_idx = nullptr) {
     TreePass &t = b->t;
+    const bool bounds = lb || ub; // (either descriptor: the bounded kernels; neither: the kernels and the bits of before)
     b->count = 0;
     b->walked = false;
     b->overflowed.clear();
@@ -158,8 +214,8 @@ int solve_impl(yalps_milpdense *b, int32_t count, int32_t n, int32_t m_ub, int32
     t.rerun_ids.clear();
     t.launches = t.overflows = 0;
     t.gpu_ms = 0.0;
-    if (trace_cap < 0) return fail(YALPS_E_ARG, "yalps_milpdense_solve: trace_cap < 0");
-    if (int rc = validate(count, n, m_ub, m_eq, c, A_ub, b_ub, A_eq, b_eq, nints, ints, nbin, bin)) return rc;
+    if (trace_cap < 0) return fail(YALPS_E_ARG, std::string(entry) + ": trace_cap < 0");
+    if (int rc = validate_bounds(count, n, m_ub, m_eq, c, A_ub, b_ub, A_eq, b_eq, lb, ub, n_upper, upper_idx, nints, ints, nbin, bin)) return rc;
     if (count == 0) return 0;
     HIP_TRY(hipSetDevice(b->device));
     const struct {
@@ -170,6 +226,8 @@ int solve_impl(yalps_milpdense *b, int32_t count, int32_t n, int32_t m_ub, int32
                     {"b_ub", m_ub ? b_ub->ptr : nullptr},
                     {"A_eq", m_eq && n ? A_eq->ptr : nullptr},
                     {"b_eq", m_eq ? b_eq->ptr : nullptr},
+                    {"lb", lb && n ? lb->ptr : nullptr},
+                    {"ub", ub && n_upper ? ub->ptr : nullptr},
                     {"x_out", n ? x_out : nullptr},
                     {"objective_out", objective_out},
                     {"status_out", status_out},
@@ -177,19 +235,21 @@ int solve_impl(yalps_milpdense *b, int32_t count, int32_t n, int32_t m_ub, int32
                     {"node_pivots_out", node_pivots_out},
                     {"root_pivots_out", root_pivots_out}};
     for (const auto &a : pointers)
-        if (int rc = check_pointer(b, a.name, a.p)) return rc;
+        if (int rc = check_pointer(b, entry, a.name, a.p)) return rc;
 
     hipStream_t s = b->stream;
-    const int32_t w = n + 1, h = 1 + m_ub + 2 * m_eq + nbin, hmax = h + 2 * nints;
+    const int32_t w = n + 1, h = 1 + m_ub + 2 * m_eq + n_upper + nbin, hmax = h + 2 * nints;
     const size_t cnt = (size_t)count, heven = ((size_t)h + 1) & ~(size_t)1, perm = (size_t)w + (size_t)h;
     const bool aux = lp_class(w, h) == HBM_CLASS && lp_aux_hbm(w, h);
 
     // ---- the root pass: the description and the binary list behind it, one launch per pass, tableaux kept for the trees
-    const size_t call_bytes = (sizeof(MilpDenseCall) + 15) & ~(size_t)15;
-    if (int rc = ensure(b->call, call_bytes + sizeof(int32_t) * (size_t)nbin)) return rc;
+    // (a bounded call: the longer description, and behind the binary list the bound rows' index list and the kind bytes)
+    const size_t desc_bytes = bounds ? sizeof(MilpDenseBoundsCall) : sizeof(MilpDenseCall), call_bytes = (desc_bytes + 15) & ~(size_t)15;
+    const size_t bin_bytes = sizeof(int32_t) * (size_t)nbin, idx_bytes = sizeof(int32_t) * (size_t)n_upper;
+    if (int rc = ensure(b->call, call_bytes + bin_bytes + (bounds ? idx_bytes + (size_t)n : 0))) return rc;
     b->q.keep = true;
     if (int rc = ensure_outputs(b->q, cnt, heven * cnt, perm * cnt, (size_t)w * (size_t)h * cnt)) return rc;
-    MilpDenseCall D{};
+    MilpDenseBoundsCall D{};
     D.n = n, D.m_ub = m_ub, D.m_eq = m_eq, D.n_bin = nbin;
     D.aux_hbm = aux ? 1 : 0;
     D.sign = maximize ? 1.0 : -1.0;
@@ -201,15 +261,29 @@ int solve_impl(yalps_milpdense *b, int32_t count, int32_t n, int32_t m_ub, int32
     D.A_eq = operand(A_eq, false);
     D.b_eq = operand(b_eq, true);
     D.bin = reinterpret_cast<const int32_t *>(b->call.as<char>() + call_bytes);
-    HIP_TRY(hipMemcpyAsync(b->call.p, &D, sizeof D, hipMemcpyHostToDevice, s));
-    if (nbin) HIP_TRY(hipMemcpyAsync(b->call.as<char>() + call_bytes, bin, sizeof(int32_t) * (size_t)nbin, hipMemcpyHostToDevice, s));
+    std::vector<uint8_t> kinds; // 0 continuous, 1 integer, 2 binary
+    if (bounds) {
+        if (lb && n) D.lb = operand(lb, true);
+        if (ub && n_upper) D.ub = operand(ub, true);
+        D.n_upper = n_upper;
+        char *behind = b->call.as<char>() + call_bytes + bin_bytes;
+        D.upper_idx = reinterpret_cast<const int32_t *>(behind);
+        D.kind = reinterpret_cast<const uint8_t *>(behind + idx_bytes);
+        kinds.assign((size_t)n, 0);
+        for (int32_t k = 0; k < nints; k++) kinds[(size_t)ints[k]] = 1;
+        for (int32_t k = 0; k < nbin; k++) kinds[(size_t)bin[k]] = 2;
+        if (n_upper) HIP_TRY(hipMemcpyAsync(behind, upper_idx, idx_bytes, hipMemcpyHostToDevice, s));
+        if (n) HIP_TRY(hipMemcpyAsync(behind + idx_bytes, kinds.data(), (size_t)n, hipMemcpyHostToDevice, s));
+    }
+    HIP_TRY(hipMemcpyAsync(b->call.p, &D, desc_bytes, hipMemcpyHostToDevice, s));
+    if (nbin) HIP_TRY(hipMemcpyAsync(b->call.as<char>() + call_bytes, bin, bin_bytes, hipMemcpyHostToDevice, s));
     if (int rc = reset_status(b->q, s, cnt)) return rc;
-    HIP_TRY(hipStreamSynchronize(s)); // (D is on this frame, `bin` is the caller's)
+    HIP_TRY(hipStreamSynchronize(s)); // (D and kinds are on this frame, `bin` and `upper_idx` are the caller's)
     b->n = n, b->w = w, b->h0 = h, b->nints = nints;
 
     QueueRun run;
     const int rc = run_queue(
-        *b, b->q, kRootKernels, QueueText{"yalps_milpdense", true, "yalps_milpdense_solve", "MILP"}, cnt,
+        *b, b->q, bounds ? bounds_kernels().roots : kRootKernels, QueueText{"yalps_milpdense", true, entry, "MILP"}, cnt,
         [&](int32_t, int *iw, int *ih) { return *iw = w, *ih = h, checkCycles != 0; },
         [&](MilpDenseLaunch &a) { a.call = b->call.as<const MilpDenseCall>(); }, [] { return 0; },
         [&](const Launch &L, const std::string &kernel, int pass, int launch, long long hist_cap) {
@@ -285,7 +359,7 @@ int solve_impl(yalps_milpdense *b, int32_t count, int32_t n, int32_t m_ub, int32
         if (nodes_out) HIP_TRY(hipMemsetAsync(nodes_out, 0, sizeof(int64_t) * cnt, s));
         if (node_pivots_out) HIP_TRY(hipMemsetAsync(node_pivots_out, 0, sizeof(int64_t) * cnt, s));
     }
-    MilpSolutionArgs a{};
+    MilpBoundsSolutionArgs a{};
     a.n = n, a.h0 = h, a.hmax = hmax, a.overflow = YALPS_MILPDENSE_OVERFLOW;
     a.sign = D.sign, a.precision = precision;
     a.status = last.status.as<const int32_t>();
@@ -298,14 +372,20 @@ int solve_impl(yalps_milpdense *b, int32_t count, int32_t n, int32_t m_ub, int32
     a.status_out = status_out, a.nodes_out = reinterpret_cast<long long *>(nodes_out);
     a.node_pivots_out = reinterpret_cast<long long *>(node_pivots_out);
     HIP_TRY(hipEventRecord(b->ev0, s));
-    milp_dense_solution_kernel<SOLUTION_LANES><<<dim3((unsigned)count), dim3(SOLUTION_LANES), 0, s>>>(a);
+    if (bounds) {
+        a.c = D.c, a.lb = D.lb, a.kind = D.kind;
+        void (*const solution)(MilpBoundsSolutionArgs) = bounds_kernels().solution;
+        solution<<<dim3((unsigned)count), dim3(SOLUTION_LANES), 0, s>>>(a);
+    } else {
+        milp_dense_solution_kernel<SOLUTION_LANES><<<dim3((unsigned)count), dim3(SOLUTION_LANES), 0, s>>>(static_cast<const MilpSolutionArgs &>(a));
+    }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(b->ev1, s));
     HIP_TRY(hipStreamSynchronize(s));
     HIP_TRY(hipEventElapsedTime(&tm.epilogue, b->ev0, b->ev1));
     char line[192];
-    std::snprintf(line, sizeof line, "launch=%lld pass=0 kernel=milp_dense_solution_kernel<%d> class=-1 trees=%d grid=%d lds=0 hist_cap=0\n",
-                  (long long)t.launches++, SOLUTION_LANES, count, count);
+    std::snprintf(line, sizeof line, "launch=%lld pass=0 kernel=milp_dense_%ssolution_kernel<%d> class=-1 trees=%d grid=%d lds=0 hist_cap=0\n",
+                  (long long)t.launches++, bounds ? "bounds_" : "", SOLUTION_LANES, count, count);
     tm.epilogue_line = line;
     b->walked = walk;
     b->count = count;
@@ -320,6 +400,16 @@ void info_close(yalps_milpdense *b, const Times &tm) {
                   (long long)std::llround((tm.root + t.gpu_ms + tm.epilogue) * 1000.0), (long long)std::llround(tm.root * 1000.0),
                   (long long)std::llround(t.gpu_ms * 1000.0), (long long)std::llround(tm.epilogue * 1000.0));
     b->info = head + join_ids(tm.rerun_lps) + "] rerun_trees=[" + join_ids(t.rerun_ids) + "]\n" + tm.root_lines + t.lines + tm.epilogue_line;
+}
+
+void call_stats(const yalps_milpdense *d, const Times &tm, int64_t *out) {
+    if (!out) return;
+    out[0] = (int64_t)(d->t.rerun_ids.size() + tm.rerun_lps.size());
+    out[1] = std::max<int64_t>(d->t.launches, tm.launches);
+    out[2] = d->t.overflows;
+    out[3] = (int64_t)std::llround(tm.root * 1000.0);
+    out[4] = (int64_t)std::llround(d->t.gpu_ms * 1000.0);
+    out[5] = (int64_t)std::llround(tm.epilogue * 1000.0);
 }
 
 void destroy_impl(yalps_milpdense *b) {
@@ -343,6 +433,16 @@ int32_t yalps_milpdense_validate(int32_t count, int32_t n, int32_t m_ub, int32_t
                                  const yalps_milpdense_operand *A_eq, const yalps_milpdense_operand *b_eq, int32_t n_integers,
                                  const int32_t *integers, int32_t n_binaries, const int32_t *binaries) {
     return validate(count, n, m_ub, m_eq, c, A_ub, b_ub, A_eq, b_eq, n_integers, integers, n_binaries, binaries);
+}
+
+int32_t yalps_milpdense_validate_bounds(int32_t count, int32_t n, int32_t m_ub, int32_t m_eq, const yalps_milpdense_operand *c,
+                                        const yalps_milpdense_operand *A_ub, const yalps_milpdense_operand *b_ub,
+                                        const yalps_milpdense_operand *A_eq, const yalps_milpdense_operand *b_eq,
+                                        const yalps_milpdense_operand *lb, const yalps_milpdense_operand *ub, int32_t n_upper,
+                                        const int32_t *upper_idx, int32_t n_integers, const int32_t *integers, int32_t n_binaries,
+                                        const int32_t *binaries) {
+    return validate_bounds(count, n, m_ub, m_eq, c, A_ub, b_ub, A_eq, b_eq, lb, ub, n_upper, upper_idx, n_integers, integers, n_binaries,
+                           binaries);
 }
 
 int32_t yalps_milpdense_create(int32_t device, void *hip_stream, yalps_milpdense **out) {
@@ -371,19 +471,34 @@ int32_t yalps_milpdense_solve(yalps_milpdense *d, int32_t count, int32_t n, int3
                               int64_t *call_stats_out) {
     if (!d) return fail(YALPS_E_ARG, "yalps_milpdense_solve: handle is NULL");
     Times tm;
-    const int32_t rc = solve_impl(d, count, n, m_ub, m_eq, c, A_ub, b_ub, A_eq, b_eq, n_integers, integers, n_binaries, binaries, maximize,
+    const int32_t rc = solve_impl(d, "yalps_milpdense_solve", count, n, m_ub, m_eq, c, A_ub, b_ub, A_eq, b_eq, n_integers, integers, n_binaries, binaries, maximize,
                                   precision, maxPivots, checkCycles, tolerance, maxIterations, trace_cap, x_out, objective_out,
                                   status_out, nodes_out, node_pivots_out, root_pivots_out, tm);
     if (rc) d->count = 0; // (no last solve to read from)
     info_close(d, tm);
-    if (call_stats_out) {
-        call_stats_out[0] = (int64_t)(d->t.rerun_ids.size() + tm.rerun_lps.size());
-        call_stats_out[1] = std::max<int64_t>(d->t.launches, tm.launches);
-        call_stats_out[2] = d->t.overflows;
-        call_stats_out[3] = (int64_t)std::llround(tm.root * 1000.0);
-        call_stats_out[4] = (int64_t)std::llround(d->t.gpu_ms * 1000.0);
-        call_stats_out[5] = (int64_t)std::llround(tm.epilogue * 1000.0);
-    }
+    call_stats(d, tm, call_stats_out);
+    return rc;
+}
+
+int32_t yalps_milpdense_solve_bounds(yalps_milpdense *d, int32_t count, int32_t n, int32_t m_ub, int32_t m_eq,
+                                     const yalps_milpdense_operand *c, const yalps_milpdense_operand *A_ub,
+                                     const yalps_milpdense_operand *b_ub, const yalps_milpdense_operand *A_eq,
+                                     const yalps_milpdense_operand *b_eq, const yalps_milpdense_operand *lb,
+                                     const yalps_milpdense_operand *ub, int32_t n_upper, const int32_t *upper_idx,
+                                     int32_t n_integers, const int32_t *integers, int32_t n_binaries, const int32_t *binaries,
+                                     int32_t maximize, double precision, double maxPivots, int32_t checkCycles, double tolerance,
+                                     double maxIterations, int32_t trace_cap, double *x_out, double *objective_out,
+                                     int32_t *status_out, int64_t *nodes_out, int64_t *node_pivots_out, int64_t *root_pivots_out,
+                                     int64_t *call_stats_out) {
+    if (!d) return fail(YALPS_E_ARG, "yalps_milpdense_solve_bounds: handle is NULL");
+    Times tm;
+    const int32_t rc = solve_impl(d, "yalps_milpdense_solve_bounds", count, n, m_ub, m_eq, c, A_ub, b_ub, A_eq, b_eq, n_integers, integers,
+                                  n_binaries, binaries, maximize, precision, maxPivots, checkCycles, tolerance, maxIterations, trace_cap,
+                                  x_out, objective_out, status_out, nodes_out, node_pivots_out, root_pivots_out, tm, lb, ub, n_upper,
+                                  upper_idx);
+    if (rc) d->count = 0; // (no last solve to read from)
+    info_close(d, tm);
+    call_stats(d, tm, call_stats_out);
     return rc;
 }
 

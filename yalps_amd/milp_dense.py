@@ -1,7 +1,9 @@
 """The host side of tensors.milp_batch (numpy only; nothing here imports torch or touches the GPU): the integer sets of a
 call, and the fallback for trees that overflowed on the device -- tableauModel's tableau of one dense MILP (reference
 src/tableau.ts:47-137), its cells as the lockstep driver (_native.MilpBatch) takes them, and solution() (src/YALPS.ts:8-50)
-of a best tableau as a dense row."""
+of a best tableau as a dense row.  With variable bounds (milp_batch's lb, ub, upper) the tableau is the bounded one -- the
+right-hand sides moved by shift_sum with the effective lower bounds, the bound rows between the equality rows and the binary
+rows -- and the dense row is moved back."""
 import math
 
 import numpy as np
@@ -41,22 +43,76 @@ def integer_sets(n, integers=(), binaries=(), who="milp_batch"):
     return sorted(set(ints) | set(bins)), bins
 
 
-def largest_node_bytes(n, m_ub, m_eq, n_int, n_bin):
-    """8 * w * (h + 2 * n_int): the root's n_bin binary rows and two cuts per integer variable."""
-    return 8 * (n + 1) * (1 + m_ub + 2 * m_eq + n_bin + 2 * n_int)
+def largest_node_bytes(n, m_ub, m_eq, n_int, n_bin, k=0):
+    """8 * w * (h + 2 * n_int): the root's k bound rows and n_bin binary rows, and two cuts per integer variable."""
+    return 8 * (n + 1) * (1 + m_ub + 2 * m_eq + k + n_bin + 2 * n_int)
 
 
-def dense_tableau(c, A_ub=None, b_ub=None, A_eq=None, b_eq=None, binaries=(), maximize=False):
-    """The flat row-major (1 + m_ub + 2 m_eq + n_bin) x (n + 1) matrix of ONE MILP: row 0 = +0.0, sign * c (a product); rows
+SHIFT_LANES = 64
+
+
+def shift_sum(a, l):
+    """sum of a[j] * l[j] in the order the kernels use (lp_dense_kernel.cuh): every product rounded on its own; 64 partial sums,
+    each from +0.0 over the columns j = k (mod 64) in ascending j; then p[k] += p[k + s] for k < s, s = 32, 16, 8, 4, 2, 1."""
+    a, l = np.asarray(a, np.float64).reshape(-1), np.asarray(l, np.float64).reshape(-1)
+    if a.size != l.size:
+        raise ValueError("shift_sum: %d coefficients, %d bounds" % (a.size, l.size))
+    p = np.zeros(SHIFT_LANES, np.float64)
+    with np.errstate(all="ignore"):
+        for lo in range(0, a.size, SHIFT_LANES):  # (one round of the lanes: lane k adds column lo + k)
+            part = a[lo:lo + SHIFT_LANES] * l[lo:lo + SHIFT_LANES]
+            p[:part.size] = p[:part.size] + part
+        s = SHIFT_LANES // 2
+        while s:
+            p[:s] = p[:s] + p[s:2 * s]
+            s //= 2
+    return np.float64(p[0])
+
+
+def bound_rows(idx, binaries, everything, who="milp_batch"):
+    """The variables with a bound row: `idx` is the ascending list `upper` stands for (tensors._upper_set).  everything (upper
+    was True): every variable that is not binary; else the list as it is, and one that names a binary variable is a ValueError
+    -- a binary variable has no bound row of its own, its ub is not read."""
+    bins = set(int(j) for j in binaries)
+    if everything:
+        return [j for j in idx if j not in bins]
+    named = [j for j in idx if j in bins]
+    if named:
+        raise ValueError("%s: upper names variable %d, which is binary: a binary variable has no bound row of its own (its ub "
+                         "is not read)" % (who, named[0]))
+    return list(idx)
+
+
+def effective_lower(lb, integers=(), binaries=()):
+    """l_eff of ONE MILP: lb[j] at a continuous variable, ceil(lb[j]) at an integer one (IEEE: ceil(-0.5) is -0.0; NaN and the
+    infinities pass through), +0.0 at a binary one, whatever lb holds there.  None without lb."""
+    if lb is None:
+        return None
+    l = np.array(lb, np.float64).reshape(-1)
+    ints, bins = [int(j) for j in integers], [int(j) for j in binaries]
+    with np.errstate(all="ignore"):
+        l[ints] = np.ceil(l[ints])
+    l[bins] = 0.0
+    return l
+
+
+def dense_tableau(c, A_ub=None, b_ub=None, A_eq=None, b_eq=None, binaries=(), maximize=False, integers=(), lb=None, ub=None, upper=()):
+    """The flat row-major (1 + m_ub + 2 m_eq + k + n_bin) x (n + 1) matrix of ONE MILP: row 0 = +0.0, sign * c (a product); rows
     1 + i = b_ub[i], A_ub[i]; rows 1 + m_ub + 2k and the next = b_eq[k], A_eq[k] and their negations; then one row per binary
-    variable j in ascending order: column 0 and column j + 1 are 1.0."""
+    variable j in ascending order: column 0 and column j + 1 are 1.0.
+    Bounds: with lb, column 0 of every operand row is moved by shift_sum(row, l_eff), one subtraction (negated in the second
+    row of an equality), l_eff = effective_lower(lb, integers, binaries); and between the equality rows and the binary rows
+    come k = len(upper) rows, ascending: ub[j] - l_eff[j] (or ub[j]) in column 0, 1.0 in column j + 1."""
     c = np.asarray(c, np.float64)
     n = c.shape[0]
     m_ub = 0 if b_ub is None else len(b_ub)
     m_eq = 0 if b_eq is None else len(b_eq)
     bins = sorted(int(j) for j in binaries)
+    idx = sorted(int(j) for j in upper)
+    low = effective_lower(lb, integers, bins)
     h0 = 1 + m_ub + 2 * m_eq
-    m = np.zeros((h0 + len(bins), n + 1), np.float64)
+    hb = h0 + len(idx)
+    m = np.zeros((hb + len(bins), n + 1), np.float64)
     m[0, 1:] = np.float64(1.0 if maximize else -1.0) * c
     if m_ub:
         m[1:1 + m_ub, 0] = b_ub
@@ -65,22 +121,40 @@ def dense_tableau(c, A_ub=None, b_ub=None, A_eq=None, b_eq=None, binaries=(), ma
         A, b = np.asarray(A_eq, np.float64).reshape(m_eq, n), np.asarray(b_eq, np.float64)
         m[1 + m_ub:h0:2, 0], m[1 + m_ub:h0:2, 1:] = b, A
         m[2 + m_ub:h0:2, 0], m[2 + m_ub:h0:2, 1:] = -b, -A
+    with np.errstate(all="ignore"):
+        if low is not None:
+            for i in range(m_ub):
+                m[1 + i, 0] = m[1 + i, 0] - shift_sum(m[1 + i, 1:], low)
+            for k in range(m_eq):
+                v = m[1 + m_ub + 2 * k, 0] - shift_sum(m[1 + m_ub + 2 * k, 1:], low)
+                m[1 + m_ub + 2 * k, 0], m[2 + m_ub + 2 * k, 0] = v, -v
+        for t, j in enumerate(idx):
+            u = np.float64(np.asarray(ub, np.float64).reshape(-1)[j])
+            m[h0 + t, 0] = u - low[j] if low is not None else u
+            m[h0 + t, j + 1] = 1.0
     for q, j in enumerate(bins):
-        m[h0 + q, 0] = m[h0 + q, j + 1] = 1.0
+        m[hb + q, 0] = m[hb + q, j + 1] = 1.0
     return m.ravel()
 
 
-def packed_milp(lp, integers, binaries, maximize, options):
+def packed_milp(lp, integers, binaries, maximize, options, lb=None, ub=None, upper=()):
     """One dense MILP as _native.PackedMilps takes it: (width, height, row, col, val, integer columns, sign, options).
-    lp = (c, A_ub, b_ub, A_eq, b_eq); integers / binaries as integer_sets returns them."""
-    m = dense_tableau(*lp, binaries=binaries, maximize=maximize)
+    lp = (c, A_ub, b_ub, A_eq, b_eq); integers / binaries as integer_sets returns them; lb / ub / upper: its bounds
+    (dense_tableau)."""
+    m = dense_tableau(*lp, binaries=binaries, maximize=maximize, integers=integers, lb=lb, ub=ub, upper=upper)
     w = len(lp[0]) + 1
     h = m.size // w
     return (w, h, *_native.dense_cells(m, w, h), [j + 1 for j in integers], 1.0 if maximize else -1.0, options)
 
 
-def dense_solution(col0, pos, var, status, result, sign, precision, n):
-    """(x[n], objective) of one best tableau of width n + 1, as solution() reads it."""
+def dense_solution(col0, pos, var, status, result, sign, precision, n, c=None, low=None):
+    """(x[n], objective) of one best tableau of width n + 1, as solution() reads it.  low (effective_lower's l_eff) and c: the
+    answer in x' moved back, x = x' + low and objective = objective' + shift_sum(c, low), one addition each whatever the
+    status."""
+    if low is not None:
+        x, objective = dense_solution(col0, pos, var, status, result, sign, precision, n)
+        with np.errstate(all="ignore"):
+            return x + np.asarray(low, np.float64), float(np.float64(objective) + shift_sum(c, low))
     w = n + 1
     if status == "optimal" or (status == "timedout" and not math.isnan(result)):
         x = np.zeros(n, np.float64)

@@ -200,8 +200,8 @@ def linprog_batch(c, A_ub=None, b_ub=None, A_eq=None, b_eq=None, *, lb=None, ub=
     (scipy's lower.marginals).  Every "optimal" row satisfies, up to rounding,
         reduced_costs = c - A_ub^T ineqlin - A_eq^T eqlin - scatter(upper)    and
         objective = ineqlin . b_ub + eqlin . b_eq + upper . ub + reduced_costs . lb.
-    Out of scope: free variables (an lb entry of -inf is taken as it lies in memory, like every other value), per-LP `upper`
-    sets, and bounds in milp_batch (where the bound rows will come before the binary rows).
+    Out of scope: free variables (an lb entry of -inf is taken as it lies in memory, like every other value) and per-LP `upper`
+    sets.  milp_batch takes the same three arguments.
 
     See the module's docstring for the loading rule: torch first."""
     sets = {}
@@ -377,18 +377,20 @@ def linprog_objective_bounds(c, A_ub=None, b_ub=None, A_eq=None, b_eq=None, *, l
 
         dlb = g reduced_costs      dub = g upper, scattered into a [B, n] zero tensor (a variable `upper` does not list: 0)
 
-    A shared lb or ub receives the sum over the batch; a row that is not "optimal" contributes exact zeros.  Free variables,
-    per-LP `upper` sets and bounds in milp_batch are out of scope, as in linprog_batch."""
+    A shared lb or ub receives the sum over the batch; a row that is not "optimal" contributes exact zeros.  Free variables
+    and per-LP `upper` sets are out of scope, as in linprog_batch."""
     options = dict(maximize=maximize, precision=precision, max_pivots=max_pivots, check_cycles=check_cycles)
     given = {"c": c, "A_ub": A_ub, "b_ub": b_ub, "A_eq": A_eq, "b_eq": b_eq, "lb": lb, "ub": ub}
     return _objective_call("linprog_objective_bounds", options, given, upper)
 
 
-def _solve_on_host(device, rows, given, batched, B, ints, bins, maximize, options, out):
+def _solve_on_host(device, rows, given, batched, B, ints, bins, maximize, options, out, bounds=(None, None), bounds_batched=(False, False),
+                   upper=()):
     """The trees `rows` of a milp_batch call through the lockstep driver (_native.MilpBatch.solve), as solve.milptree_solve
     sends its overflows: their operands are gathered on the device and copied to the host, their tableaux built there
     (milp_dense.packed_milp), and x / objective / status / nodes written into the output tensors `out`.  node_pivots of such
-    a row is -1: the lockstep driver does not count the pivots of the nodes it consumes."""
+    a row is -1: the lockstep driver does not count the pivots of the nodes it consumes.  bounds = (lb, ub) tensors or None:
+    gathered likewise, the tableaux are the bounded ones and x / objective are moved back (milp_dense.dense_solution)."""
     from . import milp_dense
     idx = torch.tensor(rows, dtype=torch.int64, device=device)
     host = []
@@ -397,8 +399,11 @@ def _solve_on_host(device, rows, given, batched, B, ints, bins, maximize, option
             host.append(None)
         else:
             host.append((t.index_select(0, idx) if has_batch else t).cpu().numpy())
+    lbs, ubs = (None if t is None else (t.index_select(0, idx) if has_batch else t).cpu().numpy() for t, has_batch in zip(bounds, bounds_batched))
     pick = lambda k, a, has_batch: None if a is None else (a[k] if has_batch else a)
-    milps = [milp_dense.packed_milp(tuple(pick(k, a, hb) for a, hb in zip(host, batched)), ints, bins, maximize, options)
+    low_of = lambda k: milp_dense.effective_lower(pick(k, lbs, bounds_batched[0]), ints, bins)
+    milps = [milp_dense.packed_milp(tuple(pick(k, a, hb) for a, hb in zip(host, batched)), ints, bins, maximize, options,
+                                    lb=pick(k, lbs, bounds_batched[0]), ub=pick(k, ubs, bounds_batched[1]), upper=upper)
              for k in range(len(rows))]
     batch = _fallbacks.get(device.index)
     if batch is None:
@@ -409,7 +414,8 @@ def _solve_on_host(device, rows, given, batched, B, ints, bins, maximize, option
     xs, objs = [], []
     for k, (st, res) in enumerate(zip(statuses, results)):
         _, col0, pos, var = batch.solution(k)
-        x, obj = milp_dense.dense_solution(col0, pos, var, st, float(res), sign, options["precision"], n)
+        x, obj = milp_dense.dense_solution(col0, pos, var, st, float(res), sign, options["precision"], n,
+                                           c=pick(k, host[0], batched[0]), low=low_of(k))
         xs.append(x)
         objs.append(obj)
     dev = lambda a, dtype: torch.as_tensor(a, dtype=dtype).to(device)
@@ -421,8 +427,8 @@ def _solve_on_host(device, rows, given, batched, B, ints, bins, maximize, option
     out.node_pivots.index_fill_(0, idx, -1)
 
 
-def milp_batch(c, A_ub=None, b_ub=None, A_eq=None, b_eq=None, *, integers=(), binaries=(), maximize=False, precision=1e-8,
-               max_pivots=8192, check_cycles=False, tolerance=0.0, max_iterations=32768, stats=None):
+def milp_batch(c, A_ub=None, b_ub=None, A_eq=None, b_eq=None, *, lb=None, ub=None, upper=True, integers=(), binaries=(), maximize=False,
+               precision=1e-8, max_pivots=8192, check_cycles=False, tolerance=0.0, max_iterations=32768, stats=None):
     """Solves B dense MILPs of one shape in one call, from device tensors to device tensors, every branch-and-cut tree walked
     on the device:
 
@@ -465,20 +471,46 @@ def milp_batch(c, A_ub=None, b_ub=None, A_eq=None, b_eq=None, *, integers=(), bi
     two cuts per integer variable -- above 4 MiB (solve() is the route for such models).  stats (a dict, optional) receives
     "launches", "reruns", "overflows", "kernels" and "gpu_ms" of the call (and "root_ms", "tree_ms", "epilogue_ms", its parts).
 
+    Bounds.  lb, ub and upper are linprog_batch's: float64 device tensors [B, n] or [n] read through their strides, lb REPLACES
+    x >= 0 (negative entries are legal), `upper` is a HOST sequence of the variables whose ub entry is read, or True, shared by
+    the batch; values are taken as they lie.  Three rules come from the variables being integer, all decided on the host:
+      1. the effective lower bound l_eff[j] is lb[j] at a continuous variable, ceil(lb[j]) at an integer one (x integer and
+         x >= lb mean x >= ceil(lb); IEEE ceil: -0.5 gives -0.0, NaN and the infinities pass through) and +0.0 at a binary
+         one, where lb is not read.  The substitution x = l_eff + x' keeps "x' integral <=> x integral", so the trees branch
+         on x'.  Everything linprog_batch does with lb is done with l_eff: every right-hand side moves by shift_sum(row, l_eff)
+         in linprog_batch's order of summation, a bound row holds ub[j] - l_eff[j], x = x' + l_eff and objective = objective' +
+         shift_sum(c, l_eff).
+      2. a binary variable has no bound row of its own and its ub is not read: upper=True means every variable that is not
+         binary, and an explicit `upper` that names a binary variable raises ValueError.
+      3. rows: linprog_batch's, then the k = len(upper) bound rows in ascending index, then the binary rows: height
+         1 + m_ub + 2 m_eq + k + len(binaries), and the 4 MiB limit counts the bound rows.
+    For finite data row i is solve() of the equivalent model in x' (linprog_batch's with the shifted right-hand sides, h<j>
+    {"max": ub[j] - l_eff[j]}, "integers" / "binaries" as given), moved back.  With no integer and no binary variable x, objective,
+    status and root_pivots are linprog_batch(..., lb=, ub=, upper=)'s bit for bit.  Without lb and ub the call launches the
+    kernels it always launched and returns the same bits.  Nothing of size B x n is materialised.  Out of scope: free
+    variables, per-MILP sets, and duals (a node's duals are not the model's).
+
     See the module's docstring for the loading rule: torch first."""
     from . import milp_dense
     sets = {}
 
     def size(n, m_ub, m_eq):
         ints, bins = sets["ints"], sets["bins"] = milp_dense.integer_sets(n, integers, binaries)
-        nbytes = milp_dense.largest_node_bytes(n, m_ub, m_eq, len(ints), len(bins))
+        idx = sets["upper"] = milp_dense.bound_rows(_upper_set(n, upper, ub is not None, "milp_batch"), bins, upper is True)
+        nbytes = milp_dense.largest_node_bytes(n, m_ub, m_eq, len(ints), len(bins), len(idx))
         if nbytes > _native.MILPDENSE_MAX_BYTES:
             raise ValueError("milp_batch: the largest possible node, %d x %d doubles (%d bytes: %d rows and two cuts for each of %d "
                              "integer variables), is above the batch limit of %d bytes; solve() is the route for such models"
-                             % (nbytes // (8 * (n + 1)), n + 1, nbytes, 1 + m_ub + 2 * m_eq + len(bins), len(ints), _native.MILPDENSE_MAX_BYTES))
+                             % (nbytes // (8 * (n + 1)), n + 1, nbytes, 1 + m_ub + 2 * m_eq + len(idx) + len(bins), len(ints), _native.MILPDENSE_MAX_BYTES))
 
-    B, n, m_ub, m_eq, device, operands, given, batched = _call_operands("milp_batch", c, A_ub, b_ub, A_eq, b_eq, size)
-    ints, bins = sets["ints"], sets["bins"]
+    B, n, m_ub, m_eq, device, operands, given, batched, bounds = _call_operands("milp_batch", c, A_ub, b_ub, A_eq, b_eq, size,
+                                                                                vectors={"lb": lb, "ub": ub})
+    ints, bins, idx = sets["ints"], sets["bins"], sets["upper"]
+    more = {}
+    if lb is not None or ub is not None:
+        # (a bound tensor without an element -- n = 0 -- stays a descriptor, so that the call still is the bounded one)
+        more = dict(lb=None if lb is None else bounds["lb"] or (None, 0, 0, 0), ub=None if ub is None else bounds["ub"] or (None, 0, 0, 0),
+                    upper=idx)
     out = MilpBatchResult(torch.empty((B, n), dtype=torch.float64, device=device), torch.empty((B,), dtype=torch.float64, device=device),
                           torch.empty((B,), dtype=torch.int32, device=device), *(torch.empty((B,), dtype=torch.int64, device=device) for _ in range(3)))
     ptr = lambda t: t.data_ptr() if t.numel() else None
@@ -491,7 +523,7 @@ def milp_batch(c, A_ub=None, b_ub=None, A_eq=None, b_eq=None, *, integers=(), bi
         call = handle.solve(B, n, m_ub, m_eq, operands, integers=ints, binaries=bins, maximize=maximize, precision=precision,
                             max_pivots=max_pivots, check_cycles=check_cycles, tolerance=tolerance, max_iterations=max_iterations,
                             x=ptr(out.x), objective=ptr(out.objective), status=ptr(out.status), nodes=ptr(out.nodes),
-                            node_pivots=ptr(out.node_pivots), root_pivots=ptr(out.root_pivots))
+                            node_pivots=ptr(out.node_pivots), root_pivots=ptr(out.root_pivots), **more)
         over = handle.overflowed() if call["overflows"] else []
         if stats is not None:
             info = handle.info()
@@ -500,5 +532,6 @@ def milp_batch(c, A_ub=None, b_ub=None, A_eq=None, b_eq=None, *, integers=(), bi
         if over:
             options = {"precision": float(precision), "maxPivots": float(max_pivots), "checkCycles": bool(check_cycles),
                        "tolerance": float(tolerance), "timeout": float("inf"), "maxIterations": float(max_iterations)}
-            _solve_on_host(device, over, given, batched, B, ints, bins, bool(maximize), options, out)
+            _solve_on_host(device, over, given, batched, B, ints, bins, bool(maximize), options, out, (lb, ub),
+                           tuple(t is not None and t.dim() == 2 for t in (lb, ub)), idx)
     return out
