@@ -41,7 +41,32 @@
  *     coefficient, 1.  Width n + 1, height 1 + m_ub + 2 m_eq + n_upper, which is what YALPS_LPDENSE_MAX_BYTES bounds.
  *   read-out: x = x' + lb, one addition per element whatever the status (NaN stays NaN, +inf stays +inf);
  *     objective = objective' + shift_sum(c, lb) with the caller's c, one addition after the rounding.
- * Free variables are out of scope: an lb entry of -inf is taken as it lies in memory, like every other value.
+ *
+ * Free variables (yalps_lpdense_solve_free).  The n_free variables free_idx names (host memory, ascending, shared by the call) have
+ * no lower bound.  Freeness is host data and is not inferred on the device: at a variable free_idx does not name, an lb entry
+ * of -inf is taken as it lies in memory, like every other value.  A free variable j is split as x[j] = p[j] - q[j] with p, q >= 0, built on the device:
+ *   p keeps column 1 + j; the twins q are n_free generated columns behind the n originals in ascending j, column 1 + n + t for
+ *     free_idx[t].  Width 1 + n + n_free, height as above, and YALPS_LPDENSE_MAX_BYTES bounds 8 * width * height.
+ *   a twin cell is the IEEE negation of the cell of column 1 + j in the same row, in every operand row, as `m[...] = -coef` makes
+ *     it: row 0 holds -(sign * c[j]), a zero becomes -0.0, the negated row of an equality holds A_eq[k, j] again.  It is a negation
+ *     of the value read, not a second product.
+ *   in the bound row of a free variable that upper_idx also lists the twin cell is -1.0, in every other bound row +0.0: x <= ub
+ *     with no lower bound.
+ *   lb is NOT read at a free variable: the effective lower bound l_eff[j] is +0.0 there and lb[j] elsewhere.  The product
+ *     a[j] * (+0.0) is still formed and added in shift_sum (a non-finite coefficient gives NaN there), which runs over the n
+ *     original columns only, in its one order; twins take no part in it.  A bound row of a free variable holds ub[j] - (+0.0) with
+ *     lb given and ub[j] without.  Permutations are the identity over width + height; the padding columns of the pitch are +0.0.
+ *   read-out: optimal: x[j] = v(p) - v(q), v the rule of x_out for each column on its own (basic and above precision: the value
+ *     rounded to precision, else +0.0), one subtraction, then + l_eff[j] where lb is given; unbounded: +inf at the unbounded
+ *     column, so x[free_idx[t]] = 0.0 - inf = -inf where that column is a twin; infeasible / cycled: NaN.
+ *     objective = -sign * result + shift_sum(c, l_eff).
+ *   marginals: ineqlin, eqlin and upper are unchanged (rows; pos[w + r] with the new width w).  For a free variable
+ *     reduced[j] = s * (cost_nb(1 + j) - cost_nb(1 + n + t)) + 0.0 with cost_nb(v) = cost(pos[v]) where pos[v] < w, else 0: the full
+ *     signed reduced cost, about 0 at an optimum, so that reduced = c - A_ub^T ineqlin - A_eq^T eqlin - scatter(upper) holds at
+ *     every j.  Other variables keep their formula.
+ * For finite data an LP is solve() of the equivalent model: the bounded call's model in x', plus one variable q<j> per free
+ * variable behind all x<j>, in ascending j, listing the negated coefficient of every constraint x<j> lists, and -c[j].
+ * Per-LP sets of free variables are out of scope.
  */
 #ifndef YALPS_LPDENSE_H
 #define YALPS_LPDENSE_H
@@ -94,6 +119,15 @@ int32_t yalps_lpdense_validate_bounds(int32_t count, int32_t n, int32_t m_ub, in
                                       const yalps_lpdense_operand *A_eq, const yalps_lpdense_operand *b_eq,
                                       const yalps_lpdense_operand *lb, const yalps_lpdense_operand *ub, int32_t n_upper,
                                       const int32_t *upper_idx);
+
+/* yalps_lpdense_validate_bounds with the free variables of yalps_lpdense_solve_free, host only: the size limit with the width
+ * that counts the n_free twin columns, n_free < 0, a NULL free_idx with n_free > 0, an index of free_idx (host memory) outside
+ * 0 .. n-1 or not ascending. */
+int32_t yalps_lpdense_validate_free(int32_t count, int32_t n, int32_t m_ub, int32_t m_eq, const yalps_lpdense_operand *c,
+                                    const yalps_lpdense_operand *A_ub, const yalps_lpdense_operand *b_ub,
+                                    const yalps_lpdense_operand *A_eq, const yalps_lpdense_operand *b_eq,
+                                    const yalps_lpdense_operand *lb, const yalps_lpdense_operand *ub, int32_t n_upper,
+                                    const int32_t *upper_idx, int32_t n_free, const int32_t *free_idx);
 
 /* Solves LPs 0 .. count-1.  maximize != 0: maximise c . x, else minimise.  precision / maxPivots (may be +Infinity) /
  * checkCycles hold for the whole call.  keep_tableaux != 0 also keeps every final matrix on the device for
@@ -158,6 +192,20 @@ int32_t yalps_lpdense_solve_bounds(yalps_lpdense *d, int32_t count, int32_t n, i
                                    double precision, double maxPivots, int32_t checkCycles, int32_t keep_tableaux, double *x_out,
                                    double *objective_out, int32_t *status_out, int64_t *pivots_out, double *ineqlin_out,
                                    double *eqlin_out, double *reduced_out, double *upper_out, float *gpu_ms_out);
+
+/* yalps_lpdense_solve_bounds (which is this call with n_free = 0, and writes the bits it wrote before) with free variables; see
+ * "Free variables" at the top.  free_idx: HOST memory, n_free ascending indices (copied before the call returns).  With
+ * n_free > 0 the call runs lp_dense_free_kernel (libyalps_lpdense_free.so, which this library links), with or without lb / ub
+ * (NULL descriptors: absent).  x_out and reduced_out stay [count][n]; yalps_lpdense_solution and yalps_lpdense_tableau give the
+ * wider tableau: width 1 + n + n_free. */
+int32_t yalps_lpdense_solve_free(yalps_lpdense *d, int32_t count, int32_t n, int32_t m_ub, int32_t m_eq,
+                                 const yalps_lpdense_operand *c, const yalps_lpdense_operand *A_ub,
+                                 const yalps_lpdense_operand *b_ub, const yalps_lpdense_operand *A_eq,
+                                 const yalps_lpdense_operand *b_eq, const yalps_lpdense_operand *lb,
+                                 const yalps_lpdense_operand *ub, int32_t n_upper, const int32_t *upper_idx, int32_t n_free,
+                                 const int32_t *free_idx, int32_t maximize, double precision, double maxPivots, int32_t checkCycles,
+                                 int32_t keep_tableaux, double *x_out, double *objective_out, int32_t *status_out, int64_t *pivots_out,
+                                 double *ineqlin_out, double *eqlin_out, double *reduced_out, double *upper_out, float *gpu_ms_out);
 
 /* LP i of the last solve, copied to the HOST (for tests and debugging): what solution() reads -- column 0 (height
  * doubles) and both permutations (width + height int32 each).  NULL pointers are skipped. */

@@ -76,7 +76,7 @@ LPDENSE_LIB_PATH = os.environ.get("YALPS_LPDENSE_LIB") or os.path.join(HERE, "li
 SYMBOLS_LPDENSE = (
     "yalps_lpdense_last_error", "yalps_lpdense_create", "yalps_lpdense_destroy", "yalps_lpdense_validate", "yalps_lpdense_solve",
     "yalps_lpdense_solve_duals", "yalps_lpdense_solution", "yalps_lpdense_tableau", "yalps_lpdense_info",
-    "yalps_lpdense_validate_bounds", "yalps_lpdense_solve_bounds",
+    "yalps_lpdense_validate_bounds", "yalps_lpdense_solve_bounds", "yalps_lpdense_validate_free", "yalps_lpdense_solve_free",
 )
 LPDENSE_MAX_BYTES = 4 << 20  # YALPS_LPDENSE_MAX_BYTES
 MILPDENSE_LIB_PATH = os.environ.get("YALPS_MILPDENSE_LIB") or os.path.join(HERE, "libyalps_milpdense.so")
@@ -977,6 +977,9 @@ _BATCH_LIBS["yalps_lpdense"] = (LPDENSE_LIB_PATH, {
         "validate_bounds": (_I32, [_I32, _I32, _I32, _I32, _DOP, _DOP, _DOP, _DOP, _DOP, _DOP, _DOP, _I32, _VP]),
         "solve_bounds": (_I32, [_VP, _I32, _I32, _I32, _I32, _DOP, _DOP, _DOP, _DOP, _DOP, _DOP, _DOP, _I32, _VP, _I32, C.c_double,
                                 C.c_double, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.POINTER(C.c_float)]),
+        "validate_free": (_I32, [_I32, _I32, _I32, _I32, _DOP, _DOP, _DOP, _DOP, _DOP, _DOP, _DOP, _I32, _VP, _I32, _VP]),
+        "solve_free": (_I32, [_VP, _I32, _I32, _I32, _I32, _DOP, _DOP, _DOP, _DOP, _DOP, _DOP, _DOP, _I32, _VP, _I32, _VP, _I32, C.c_double,
+                              C.c_double, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.POINTER(C.c_float)]),
         "solution": (_I32, [_VP, _I32, _VP, _VP, _VP]), "tableau": (_I32, [_VP, _I32, _VP])})
 
 
@@ -1016,6 +1019,16 @@ def lpdense_validate_bounds(count, n, m_ub, m_eq, operands, lb=None, ub=None, up
                                                               lbp, ubp, k, idx.ctypes.data))
 
 
+def lpdense_validate_free(count, n, m_ub, m_eq, operands, lb=None, ub=None, upper=(), free=()):
+    """The host-only argument checks of yalps_lpdense_solve_free: lpdense_validate_bounds' with the width that counts the
+    len(free) twin columns, plus the index list of the free variables."""
+    ops = _dense_operands(operands)
+    lbp, ubp, k, idx = _dense_bounds(lb, ub, upper)
+    fidx = np.ascontiguousarray(free, np.int32).reshape(-1)
+    lpdense_check(lpdense_lib().yalps_lpdense_validate_free(int(count), int(n), int(m_ub), int(m_eq), *(C.byref(o) for o in ops),
+                                                            lbp, ubp, k, idx.ctypes.data, int(fidx.size), fidx.ctypes.data))
+
+
 class LpDense:
     """Batches of dense LPs of one shape, operands and answers in device memory (yalps_lpdense_*).  Pointers are plain
     integers (a tensor's data_ptr()); nothing here imports torch.  Belongs to one thread at a time."""
@@ -1028,7 +1041,7 @@ class LpDense:
 
     def solve(self, count, n, m_ub, m_eq, operands, maximize=False, precision=1e-8, max_pivots=8192.0, check_cycles=False,
               keep_tableaux=False, x=None, objective=None, status=None, pivots=None, ineqlin=None, eqlin=None, reduced=None,
-              lb=None, ub=None, upper=(), upper_out=None):
+              lb=None, ub=None, upper=(), upper_out=None, free=()):
         """operands = (c, A_ub, b_ub, A_eq, b_eq), each (device pointer, batch, row, col strides in doubles) or None where it
         has no element; x / objective / status / pivots: device pointers of contiguous float64 [count][n], float64 [count],
         int32 [count], int64 [count], or None; ineqlin / eqlin / reduced: the marginals (yalps_lpdense_solve_duals), device
@@ -1036,14 +1049,21 @@ class LpDense:
         yalps_lpdense_solve.  lb / ub: (device pointer, batch, row, col) of the bounds x >= lb and x[j] <= ub[j] for the
         ascending indices j of `upper` (a host sequence), or None; upper_out: device pointer of contiguous float64
         [count][len(upper)], the bound rows' marginals, or None -- with lb or ub given the call is yalps_lpdense_solve_bounds, and
-        the tableau is len(upper) rows taller.  The outputs are complete on return.  Returns gpu_ms."""
+        the tableau is len(upper) rows taller.  free: the ascending indices of the variables without a lower bound (a host
+        sequence) -- with any the call is yalps_lpdense_solve_free, with or without lb / ub, and the tableau is len(free) columns
+        wider.  The outputs are complete on return.  Returns gpu_ms."""
         ops = _dense_operands(operands)
         ms = C.c_float()
         self.shape = None
         head = (self.handle, int(count), int(n), int(m_ub), int(m_eq), *(C.byref(o) for o in ops), int(bool(maximize)), float(precision),
                 float(max_pivots), int(bool(check_cycles)), int(bool(keep_tableaux)), x, objective, status, pivots)
         k = 0
-        if lb is not None or ub is not None:
+        if len(free):
+            lbp, ubp, k, idx = _dense_bounds(lb, ub, upper)
+            fidx = np.ascontiguousarray(free, np.int32).reshape(-1)
+            lpdense_check(lpdense_lib().yalps_lpdense_solve_free(*head[:10], lbp, ubp, k, idx.ctypes.data, int(fidx.size), fidx.ctypes.data,
+                                                                 *head[10:], ineqlin, eqlin, reduced, upper_out, C.byref(ms)))
+        elif lb is not None or ub is not None:
             lbp, ubp, k, idx = _dense_bounds(lb, ub, upper)
             lpdense_check(lpdense_lib().yalps_lpdense_solve_bounds(*head[:10], lbp, ubp, k, idx.ctypes.data, *head[10:], ineqlin, eqlin,
                                                                    reduced, upper_out, C.byref(ms)))
@@ -1053,7 +1073,7 @@ class LpDense:
             lpdense_check(lpdense_lib().yalps_lpdense_solve(*head, C.byref(ms)))
         else:
             lpdense_check(lpdense_lib().yalps_lpdense_solve_duals(*head, ineqlin, eqlin, reduced, C.byref(ms)))
-        self.shape = (int(count), int(n) + 1, 1 + int(m_ub) + 2 * int(m_eq) + k)
+        self.shape = (int(count), int(n) + 1 + len(free), 1 + int(m_ub) + 2 * int(m_eq) + k)
         return ms.value
 
     def _check(self, i):

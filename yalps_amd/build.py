@@ -9,6 +9,7 @@
   yalps_amd/libyalps_milptree.so  batches of MILPs, every tree walked on the device (include/yalps_milptree.h) hipcc
   yalps_amd/libyalps_lpdense.so   batches of dense LPs of one shape, device tensors in and out (include/yalps_lpdense.h) hipcc
   yalps_amd/libyalps_lpdense_bounds.so   its kernels with variable bounds, linked by libyalps_lpdense.so             hipcc
+  yalps_amd/libyalps_lpdense_free.so     its kernels with free variables, linked by libyalps_lpdense.so              hipcc
   yalps_amd/libyalps_milpdense.so batches of dense MILPs of one shape, device tensors in and out, trees walked on the device (include/yalps_milpdense.h) hipcc
   yalps_amd/libyalps_milpdense_bounds.so its root and solution kernels with variable bounds, linked by libyalps_milpdense.so hipcc
   yalps_amd/napi/yalps_napi.node  thin N-API shim over the C ABI (optional)  g++
@@ -70,6 +71,9 @@ LPDENSE_DEPS = [os.path.join(CSRC, "lp_dense_kernel.cuh")] + QUEUE_DEPS
 LIB_LPDENSE_BOUNDS = os.path.join(HERE, "libyalps_lpdense_bounds.so")
 LPDENSE_BOUNDS_SRC = os.path.join(CSRC, "lp_dense_bounds.hip")
 LPDENSE_HEADER = os.path.join(ROOT, "include", "yalps_lpdense.h")
+# and with free variables, likewise a code object of their own that libyalps_lpdense.so links
+LIB_LPDENSE_FREE = os.path.join(HERE, "libyalps_lpdense_free.so")
+LPDENSE_FREE_SRC = os.path.join(CSRC, "lp_dense_free.hip")
 # the dense MILP library: a dense root pass, milp_tree_kernel compiled again on the tree pass both libraries share, and solution() on the device
 LIB_MILPDENSE = os.path.join(HERE, "libyalps_milpdense.so")
 MILPDENSE_SRC = os.path.join(CSRC, "milp_dense.hip")
@@ -169,7 +173,7 @@ def check_register_budgets(lib=LIB, min_resident=15):
                 bad.append("%s: sgpr_spill_count %s, bound %d" % (name, md.get("sgpr_spill_count"), RESIDENT2_SGPR_SPILLS[shape]))
         if any(tag in name for tag in NO_SCRATCH) and int(md["private_segment_fixed_size"]) != 0:
             bad.append("%s: private_segment_fixed_size %s (scratch)" % (name, md["private_segment_fixed_size"]))
-        queue = "lp_dense_bounds_kernel" in name or "lp_batch_kernel" in name or "milp_node_kernel" in name or "lp_variants_kernel" in name or "lp_sens_kernel" in name or "lp_warm_kernel" in name or "milp_tree_kernel" in name or "lp_dense_kernel" in name or "milp_dense_root_kernel" in name or "milp_dense_bounds_root_kernel" in name
+        queue = "lp_dense_free_kernel" in name or "lp_dense_bounds_kernel" in name or "lp_batch_kernel" in name or "milp_node_kernel" in name or "lp_variants_kernel" in name or "lp_sens_kernel" in name or "lp_warm_kernel" in name or "milp_tree_kernel" in name or "lp_dense_kernel" in name or "milp_dense_root_kernel" in name or "milp_dense_bounds_root_kernel" in name
         if queue and int(md["agpr_count"]) != 0:
             bad.append("%s: agpr_count %s" % (name, md["agpr_count"]))
         # its dynamic LDS block (tableau and pivot row, swept 16 bytes at a time) starts where the static LDS ends
@@ -278,11 +282,14 @@ def build_milptree(force=False, verbose=False):
 
 def build_lpdense(force=False, verbose=False):
     """libyalps_lpdense_bounds.so: lp_dense_bounds.hip alone, the six lp_dense_bounds_kernel forms (they pass the same register
-    budget: "lp_dense" is under NO_SCRATCH); then libyalps_lpdense.so: lp_dense.hip alone, linking it."""
+    budget: "lp_dense" is under NO_SCRATCH); libyalps_lpdense_free.so: lp_dense_free.hip alone, the six lp_dense_free_kernel forms,
+    under the same budget; then libyalps_lpdense.so: lp_dense.hip alone, linking both."""
     bounds = build_single_unit(LPDENSE_BOUNDS_SRC, LIB_LPDENSE_BOUNDS, LPDENSE_DEPS, LPDENSE_HEADER,
                                ("lp_dense_bounds_kernel",), force, verbose)
-    return build_single_unit(LPDENSE_SRC, LIB_LPDENSE, LPDENSE_DEPS + [bounds], LPDENSE_HEADER,
-                             ("lp_dense_kernel",), force, verbose, link=(bounds,))
+    free = build_single_unit(LPDENSE_FREE_SRC, LIB_LPDENSE_FREE, LPDENSE_DEPS, LPDENSE_HEADER,
+                             ("lp_dense_free_kernel",), force, verbose)
+    return build_single_unit(LPDENSE_SRC, LIB_LPDENSE, LPDENSE_DEPS + [bounds, free], LPDENSE_HEADER,
+                             ("lp_dense_kernel",), force, verbose, link=(bounds, free))
 
 
 def build_milpdense(force=False, verbose=False):

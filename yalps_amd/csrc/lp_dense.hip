@@ -7,6 +7,7 @@
 // yalps_lpdense_solution asks for them.
 // A call with bounds (lb / ub) runs lp_dense_bounds_kernel, whose six forms are libyalps_lpdense_bounds.so's: this library links
 // it and takes the kernels' pointers from yalps_lpdense_bounds_forms, so its own code object holds the boundless forms alone.
+// A call with free variables (n_free > 0) runs lp_dense_free_kernel, libyalps_lpdense_free.so's six forms, taken the same way.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -35,6 +36,7 @@ const KernelTable<DenseLaunch> kDenseKernels = QUEUE_KERNEL_TABLE(lp_dense_kerne
 } // namespace
 
 extern "C" void yalps_lpdense_bounds_forms(void *out[6]); // lp_dense_bounds.hip
+extern "C" void yalps_lpdense_free_forms(void *out[6]);   // lp_dense_free.hip
 
 namespace {
 // the same table over libyalps_lpdense_bounds.so's kernels
@@ -49,13 +51,26 @@ const KernelTable<DenseLaunch> &bounds_kernels() {
     }();
     return table;
 }
+
+// and over libyalps_lpdense_free.so's
+const KernelTable<DenseLaunch> &free_kernels() {
+    static const KernelTable<DenseLaunch> table = [] {
+        KernelTable<DenseLaunch> t = kDenseKernels;
+        t.name = "lp_dense_free_kernel";
+        void *fn[6];
+        yalps_lpdense_free_forms(fn);
+        for (int k = 0; k < 6; k++) t.forms[k].fn = reinterpret_cast<void (*)(DenseLaunch)>(fn[k]);
+        return t;
+    }();
+    return table;
+}
 } // namespace
 
 struct yalps_lpdense : QueueDevice {
     QueueBufs q;
     DevBuf call;
     DenseCall desc;               // the call's description as it was uploaded
-    std::vector<int32_t> upper_idx; // the call's bound rows, kept until their upload has gone
+    std::vector<int32_t> upper_idx; // the call's index lists (bound rows, free variables, the twin of every variable), kept until their upload has gone
     // the last solve
     int32_t w = 0, h = 0, count = 0;
     std::string info;
@@ -72,11 +87,13 @@ int check_operand(const char *name, const yalps_lpdense_operand *o, int32_t coun
 }
 
 int validate(int32_t count, int32_t n, int32_t m_ub, int32_t m_eq, const yalps_lpdense_operand *c, const yalps_lpdense_operand *A_ub,
-             const yalps_lpdense_operand *b_ub, const yalps_lpdense_operand *A_eq, const yalps_lpdense_operand *b_eq, int32_t n_upper = 0) {
+             const yalps_lpdense_operand *b_ub, const yalps_lpdense_operand *A_eq, const yalps_lpdense_operand *b_eq, int32_t n_upper = 0,
+             int32_t n_free = 0) {
     if (count < 0) return fail(YALPS_E_ARG, "yalps_lpdense: count < 0");
     if (n < 0 || m_ub < 0 || m_eq < 0) return fail(YALPS_E_ARG, "yalps_lpdense: n, m_ub and m_eq must be at least 0");
     if (n_upper < 0) return fail(YALPS_E_ARG, "yalps_lpdense: n_upper < 0");
-    const int64_t w = (int64_t)n + 1, h = 1 + (int64_t)m_ub + 2 * (int64_t)m_eq + (int64_t)n_upper;
+    if (n_free < 0) return fail(YALPS_E_ARG, "yalps_lpdense: n_free < 0");
+    const int64_t w = (int64_t)n + 1 + (int64_t)n_free, h = 1 + (int64_t)m_ub + 2 * (int64_t)m_eq + (int64_t)n_upper;
     if (w > INT32_MAX || h > INT32_MAX || 8 * w * h > YALPS_LPDENSE_MAX_BYTES)
         return fail(YALPS_E_ARG, "yalps_lpdense: tableau of " + std::to_string(h) + " x " + std::to_string(w) + " doubles is above the limit of " +
                                      std::to_string((long long)YALPS_LPDENSE_MAX_BYTES) + " bytes");
@@ -91,8 +108,9 @@ int validate(int32_t count, int32_t n, int32_t m_ub, int32_t m_eq, const yalps_l
 // the bounds of a call: lb / ub may be NULL descriptors (absent); upper_idx is host memory, ascending, inside 0 .. n-1
 int validate_bounds(int32_t count, int32_t n, int32_t m_ub, int32_t m_eq, const yalps_lpdense_operand *c, const yalps_lpdense_operand *A_ub,
                     const yalps_lpdense_operand *b_ub, const yalps_lpdense_operand *A_eq, const yalps_lpdense_operand *b_eq,
-                    const yalps_lpdense_operand *lb, const yalps_lpdense_operand *ub, int32_t n_upper, const int32_t *upper_idx) {
-    if (int rc = validate(count, n, m_ub, m_eq, c, A_ub, b_ub, A_eq, b_eq, n_upper)) return rc;
+                    const yalps_lpdense_operand *lb, const yalps_lpdense_operand *ub, int32_t n_upper, const int32_t *upper_idx,
+                    int32_t n_free = 0, const int32_t *free_idx = nullptr) {
+    if (int rc = validate(count, n, m_ub, m_eq, c, A_ub, b_ub, A_eq, b_eq, n_upper, n_free)) return rc;
     if (lb)
         if (int rc = check_operand("lb", lb, count, n, 1)) return rc;
     if (ub)
@@ -104,6 +122,14 @@ int validate_bounds(int32_t count, int32_t n, int32_t m_ub, int32_t m_eq, const 
             return fail(YALPS_E_ARG, "yalps_lpdense: upper_idx[" + std::to_string(t) + "] = " + std::to_string(upper_idx[t]) + " is outside 0 .. n-1");
         if (t && upper_idx[t] <= upper_idx[t - 1])
             return fail(YALPS_E_ARG, "yalps_lpdense: upper_idx is not ascending at " + std::to_string(t));
+    }
+    // the free variables: host memory, ascending, inside 0 .. n-1 (the width that counts their twins is checked above)
+    if (n_free > 0 && !free_idx) return fail(YALPS_E_ARG, "yalps_lpdense: free_idx is NULL");
+    for (int32_t t = 0; t < n_free; t++) {
+        if (free_idx[t] < 0 || free_idx[t] >= n)
+            return fail(YALPS_E_ARG, "yalps_lpdense: free_idx[" + std::to_string(t) + "] = " + std::to_string(free_idx[t]) + " is outside 0 .. n-1");
+        if (t && free_idx[t] <= free_idx[t - 1])
+            return fail(YALPS_E_ARG, "yalps_lpdense: free_idx is not ascending at " + std::to_string(t));
     }
     return 0;
 }
@@ -137,7 +163,8 @@ int create_impl(int32_t device, void *hip_stream, yalps_lpdense **out) {
     if (hip_stream == static_cast<void *>(hipStreamLegacy)) b->stream = nullptr; // the device's default stream, by its own name
     b->q.hist_first = std::max(1, env_int("YALPS_LPDENSE_HIST", (int)HIST_FIRST)); // (test hook: forces the rerun)
     if (int rc = raise_lds_limit(kDenseKernels)) return rc;
-    return raise_lds_limit(bounds_kernels());
+    if (int rc = raise_lds_limit(bounds_kernels())) return rc;
+    return raise_lds_limit(free_kernels());
 }
 
 int solve_impl(yalps_lpdense *b, const char *entry, int32_t count, int32_t n, int32_t m_ub, int32_t m_eq, const yalps_lpdense_operand *c,
@@ -146,9 +173,10 @@ int solve_impl(yalps_lpdense *b, const char *entry, int32_t count, int32_t n, in
                double *x_out, double *objective_out, int32_t *status_out, int64_t *pivots_out, double *ineqlin_out,
                double *eqlin_out, double *reduced_out, float *gpu_ms_out, const yalps_lpdense_operand *lb = nullptr,
                const yalps_lpdense_operand *ub = nullptr, int32_t n_upper = 0, const int32_t *upper_idx = nullptr,
-               double *upper_out = nullptr) {
-    if (int rc = validate_bounds(count, n, m_ub, m_eq, c, A_ub, b_ub, A_eq, b_eq, lb, ub, n_upper, upper_idx)) return rc;
-    const bool bounds = lb || ub; // (either descriptor: lp_dense_bounds_kernel; neither: the kernels and the bits of before)
+               double *upper_out = nullptr, int32_t n_free = 0, const int32_t *free_idx = nullptr) {
+    if (int rc = validate_bounds(count, n, m_ub, m_eq, c, A_ub, b_ub, A_eq, b_eq, lb, ub, n_upper, upper_idx, n_free, free_idx)) return rc;
+    // (a free variable: lp_dense_free_kernel; else either descriptor: lp_dense_bounds_kernel; neither: the kernels and the bits of before)
+    const bool bounds = lb || ub;
     b->count = 0;
     b->q.keep = keep != 0;
     b->info = "launches=0 reruns=0\n";
@@ -177,14 +205,14 @@ int solve_impl(yalps_lpdense *b, const char *entry, int32_t count, int32_t n, in
         if (int rc = check_pointer(b, entry, a.name, a.p)) return rc;
 
     hipStream_t s = b->stream;
-    const int32_t w = n + 1, h = 1 + m_ub + 2 * m_eq + n_upper;
+    const int32_t w = n + 1 + n_free, h = 1 + m_ub + 2 * m_eq + n_upper;
     const size_t cnt = (size_t)count, heven = ((size_t)h + 1) & ~(size_t)1, perm = (size_t)w + (size_t)h;
     const int cls = lp_class(w, h);
     const bool aux = cls == HBM_CLASS && lp_aux_hbm(w, h);
     // x / objective of a call that does not want them: rows of the handle's own, behind the call's description
     const size_t call_bytes = (sizeof(DenseCall) + 15) & ~(size_t)15;
     const size_t own_x = x_out || !n ? 0 : sizeof(double) * cnt * (size_t)n, own_obj = objective_out ? 0 : sizeof(double) * cnt;
-    const size_t own_end = (own_x + own_obj + 15) & ~(size_t)15, idx_bytes = sizeof(int32_t) * (size_t)n_upper; // (the index list last)
+    const size_t own_end = (own_x + own_obj + 15) & ~(size_t)15, idx_bytes = sizeof(int32_t) * ((size_t)n_upper + (n_free ? (size_t)n_free + (size_t)n : 0)); // (the index lists last)
     if (int rc = ensure(b->call, call_bytes + own_end + idx_bytes)) return rc;
     if (int rc = ensure_outputs(b->q, cnt, heven * cnt, perm * cnt, (size_t)w * (size_t)h * cnt)) return rc;
     char *behind = b->call.as<char>() + call_bytes;
@@ -211,9 +239,18 @@ int solve_impl(yalps_lpdense *b, const char *entry, int32_t count, int32_t n, in
     if (ub && n_upper) D.ub = operand(ub, true);
     D.n_upper = n_upper;
     D.upper = n_upper ? upper_out : nullptr;
-    if (n_upper) {
+    D.n_free = n_free;
+    if (idx_bytes) { // upper_idx[n_upper], then free_idx[n_free] and twin[n] where the call has free variables: one upload
         b->upper_idx.assign(upper_idx, upper_idx + n_upper);
-        D.upper_idx = reinterpret_cast<const int32_t *>(behind + own_end);
+        const int32_t *lists = reinterpret_cast<const int32_t *>(behind + own_end);
+        if (n_upper) D.upper_idx = lists;
+        if (n_free) {
+            b->upper_idx.insert(b->upper_idx.end(), free_idx, free_idx + n_free);
+            b->upper_idx.resize((size_t)n_upper + (size_t)n_free + (size_t)n, -1);
+            for (int32_t t = 0; t < n_free; t++) b->upper_idx[(size_t)n_upper + (size_t)n_free + (size_t)free_idx[t]] = 1 + n + t;
+            D.free_idx = lists + n_upper;
+            D.twin = lists + n_upper + n_free;
+        }
         HIP_TRY(hipMemcpyAsync(behind + own_end, b->upper_idx.data(), idx_bytes, hipMemcpyHostToDevice, s));
     }
     HIP_TRY(hipMemcpyAsync(b->call.p, &D, sizeof D, hipMemcpyHostToDevice, s));
@@ -226,7 +263,7 @@ int solve_impl(yalps_lpdense *b, const char *entry, int32_t count, int32_t n, in
     std::string text;
     QueueRun run;
     const int rc = run_queue(
-        *b, b->q, bounds ? bounds_kernels() : kDenseKernels, QueueText{"yalps_lpdense", true, "yalps_lpdense_solve", "LP"}, cnt,
+        *b, b->q, n_free ? free_kernels() : bounds ? bounds_kernels() : kDenseKernels, QueueText{"yalps_lpdense", true, "yalps_lpdense_solve", "LP"}, cnt,
         [&](int32_t, int *iw, int *ih) { return *iw = w, *ih = h, checkCycles != 0; },
         [&](DenseLaunch &a) { a.call = b->call.as<const DenseCall>(); },
         [&] { // on the way back with the statuses, device to device (a pass that reruns some leaves them to the next one)
@@ -275,6 +312,14 @@ int32_t yalps_lpdense_validate_bounds(int32_t count, int32_t n, int32_t m_ub, in
                                       const yalps_lpdense_operand *lb, const yalps_lpdense_operand *ub, int32_t n_upper,
                                       const int32_t *upper_idx) {
     return validate_bounds(count, n, m_ub, m_eq, c, A_ub, b_ub, A_eq, b_eq, lb, ub, n_upper, upper_idx);
+}
+
+int32_t yalps_lpdense_validate_free(int32_t count, int32_t n, int32_t m_ub, int32_t m_eq, const yalps_lpdense_operand *c,
+                                    const yalps_lpdense_operand *A_ub, const yalps_lpdense_operand *b_ub,
+                                    const yalps_lpdense_operand *A_eq, const yalps_lpdense_operand *b_eq,
+                                    const yalps_lpdense_operand *lb, const yalps_lpdense_operand *ub, int32_t n_upper,
+                                    const int32_t *upper_idx, int32_t n_free, const int32_t *free_idx) {
+    return validate_bounds(count, n, m_ub, m_eq, c, A_ub, b_ub, A_eq, b_eq, lb, ub, n_upper, upper_idx, n_free, free_idx);
 }
 
 int32_t yalps_lpdense_create(int32_t device, void *hip_stream, yalps_lpdense **out) {
@@ -333,6 +378,22 @@ int32_t yalps_lpdense_solve_bounds(yalps_lpdense *d, int32_t count, int32_t n, i
     const int32_t rc = solve_impl(d, "yalps_lpdense_solve_bounds", count, n, m_ub, m_eq, c, A_ub, b_ub, A_eq, b_eq, maximize, precision,
                                   maxPivots, checkCycles, keep_tableaux, x_out, objective_out, status_out, pivots_out, ineqlin_out,
                                   eqlin_out, reduced_out, gpu_ms_out, lb, ub, n_upper, upper_idx, upper_out);
+    if (rc) d->count = 0; // (no last solve to read from)
+    return rc;
+}
+
+int32_t yalps_lpdense_solve_free(yalps_lpdense *d, int32_t count, int32_t n, int32_t m_ub, int32_t m_eq,
+                                 const yalps_lpdense_operand *c, const yalps_lpdense_operand *A_ub,
+                                 const yalps_lpdense_operand *b_ub, const yalps_lpdense_operand *A_eq,
+                                 const yalps_lpdense_operand *b_eq, const yalps_lpdense_operand *lb,
+                                 const yalps_lpdense_operand *ub, int32_t n_upper, const int32_t *upper_idx, int32_t n_free,
+                                 const int32_t *free_idx, int32_t maximize, double precision, double maxPivots, int32_t checkCycles,
+                                 int32_t keep_tableaux, double *x_out, double *objective_out, int32_t *status_out, int64_t *pivots_out,
+                                 double *ineqlin_out, double *eqlin_out, double *reduced_out, double *upper_out, float *gpu_ms_out) {
+    if (!d) return fail(YALPS_E_ARG, "yalps_lpdense_solve_free: handle is NULL");
+    const int32_t rc = solve_impl(d, "yalps_lpdense_solve_free", count, n, m_ub, m_eq, c, A_ub, b_ub, A_eq, b_eq, maximize, precision,
+                                  maxPivots, checkCycles, keep_tableaux, x_out, objective_out, status_out, pivots_out, ineqlin_out,
+                                  eqlin_out, reduced_out, gpu_ms_out, lb, ub, n_upper, upper_idx, upper_out, n_free, free_idx);
     if (rc) d->count = 0; // (no last solve to read from)
     return rc;
 }

@@ -37,6 +37,21 @@
 //   after  x = x' + lb, one addition per element whatever the status; objective = objective' + shift_sum(c, lb), recomputed
 //          here by wave 0 (lane 0 of the workgroup writes it), one addition after the rounding; upper[t] = ineqlin's
 //          formula on bound row t.
+//
+// Free variables (DenseFreeJob, lp_dense_free_kernel; a sibling job, so that DenseJob<false> and DenseJob<true> are compiled from
+// the lines they were compiled from): a free variable j is split as x[j] = p[j] - q[j], p, q >= 0.  p keeps column 1 + j, the
+// twins q are n_free generated columns behind the n originals in ascending j, so w = 1 + n + n_free; h as with bounds.
+//   fill   a twin cell is the IEEE negation of the cell of column 1 + j in the same row -- of the value written there, not a
+//          second product: one strided read of the operand at free_idx[c - n] by the lane that owns column c.  In a bound row
+//          of a free variable the twin cell is -1.0, in every other bound row +0.0.  lb is not read at a free variable: the
+//          effective lower bound there is +0.0, whose product with the coefficient is still formed and added in shift_sum,
+//          which runs over the n original columns alone.  The branches are on r (a row group) and on c (a lane), never per LP.
+//   after  x[j] = v(p) - v(q), each v today's rule on its own column (basic and above precision: rounded; else +0.0), one
+//          subtraction, then + l_eff[j] where lb is given; "unbounded": +inf at the unbounded column, so -inf where that is a
+//          twin.  The lane that owns j reads twin[j] (-1, or the twin's column) and, for a free variable, one more pos entry:
+//          no barrier and no LDS beyond the bounded job's.
+//          reduced[j] of a free variable = s * (cost_nb(1 + j) - cost_nb(twin[j])) + 0.0, cost_nb(v) = cost(pos[v]) where
+//          pos[v] < w, else 0: the full signed reduced cost.  The rows' marginals use the new w and are otherwise unchanged.
 // ------------------------------------------------------------------------------------------
 struct DenseOperand {
     const double *p;              // element (i, r, c) at p[i * sb + r * sr + c * sc]; a vector has sc = 0 and is indexed by r
@@ -58,6 +73,10 @@ struct DenseCall {
     int32_t n_upper;              // bound rows; ub is read at upper_idx[0 .. n_upper) only
     const int32_t *upper_idx;     // device, ascending
     double *upper;                // [count][n_upper]  the bound rows' marginals, or nullptr
+    // free variables: read by DenseFreeJob only (behind everything the other twelve kernels read, whose offsets stay)
+    int32_t n_free;               // twin columns behind the n originals
+    const int32_t *free_idx;      // device, ascending: twin t (column 1 + n + t) is the twin of variable free_idx[t]
+    const int32_t *twin;          // device, [n]: the twin's column 1 + n + t of a free variable, -1 of any other
 };
 
 struct DenseLaunch : QueueLaunch {
@@ -302,4 +321,228 @@ __global__ __launch_bounds__(T) void lp_dense_kernel(DenseLaunch L) {
 template <int T, bool CHECK, bool LDS>
 __global__ __launch_bounds__(T) void lp_dense_bounds_kernel(DenseLaunch L) {
     wg_queue<T, CHECK, LDS>(L, DenseJob<true>(L));
+}
+
+// ------------------------------------------------------------------------------------------ free variables
+// the effective lower bound of variable j: +0.0 at a free variable, where lb is not read
+__device__ __forceinline__ double dense_free_low(const double *l, long long sl, const int32_t *twin, int j) {
+    return twin[j] >= 0 ? 0.0 : l[(long long)j * sl];
+}
+
+// shift_sum(a, l_eff) over the n original columns, THE order of dense_shift_sum
+__device__ __forceinline__ double dense_free_shift_sum(const double *a, long long sa, const double *l, long long sl, const int32_t *twin,
+                                                       int n) {
+    double p = 0.0;
+    for (int j = threadIdx.x & 63; j < n; j += 64) p = p + a[(long long)j * sa] * dense_free_low(l, sl, twin, j);
+    for (int s = 32; s > 0; s >>= 1) p = p + __shfl_down(p, s, 64);
+    return p;
+}
+
+// cost_nb(v): cost at the column variable v ended in, 0 where it is basic
+__device__ __forceinline__ double dense_cost_nb(const double *mat, const int32_t *pos, int w, int v) {
+    const int p = pos[v];
+    return p < w ? dense_cost(mat, p) : 0.0;
+}
+
+// dense_marginals for a tableau of n + n_free columns: the rows' formulas with the wider w, reduced[n] with the twin's term
+template <int T>
+__device__ __forceinline__ void dense_free_marginals(const DenseCall *d, const int32_t *pos, const double *mat, long long i, int w,
+                                                     bool optimal) {
+    const int tid = threadIdx.x, n = d->n, m_ub = d->m_ub, m_eq = d->m_eq;
+    const double sign = d->sign, nan = __longlong_as_double(0x7ff8000000000000ll);
+    if (double *out = d->ineqlin) {
+        out += i * m_ub;
+        for (int r = tid; r < m_ub; r += T) out[r] = optimal ? sign * dense_row_dual(mat, pos, w, 1 + r) + 0.0 : nan;
+    }
+    if (double *out = d->eqlin) {
+        out += i * m_eq;
+        for (int k = tid; k < m_eq; k += T) {
+            const int r = 1 + m_ub + 2 * k;
+            out[k] = optimal ? sign * (dense_row_dual(mat, pos, w, r) - dense_row_dual(mat, pos, w, r + 1)) + 0.0 : nan;
+        }
+    }
+    if (double *out = d->reduced) {
+        out += i * n;
+        const int32_t *twin = d->twin;
+        for (int j = tid; j < n; j += T) {
+            double v = nan;
+            if (optimal) {
+                const int tj = twin[j];
+                if (tj >= 0) {
+                    v = sign * (dense_cost_nb(mat, pos, w, j + 1) - dense_cost_nb(mat, pos, w, tj)) + 0.0;
+                } else {
+                    const int p = pos[j + 1];
+                    v = p < w ? sign * dense_cost(mat, p) + 0.0 : 0.0;
+                }
+            }
+            out[j] = v;
+        }
+    }
+}
+
+// DenseFreeJob::fill.  A function of its own, not inlined, as dense_free_readout and for its reason: with the read-out alone out
+// of line the <1024,check> HBM form still spilled two registers.
+template <int T>
+__device__ __attribute__((noinline)) void dense_free_fill(const DenseCall *d, long long i, int w, int h, double *mat, double *rhs, int32_t *pos,
+                                                          int32_t *var, int lp) {
+    const int tid = threadIdx.x, n = d->n, nw = w - 1, m_ub = d->m_ub; // nw: the originals and the twins
+    const double sign = d->sign;
+    const int Uc = wg_unit_lanes(lp + 1, T), cu0 = tid % Uc, cg0 = tid / Uc, CG = T / Uc;
+    const int32_t *twin = d->twin, *free_idx = d->free_idx;
+    const double *lb = nullptr, *ub = nullptr;
+    const long long lbs = d->lb.sr, ubs = d->ub.sr;
+    const int h0 = h - d->n_upper; // the first bound row
+    if (d->lb.p) lb = d->lb.p + i * d->lb.sb;
+    if (d->ub.p) ub = d->ub.p + i * d->ub.sb;
+    if (lb) { // the shifts: one wave per operand row, parked in the row's rhs slot
+        const int m_eq = d->m_eq;
+        for (int q = tid >> 6; q < m_ub + m_eq; q += T >> 6) {
+            const bool eq = q >= m_ub;
+            const DenseOperand &A = eq ? d->A_eq : d->A_ub;
+            const int k = eq ? q - m_ub : q;
+            const double v = dense_free_shift_sum(A.p + i * A.sb + (long long)k * A.sr, A.sc, lb, lbs, twin, n);
+            if ((tid & 63) == 0) {
+                if (eq) rhs[1 + m_ub + 2 * k] = rhs[2 + m_ub + 2 * k] = v;
+                else rhs[1 + q] = v;
+            }
+        }
+        __syncthreads();
+    }
+    for (int r = cg0; r < h; r += CG) {
+        double *dst = mat + (size_t)r * lp;
+        if (r >= h0) { // a bound row: nothing but column 0 is read; -1.0 at the twin of a free variable
+            const int j = d->upper_idx[r - h0], tj = twin[j] - 1;
+            for (int c = cu0; c <= lp; c += Uc) {
+                if (c == lp) {
+                    const double u = ub[(long long)j * ubs];
+                    rhs[r] = lb ? u - dense_free_low(lb, lbs, twin, j) : u;
+                } else {
+                    dst[c] = c == j ? 1.0 : (c == tj ? -1.0 : 0.0);
+                }
+            }
+            continue;
+        }
+        const double *a, *b; // the row's coefficients, and its right-hand side
+        long long sc;
+        bool neg = false;
+        if (r == 0) {
+            a = d->c.p + i * d->c.sb;
+            sc = d->c.sr;
+            b = nullptr;
+        } else if (r <= m_ub) {
+            a = d->A_ub.p + i * d->A_ub.sb + (long long)(r - 1) * d->A_ub.sr;
+            sc = d->A_ub.sc;
+            b = d->b_ub.p + i * d->b_ub.sb + (long long)(r - 1) * d->b_ub.sr;
+        } else {
+            const int k = (r - 1 - m_ub) >> 1;
+            neg = ((r - 1 - m_ub) & 1) != 0;
+            a = d->A_eq.p + i * d->A_eq.sb + (long long)k * d->A_eq.sr;
+            sc = d->A_eq.sc;
+            b = d->b_eq.p + i * d->b_eq.sb + (long long)k * d->b_eq.sr;
+        }
+        for (int c = cu0; c <= lp; c += Uc) {
+            if (c == lp) {
+                if (lb && r != 0) {
+                    const double v = *b - rhs[r];
+                    rhs[r] = neg ? -v : v;
+                } else {
+                    rhs[r] = r == 0 ? 0.0 : (neg ? -*b : *b);
+                }
+            } else if (c >= nw) {
+                dst[c] = 0.0;
+            } else { // column c of the originals, or the twin of free_idx[c - n]: the negation of the cell written there
+                const bool tw = c >= n;
+                const double v = a[(long long)(tw ? free_idx[c - n] : c) * sc];
+                const double cell = r == 0 ? sign * v : (neg ? -v : v);
+                dst[c] = tw ? -cell : cell;
+            }
+        }
+    }
+    for (int p = tid; p < w + h; p += T) {
+        pos[p] = p;
+        var[p] = p;
+    }
+}
+
+// DenseFreeJob::after behind its barrier: solution() on the device with x[j] = v(p) - v(q) at a free variable, and the marginals.
+// A function of its own, not inlined (as lp_sens_kernel's epilogue and for its reason): inlined, its registers came on top of
+// wg_simplex's in the allocator's eyes and the <1024,check> HBM form spilled two registers to scratch.
+template <int T>
+__device__ __attribute__((noinline)) void dense_free_readout(const DenseCall *d, const int32_t *pos, const int32_t *var, const double *result,
+                                                             const double *mat, const double *rhs, long long i, int w, int h, int status) {
+    const int tid = threadIdx.x, n = d->n;
+    double *x = d->x + i * n;
+    const double sign = d->sign, p = d->precision;
+    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    const int32_t *twin = d->twin;
+    double objective = nan;
+    const double *lb = nullptr; // x = x' + l_eff, whatever the status
+    const long long lbs = d->lb.sr;
+    if (d->lb.p) lb = d->lb.p + i * d->lb.sb;
+    if (status == YALPS_OPTIMAL) {
+        for (int j = tid; j < n; j += T) {
+            const int row = pos[j + 1] - w, tj = twin[j];
+            const double v = row >= 0 ? rhs[row] : 0.0;
+            double xv = v > p ? round_to_precision(v, p) : 0.0;
+            if (tj >= 0) {
+                const int qrow = pos[tj] - w;
+                const double q = qrow >= 0 ? rhs[qrow] : 0.0;
+                xv = xv - (q > p ? round_to_precision(q, p) : 0.0);
+            }
+            x[j] = lb ? xv + (tj >= 0 ? 0.0 : lb[(long long)j * lbs]) : xv;
+        }
+        objective = -sign * *result;
+    } else if (status == YALPS_UNBOUNDED) {
+        const int at = (int)*result;
+        const int v = (unsigned)at < (unsigned)(w + h) ? var[at] : -1; // the unbounded column, 1-based
+        for (int j = tid; j < n; j += T) {
+            const int tj = twin[j];
+            double xv = j + 1 == v ? INFINITY : 0.0;
+            if (tj >= 0) xv = xv - (tj == v ? INFINITY : 0.0);
+            x[j] = lb ? xv + (tj >= 0 ? 0.0 : lb[(long long)j * lbs]) : xv;
+        }
+        objective = sign * INFINITY;
+    } else {
+        for (int j = tid; j < n; j += T) x[j] = nan; // (NaN + l_eff[j] is NaN)
+    }
+    // (wave 0 alone computes the constant, whole: the condition is the same for all lanes of a wave; the caller's c, not sign * c)
+    if (lb && tid < 64) objective = objective + dense_free_shift_sum(d->c.p + i * d->c.sb, d->c.sr, lb, lbs, twin, n);
+    if (tid == 0) d->objective[i] = objective;
+    if (d->ineqlin || d->eqlin || d->reduced) dense_free_marginals<T>(d, pos, mat, i, w, status == YALPS_OPTIMAL);
+    if (d->upper) dense_upper_marginals<T>(d, pos, mat, i, w, status == YALPS_OPTIMAL);
+}
+
+// DenseJob<true> with n_free twin columns; lb / ub may be absent (null descriptors), as there
+struct DenseFreeJob : QueueJobBase {
+    const DenseLaunch &L;
+    const DenseCall *d;
+    int idx;
+    __device__ __forceinline__ explicit DenseFreeJob(const DenseLaunch &launch) : L(launch), d(launch.call), idx(0) {}
+    __device__ __forceinline__ QueueItem item(int i) {
+        idx = i;
+        const int w = d->n + 1 + d->n_free, h = 1 + d->m_ub + 2 * d->m_eq + d->n_upper, heven = (h + 1) & ~1;
+        return QueueItem{w, h, (long long)((size_t)i * heven), (long long)((size_t)i * ((size_t)w + h)), d->aux_hbm};
+    }
+    __device__ __forceinline__ double precision() const { return d->precision; }
+    __device__ __forceinline__ double max_pivots() const { return d->max_pivots; }
+    __device__ __forceinline__ long long tab_off(int i, const QueueItem &it) const { return (long long)((size_t)i * it.w * it.h); }
+
+    template <int T, bool LDS>
+    __device__ __forceinline__ void fill(const QueueItem &it, double *mat, double *rhs, int32_t *pos, int32_t *var, int lp) const {
+        dense_free_fill<T>(d, idx, it.w, it.h, mat, rhs, pos, var, lp);
+    }
+
+    // solution() on the device: dense_free_readout.  Every lane; the barrier is met whatever the status.
+    template <int T>
+    __device__ __forceinline__ void after(const QueueItem &it, int status, const double *mat, const double *rhs, int) const {
+        __syncthreads(); // the queue's copies of pos / var / col0 and lane T - 1's result are written
+        if (status == WG_HISTORY_FULL) return;
+        dense_free_readout<T>(d, L.pos + it.perm_off, L.var + it.perm_off, L.result + idx, mat, rhs, idx, it.w, it.h, status);
+    }
+};
+
+// the same queue with free variables; instantiated by lp_dense_free.hip alone (libyalps_lpdense_free.so)
+template <int T, bool CHECK, bool LDS>
+__global__ __launch_bounds__(T) void lp_dense_free_kernel(DenseLaunch L) {
+    wg_queue<T, CHECK, LDS>(L, DenseFreeJob(L));
 }

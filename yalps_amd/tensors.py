@@ -1,5 +1,5 @@
 """linprog_batch: batches of small dense LPs straight from torch tensors on the GPU (libyalps_lpdense.so), with variable
-bounds lb <= x <= ub shifted and built on the device, and with their dual solutions on request; linprog_objective: the optimal value as a differentiable torch function; milp_batch: batches of small
+bounds lb <= x <= ub shifted and built on the device, free variables split and built there too, and with their dual solutions on request; linprog_objective: the optimal value as a differentiable torch function; milp_batch: batches of small
 dense MILPs the same way, every branch-and-cut tree walked on the device (libyalps_milpdense.so).
 
 This module imports torch; `import yalps_amd` does not.  linprog_batch computes nothing with torch: it supplies the device
@@ -142,7 +142,30 @@ def _upper_set(n, upper, has_ub, who="linprog_batch"):
     return sorted(idx)
 
 
-def linprog_batch(c, A_ub=None, b_ub=None, A_eq=None, b_eq=None, *, lb=None, ub=None, upper=True, maximize=False, precision=1e-8,
+def _free_set(n, free, who="linprog_batch"):
+    """`free` as the ascending list of 0-based indices of the variables without a lower bound (True: all n; (), False, None:
+    none); raises as _upper_set does: TypeError for a string, something that is no sequence, a bool or non-integer entry,
+    ValueError for a duplicate or an index outside 0 .. n - 1."""
+    if free is True:
+        return list(range(n))
+    if free is False or free is None:
+        free = ()
+    if isinstance(free, (str, bytes)) or not hasattr(free, "__iter__"):
+        raise TypeError("%s: free must be a sequence of variable indices or True, not %r" % (who, free))
+    idx = []
+    for j in free:
+        if isinstance(j, bool) or int(j) != j:
+            raise TypeError("%s: free holds %r; variable indices are integers" % (who, j))
+        idx.append(int(j))
+    bad = [j for j in idx if not 0 <= j < n]
+    if bad:
+        raise ValueError("%s: free names variable %d, outside 0 .. %d" % (who, bad[0], n - 1))
+    if len(set(idx)) != len(idx):
+        raise ValueError("%s: free names variable %d twice" % (who, next(j for k, j in enumerate(idx) if j in idx[:k])))
+    return sorted(idx)
+
+
+def linprog_batch(c, A_ub=None, b_ub=None, A_eq=None, b_eq=None, *, lb=None, ub=None, upper=True, free=(), maximize=False, precision=1e-8,
                   max_pivots=8192, check_cycles=False, stats=None, duals=False):
     """Solves B dense LPs of one shape in one call, from device tensors to device tensors:
 
@@ -200,22 +223,42 @@ def linprog_batch(c, A_ub=None, b_ub=None, A_eq=None, b_eq=None, *, lb=None, ub=
     (scipy's lower.marginals).  Every "optimal" row satisfies, up to rounding,
         reduced_costs = c - A_ub^T ineqlin - A_eq^T eqlin - scatter(upper)    and
         objective = ineqlin . b_ub + eqlin . b_eq + upper . ub + reduced_costs . lb.
-    Out of scope: free variables (an lb entry of -inf is taken as it lies in memory, like every other value) and per-LP `upper`
-    sets.  milp_batch takes the same three arguments.
+
+    Free variables.  `free` is a HOST sequence of 0-based indices of the variables that have no lower bound (scipy's
+    bounds=(None, ...)), or True for all n, shared by the batch -- it changes the tableau's width, and one call has one shape.
+    (), False and None mean none, and such a call is the call it was: the same kernels, the same bits, with and without
+    bounds.  It is checked like `upper`: a duplicate or out-of-range index raises ValueError, a string, a bool or a
+    non-integer entry TypeError, before the library is touched.  Nothing is materialised: a free variable j is split on the
+    device as x[j] = p[j] - q[j] with p, q >= 0; p keeps column 1 + j and the f = len(free) twins q are generated columns
+    behind the n originals in ascending j, each cell the IEEE negation of the cell of column 1 + j in its row (a negation of
+    the value read, not a second product: row 0 holds -(sign c[j]), a zero becomes -0.0, the negated row of an equality
+    holds A_eq[k, j] again).  The tableau is (1 + n + f) x (1 + m_ub + 2 m_eq + k), and the 4 MiB limit holds for that shape.
+    lb is NOT read at a free variable: its effective lower bound is +0.0 (the product with +0.0 is still formed in shift_sum,
+    which runs over the n original columns alone).  A free variable that `upper` lists keeps its bound row, with -1.0 in the
+    twin's column: x[j] <= ub[j] and no lower bound, scipy's (None, ub).  For finite data row i is solve() of the equivalent
+    model: the bounded call's, plus one variable q<j> per free variable behind all x<j>, listing the negated coefficient of
+    every constraint x<j> lists, and -c[j].  "optimal" gives x[j] = v(p) - v(q), each v the rule above on its own column,
+    then + the effective lower bound where lb is given; "unbounded" gives +inf at the unbounded column, so -inf at a free
+    variable whose twin it is.  reduced_costs[j] of a free variable is the full signed reduced cost, the p column's term minus
+    the twin's -- about 0 at an optimum, as scipy reports -- so the two identities above hold at every j, with the effective
+    lower bound in place of lb.  A call with free variables runs lp_dense_free_kernel, with or without lb / ub.
+    Out of scope: per-LP `upper` and `free` sets, and inferring freeness from the data (an lb entry of -inf at a variable `free`
+    does not list is taken as it lies in memory, like every other value).  milp_batch takes lb, ub and upper, not free.
 
     See the module's docstring for the loading rule: torch first."""
     sets = {}
 
     def size(n, m_ub, m_eq):
         k = len(sets.setdefault("upper", _upper_set(n, upper, ub is not None)))
-        w, h = n + 1, 1 + m_ub + 2 * m_eq + k
+        f = len(sets.setdefault("free", _free_set(n, free)))
+        w, h = n + 1 + f, 1 + m_ub + 2 * m_eq + k
         if 8 * w * h > _native.LPDENSE_MAX_BYTES:
             raise ValueError("linprog_batch: a tableau of %d x %d doubles (%d bytes) is above the batch limit of %d bytes; "
                              "solve() is the route for such models" % (h, w, 8 * w * h, _native.LPDENSE_MAX_BYTES))
 
     B, n, m_ub, m_eq, device, operands, _, _, bounds = _call_operands("linprog_batch", c, A_ub, b_ub, A_eq, b_eq, size,
                                                                       vectors={"lb": lb, "ub": ub})
-    idx = sets["upper"]
+    idx, fidx = sets["upper"], sets["free"]
     bounded = lb is not None or ub is not None
     ptr = lambda t: t.data_ptr() if t.numel() else None
     x = torch.empty((B, n), dtype=torch.float64, device=device)
@@ -229,6 +272,8 @@ def linprog_batch(c, A_ub=None, b_ub=None, A_eq=None, b_eq=None, *, lb=None, ub=
         # (a bound tensor without an element -- n = 0 -- stays a descriptor, so that the call still is the bounded one)
         more = dict(lb=None if lb is None else bounds["lb"] or (None, 0, 0, 0), ub=None if ub is None else bounds["ub"] or (None, 0, 0, 0),
                     upper=idx, upper_out=None if upper_out is None else ptr(upper_out))
+    if fidx:
+        more["free"] = fidx
     with torch.cuda.device(device), _lock:  # (the library selects the handle's device; torch's choice comes back afterwards)
         stream = torch.cuda.current_stream(device).cuda_stream or 1  # (the default stream's handle is 0: hipStreamLegacy names it)
         key = (device.index, stream)
@@ -280,14 +325,16 @@ class _Objective(torch.autograd.Function):
 
 class _BoundedObjective(torch.autograd.Function):
     """_Objective for a call with lb or ub (None: absent): the same forward and the same five gradients with the full x, plus
-    d lb = g reduced_costs and d ub = g upper scattered into a [B, n] zero tensor."""
+    d lb = g reduced_costs (exactly 0 at a free variable) and d ub = g upper scattered into a [B, n] zero tensor."""
 
     @staticmethod
-    def forward(ctx, options, upper, c, A_ub, b_ub, A_eq, b_eq, lb, ub):
-        out = linprog_batch(c, A_ub, b_ub, A_eq, b_eq, lb=lb, ub=ub, upper=upper, duals=True, **options)
+    def forward(ctx, options, sets, c, A_ub, b_ub, A_eq, b_eq, lb, ub):
+        upper, free = sets
+        out = linprog_batch(c, A_ub, b_ub, A_eq, b_eq, lb=lb, ub=ub, upper=upper, free=free, duals=True, **options)
         ctx.sides = (A_ub is not None, A_eq is not None)
         ctx.bounds = (lb is not None, ub is not None)
         ctx.upper = _upper_set(c.shape[-1], upper, ub is not None)
+        ctx.free = _free_set(c.shape[-1], free)
         ctx.save_for_backward(out.x, out.status, out.ineqlin, out.eqlin, out.reduced_costs, *out[7:])
         rest = out[:1] + out[2:]
         ctx.mark_non_differentiable(*rest)
@@ -306,7 +353,13 @@ class _BoundedObjective(torch.autograd.Function):
             gy = g * y
             grads.append(-gy.unsqueeze(2) * x.unsqueeze(1) if has and need[3 + 2 * k] else None)
             grads.append(gy if has and need[4 + 2 * k] else None)
-        grads.append(g * reduced if ctx.bounds[0] and need[7] else None)
+        d_lb = None
+        if ctx.bounds[0] and need[7]:
+            d_lb = g * reduced
+            free = getattr(ctx, "free", ())
+            if free:
+                d_lb[:, free] = 0.0  # (lb is not read at a free variable)
+        grads.append(d_lb)
         d_ub = None
         if ctx.bounds[1] and need[8]:
             d_ub = torch.zeros_like(x)
@@ -315,7 +368,7 @@ class _BoundedObjective(torch.autograd.Function):
         return tuple(grads)
 
 
-def _objective_call(who, options, given, upper=True):
+def _objective_call(who, options, given, upper=True, free=()):
     """linprog_objective and linprog_objective_bounds behind their argument lists: given = {name: tensor or None} of the five
     operands, and of lb / ub where the call has bounds."""
     for tag in ("ub", "eq"):
@@ -336,7 +389,8 @@ def _objective_call(who, options, given, upper=True):
     if "lb" in given:
         has_ub = given["ub"] is not None
         _upper_set(given["c"].shape[-1], upper, has_ub, who)
-        objective, *rest = _BoundedObjective.apply(options, upper, *expanded)
+        _free_set(given["c"].shape[-1], free, who)
+        objective, *rest = _BoundedObjective.apply(options, (upper, free), *expanded)
         return objective, (LinprogBoundDuals if has_ub else LinprogDuals)(rest[0], objective.detach(), *rest[1:])
     objective, *rest = _Objective.apply(options, *expanded)
     return objective, LinprogDuals(rest[0], objective.detach(), *rest[1:])
@@ -369,7 +423,7 @@ def linprog_objective(c, A_ub=None, b_ub=None, A_eq=None, b_eq=None, *, maximize
     return _objective_call("linprog_objective", options, {"c": c, "A_ub": A_ub, "b_ub": b_ub, "A_eq": A_eq, "b_eq": b_eq})
 
 
-def linprog_objective_bounds(c, A_ub=None, b_ub=None, A_eq=None, b_eq=None, *, lb=None, ub=None, upper=True, maximize=False,
+def linprog_objective_bounds(c, A_ub=None, b_ub=None, A_eq=None, b_eq=None, *, lb=None, ub=None, upper=True, free=(), maximize=False,
                              precision=1e-8, max_pivots=8192, check_cycles=False):
     """linprog_objective with linprog_batch's bounds lb, ub and upper (a function of its own: linprog_objective keeps the
     argument list it has): (objective [B], what linprog_batch(..., lb=, ub=, upper=, duals=True) returns -- LinprogBoundDuals
@@ -377,11 +431,12 @@ def linprog_objective_bounds(c, A_ub=None, b_ub=None, A_eq=None, b_eq=None, *, l
 
         dlb = g reduced_costs      dub = g upper, scattered into a [B, n] zero tensor (a variable `upper` does not list: 0)
 
-    A shared lb or ub receives the sum over the batch; a row that is not "optimal" contributes exact zeros.  Free variables
-    and per-LP `upper` sets are out of scope, as in linprog_batch."""
+    A shared lb or ub receives the sum over the batch; a row that is not "optimal" contributes exact zeros.  `free` is
+    linprog_batch's: all formulas hold with the full x, which may now be negative, and dlb is exactly 0 at a free variable,
+    where lb is not read.  Per-LP `upper` and `free` sets are out of scope, as in linprog_batch."""
     options = dict(maximize=maximize, precision=precision, max_pivots=max_pivots, check_cycles=check_cycles)
     given = {"c": c, "A_ub": A_ub, "b_ub": b_ub, "A_eq": A_eq, "b_eq": b_eq, "lb": lb, "ub": ub}
-    return _objective_call("linprog_objective_bounds", options, given, upper)
+    return _objective_call("linprog_objective_bounds", options, given, upper, free)
 
 
 def _solve_on_host(device, rows, given, batched, B, ints, bins, maximize, options, out, bounds=(None, None), bounds_batched=(False, False),
