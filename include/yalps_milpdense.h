@@ -149,6 +149,50 @@ int32_t yalps_milpdense_solve_bounds(yalps_milpdense *d, int32_t count, int32_t 
                                      int32_t *status_out, int64_t *nodes_out, int64_t *node_pivots_out, int64_t *root_pivots_out,
                                      int64_t *call_stats_out);
 
+/* Free variables.  free_idx is a HOST list of n_free 0-based indices, strictly ascending: the variables without a lower bound.
+ * The rules, all decided on the host:
+ *   1. the split is yalps_lpdense_solve_free's: x[j] = p[j] - q[j]; p keeps column 1 + j, the n_free twins q are generated
+ *      columns behind the n originals in ascending j, each cell the IEEE negation of the cell written at column 1 + j of that
+ *      row (one strided read, not a second product), -1.0 in the bound row of a free variable upper_idx lists, +0.0 in every
+ *      other generated row, the binary rows included.  Width 1 + n + n_free.
+ *   2. lb is not read at a free variable: l_eff[j] is +0.0 there, with no ceil, integer or not; the product with +0.0 is still
+ *      formed and added in shift_sum, which runs over the n original columns only.  Elsewhere l_eff is the bounded call's.
+ *   3. a binary variable cannot be free: an entry of free_idx that is in `binaries` is refused ("variable j is binary").
+ *   4. a free integer variable has two integer columns: milp_tree_kernel is handed the n_integers columns 1 + j in ascending
+ *      j, then the twin columns of the free integer variables in ascending j (the whole list ascends):
+ *      n_int_eff = n_integers + |free & integers| columns, tree slices of height + 2 * n_int_eff rows, and a largest node of
+ *      8 * (1 + n + n_free) * (height + 2 * n_int_eff) bytes, which is what YALPS_MILPDENSE_MAX_BYTES bounds and the refusal
+ *      says.
+ *   5. rows: yalps_lpdense's, then the n_upper bound rows, then the binary rows, as with bounds.
+ *   6. x_out[j] of a free variable, from the best tableau: optimal / timedout with a result v(p) - v(q), each v the rule above
+ *      on its own column, one subtraction, then + l_eff[j] where lb is given; unbounded: +inf at the unbounded column, so -inf
+ *      where that column is a twin; else NaN.  objective_out = objective' + shift_sum(c, l_eff), one addition.
+ * yalps_milpdense_validate_free: yalps_milpdense_validate_bounds' refusals with that width and that largest node, plus a
+ * negative n_free, a NULL free_idx, and free_idx out of 0 .. n - 1, not strictly ascending, or naming a binary variable. */
+int32_t yalps_milpdense_validate_free(int32_t count, int32_t n, int32_t m_ub, int32_t m_eq, const yalps_milpdense_operand *c,
+                                      const yalps_milpdense_operand *A_ub, const yalps_milpdense_operand *b_ub,
+                                      const yalps_milpdense_operand *A_eq, const yalps_milpdense_operand *b_eq,
+                                      const yalps_milpdense_operand *lb, const yalps_milpdense_operand *ub, int32_t n_upper,
+                                      const int32_t *upper_idx, int32_t n_free, const int32_t *free_idx, int32_t n_integers,
+                                      const int32_t *integers, int32_t n_binaries, const int32_t *binaries);
+
+/* yalps_milpdense_solve_bounds with free variables (the rules above); lb and ub may both be NULL.  With n_free = 0 the call is
+ * yalps_milpdense_solve_bounds (or, with neither descriptor, yalps_milpdense_solve): the same kernels, the same bits.  With
+ * n_free > 0 it runs milp_dense_free_root_kernel and milp_dense_free_solution_kernel.  With n_integers = 0 the first three
+ * outputs and root_pivots_out are yalps_lpdense_solve_free's x, objective, status and pivots, bit for bit.
+ * yalps_milpdense_solution / _trace speak of the split tableau: width 1 + n + n_free, cut variables may be twin columns, and
+ * "n_integers" in their room rules reads n_int_eff. */
+int32_t yalps_milpdense_solve_free(yalps_milpdense *d, int32_t count, int32_t n, int32_t m_ub, int32_t m_eq,
+                                   const yalps_milpdense_operand *c, const yalps_milpdense_operand *A_ub,
+                                   const yalps_milpdense_operand *b_ub, const yalps_milpdense_operand *A_eq,
+                                   const yalps_milpdense_operand *b_eq, const yalps_milpdense_operand *lb,
+                                   const yalps_milpdense_operand *ub, int32_t n_upper, const int32_t *upper_idx, int32_t n_free,
+                                   const int32_t *free_idx, int32_t n_integers, const int32_t *integers, int32_t n_binaries,
+                                   const int32_t *binaries, int32_t maximize, double precision, double maxPivots, int32_t checkCycles,
+                                   double tolerance, double maxIterations, int32_t trace_cap, double *x_out, double *objective_out,
+                                   int32_t *status_out, int64_t *nodes_out, int64_t *node_pivots_out, int64_t *root_pivots_out,
+                                   int64_t *call_stats_out);
+
 /* The trees of the last solve that ended YALPS_MILPDENSE_OVERFLOW, ascending: at most `cap` indices into ids (HOST, may be
  * NULL with cap = 0).  Returns their number. */
 int32_t yalps_milpdense_overflowed(const yalps_milpdense *d, int32_t *ids, int32_t cap);

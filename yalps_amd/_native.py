@@ -83,7 +83,8 @@ MILPDENSE_LIB_PATH = os.environ.get("YALPS_MILPDENSE_LIB") or os.path.join(HERE,
 SYMBOLS_MILPDENSE = (
     "yalps_milpdense_create", "yalps_milpdense_destroy", "yalps_milpdense_validate", "yalps_milpdense_solve",
     "yalps_milpdense_overflowed", "yalps_milpdense_solution", "yalps_milpdense_trace", "yalps_milpdense_info",
-    "yalps_milpdense_last_error", "yalps_milpdense_validate_bounds", "yalps_milpdense_solve_bounds")
+    "yalps_milpdense_last_error", "yalps_milpdense_validate_bounds", "yalps_milpdense_solve_bounds",
+    "yalps_milpdense_validate_free", "yalps_milpdense_solve_free")
 MILPDENSE_MAX_BYTES = 4 << 20  # YALPS_MILPDENSE_MAX_BYTES: the largest possible node, root height + 2 * n_integers rows
 LPBATCH_HBM_CLASS = 4        # yalps_lpbatch_class: 0..3 the LDS form, 4 the HBM form
 
@@ -1540,6 +1541,9 @@ _BATCH_LIBS["yalps_milpdense"] = (MILPDENSE_LIB_PATH, {
         "validate_bounds": (_I32, [_I32, _I32, _I32, _I32, _DOP, _DOP, _DOP, _DOP, _DOP, _DOP, _DOP, _I32, _VP, _I32, _VP, _I32, _VP]),
         "solve_bounds": (_I32, [_VP, _I32, _I32, _I32, _I32, _DOP, _DOP, _DOP, _DOP, _DOP, _DOP, _DOP, _I32, _VP, _I32, _VP, _I32, _VP, _I32,
                                 C.c_double, C.c_double, _I32, C.c_double, C.c_double, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+        "validate_free": (_I32, [_I32, _I32, _I32, _I32, _DOP, _DOP, _DOP, _DOP, _DOP, _DOP, _DOP, _I32, _VP, _I32, _VP, _I32, _VP, _I32, _VP]),
+        "solve_free": (_I32, [_VP, _I32, _I32, _I32, _I32, _DOP, _DOP, _DOP, _DOP, _DOP, _DOP, _DOP, _I32, _VP, _I32, _VP, _I32, _VP, _I32, _VP,
+                              _I32, C.c_double, C.c_double, _I32, C.c_double, C.c_double, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
         "overflowed": (_I32, [_VP, _VP, _I32]),
         "solution": (_I32, [_VP, _I32, C.POINTER(_I32), C.POINTER(C.c_double), C.POINTER(_I32), _VP, _VP, _VP]),
         "trace": (_I32, [_VP, _I32, C.POINTER(_I32)] + [_VP] * 8)})
@@ -1577,6 +1581,18 @@ def milpdense_validate_bounds(count, n, m_ub, m_eq, operands, integers=(), binar
         bins.size, bins.ctypes.data))
 
 
+def milpdense_validate_free(count, n, m_ub, m_eq, operands, integers=(), binaries=(), lb=None, ub=None, upper=(), free=()):
+    """The host-only argument checks of yalps_milpdense_solve_free: milpdense_validate_bounds' with the width that counts the
+    len(free) twin columns and the largest node that counts the cuts of the free integer variables' twins, plus the index list
+    of the free variables, which is ascending and names no binary variable."""
+    ops, ints, bins = _dense_operands(operands), _index_list(integers), _index_list(binaries)
+    lbp, ubp, k, idx = _dense_bounds(lb, ub, _index_list(upper))
+    fidx = _index_list(free)
+    milpdense_check(milpdense_lib().yalps_milpdense_validate_free(
+        int(count), int(n), int(m_ub), int(m_eq), *(C.byref(o) for o in ops), lbp, ubp, k, idx.ctypes.data, fidx.size, fidx.ctypes.data,
+        ints.size, ints.ctypes.data, bins.size, bins.ctypes.data))
+
+
 class MilpDense:
     """Batches of dense MILPs of one shape, operands and answers in device memory, every tree walked on the device
     (yalps_milpdense_*).  Pointers are plain integers (a tensor's data_ptr()); nothing here imports torch.  Belongs to one
@@ -1586,15 +1602,18 @@ class MilpDense:
         self.handle = C.c_void_p()
         milpdense_check(milpdense_lib().yalps_milpdense_create(device, C.c_void_p(stream) if stream is not None else None,
                                                                C.byref(self.handle)))
-        self.shape, self.trace_cap = None, 0  # (count, width, root height, n_integers) of the last solve
+        self.shape, self.trace_cap = None, 0  # (count, width, root height, integer columns) of the last solve
 
     def solve(self, count, n, m_ub, m_eq, operands, integers=(), binaries=(), maximize=False, precision=1e-8, max_pivots=8192.0,
               check_cycles=False, tolerance=0.0, max_iterations=32768.0, trace_cap=0, x=None, objective=None, status=None,
-              nodes=None, node_pivots=None, root_pivots=None, lb=None, ub=None, upper=()):
+              nodes=None, node_pivots=None, root_pivots=None, lb=None, ub=None, upper=(), free=(), entry=None):
         """operands = (c, A_ub, b_ub, A_eq, b_eq) as LpDense.solve takes them; integers / binaries: ascending 0-based variable
         indices, `integers` the union of both sets; lb / ub: (device pointer, batch, row, col) of the bounds x >= lb and
         x[j] <= ub[j] for the ascending indices j of `upper` (a host sequence that names no binary variable), or None -- with lb
-        or ub given the call is yalps_milpdense_solve_bounds, and the root is len(upper) rows taller; x / objective / status / nodes / node_pivots / root_pivots: device pointers
+        or ub given the call is yalps_milpdense_solve_bounds, and the root is len(upper) rows taller; free: the ascending indices
+        of the variables without a lower bound (a host sequence that names no binary variable) -- with any the call is
+        yalps_milpdense_solve_free, with or without lb / ub, the tableau is len(free) columns wider and the twins of the free
+        integer variables are integer columns too; entry="free" takes that entry point whatever `free` holds; x / objective / status / nodes / node_pivots / root_pivots: device pointers
         of contiguous float64 [count][n], float64 [count], int32 [count] and three int64 [count], or None.  The outputs are
         complete on return.  Returns {"reruns", "launches", "overflows", "root_ms", "tree_ms", "epilogue_ms", "gpu_ms"}."""
         ops, ints, bins = _dense_operands(operands), _index_list(integers), _index_list(binaries)
@@ -1605,14 +1624,19 @@ class MilpDense:
                 int(bool(check_cycles)), float(tolerance), float(max_iterations), int(trace_cap), x, objective, status, nodes, node_pivots,
                 root_pivots, call.ctypes.data)
         k = 0
-        if lb is not None or ub is not None:
+        fidx = _index_list(free)
+        if fidx.size or entry == "free":
+            lbp, ubp, k, idx = _dense_bounds(lb, ub, _index_list(upper))
+            milpdense_check(milpdense_lib().yalps_milpdense_solve_free(*head, lbp, ubp, k, idx.ctypes.data, fidx.size, fidx.ctypes.data, *tail))
+        elif lb is not None or ub is not None:
             lbp, ubp, k, idx = _dense_bounds(lb, ub, _index_list(upper))
             milpdense_check(milpdense_lib().yalps_milpdense_solve_bounds(*head, lbp, ubp, k, idx.ctypes.data, *tail))
         elif len(upper):
             raise NativeError("MilpDense.solve: upper without lb or ub")
         else:
             milpdense_check(milpdense_lib().yalps_milpdense_solve(*head, *tail))
-        self.shape = (int(count), int(n) + 1, 1 + int(m_ub) + 2 * int(m_eq) + k + bins.size, ints.size)
+        twins = len(set(fidx.tolist()) & set(ints.tolist()))
+        self.shape = (int(count), int(n) + 1 + fidx.size, 1 + int(m_ub) + 2 * int(m_eq) + k + bins.size, ints.size + twins)
         self.trace_cap = int(trace_cap)
         root, tree, epi = (call[k] / 1000.0 for k in (3, 4, 5))
         return {"reruns": int(call[0]), "launches": int(call[1]), "overflows": int(call[2]), "root_ms": root, "tree_ms": tree,

@@ -12,6 +12,7 @@
   yalps_amd/libyalps_lpdense_free.so     its kernels with free variables, linked by libyalps_lpdense.so              hipcc
   yalps_amd/libyalps_milpdense.so batches of dense MILPs of one shape, device tensors in and out, trees walked on the device (include/yalps_milpdense.h) hipcc
   yalps_amd/libyalps_milpdense_bounds.so its root and solution kernels with variable bounds, linked by libyalps_milpdense.so hipcc
+  yalps_amd/libyalps_milpdense_free.so   its root and solution kernels with free variables, linked by libyalps_milpdense.so hipcc
   yalps_amd/napi/yalps_napi.node  thin N-API shim over the C ABI (optional)  g++
 
 The .so files are git-ignored but travel to the GPU box with the tree.
@@ -78,12 +79,16 @@ LPDENSE_FREE_SRC = os.path.join(CSRC, "lp_dense_free.hip")
 LIB_MILPDENSE = os.path.join(HERE, "libyalps_milpdense.so")
 MILPDENSE_SRC = os.path.join(CSRC, "milp_dense.hip")
 MILPDENSE_DEPS = [os.path.join(CSRC, f) for f in ("milp_dense_kernel.cuh", "milp_tree_kernel.cuh", "milp_tree_rules.cuh", "milp_tree_host.inc",
-                                                  "lp_batch_kernel.cuh", "milp_dense_bounds_kernel.cuh")] + QUEUE_DEPS  # (the last: the bounded call's structs)
+                                                  "lp_batch_kernel.cuh", "milp_dense_bounds_kernel.cuh", "milp_dense_free_kernel.cuh")] + QUEUE_DEPS  # (the last two: the structs of a call with bounds, with free variables)
 MILPDENSE_HEADER = os.path.join(ROOT, "include", "yalps_milpdense.h")
 # its root and solution kernels with bounds, a code object of their own that libyalps_milpdense.so links: the boundless library's holds the kernels it always held
 LIB_MILPDENSE_BOUNDS = os.path.join(HERE, "libyalps_milpdense_bounds.so")
 MILPDENSE_BOUNDS_SRC = os.path.join(CSRC, "milp_dense_bounds.hip")
 MILPDENSE_BOUNDS_DEPS = [os.path.join(CSRC, f) for f in ("milp_dense_bounds_kernel.cuh", "milp_dense_kernel.cuh", "milp_tree_rules.cuh")] + QUEUE_DEPS
+# and with free variables, likewise a code object of their own that libyalps_milpdense.so links
+LIB_MILPDENSE_FREE = os.path.join(HERE, "libyalps_milpdense_free.so")
+MILPDENSE_FREE_SRC = os.path.join(CSRC, "milp_dense_free.hip")
+MILPDENSE_FREE_DEPS = [os.path.join(CSRC, "milp_dense_free_kernel.cuh")] + MILPDENSE_BOUNDS_DEPS
 OBJ_DIR = os.path.join(HERE, "build")
 HEADER = os.path.join(ROOT, "include", "yalps_hip.h")
 NAPI_SRC = os.path.join(HERE, "napi", "yalps_napi.cc")
@@ -139,7 +144,7 @@ def kernel_metadata(lib=LIB):
 # scratch and without accumulator registers, or not at all.  (Two instantiations that broke this rule computed wrong
 # rows on the GPU -- DESIGN.md 4.7 -- so the rule is part of the build, not of an optional test.)
 # ("batch_kernel" also matches libyalps_lpbatch.so's lp_batch_kernel.)
-NO_SCRATCH = ("lp_sens", "lp_dense", "milp_dense_root_kernel", "milp_dense_solution_kernel", "milp_dense_bounds_root_kernel", "milp_dense_bounds_solution_kernel", "lp_variants", "lp_warm", "milp_node_kernel", "milp_tree_kernel", "dshard_kernel", "dshard_select_kernel", "dshard_sweep_kernel", "small_kernel", "batch_kernel", "assemble", "resident_kernel", "resident2_kernel", "stream_kernel", "stream2_kernel", "stream3_kernel", "sweep_kernel")
+NO_SCRATCH = ("lp_sens", "lp_dense", "milp_dense_root_kernel", "milp_dense_solution_kernel", "milp_dense_bounds_root_kernel", "milp_dense_bounds_solution_kernel", "milp_dense_free_root_kernel", "milp_dense_free_solution_kernel", "lp_variants", "lp_warm", "milp_node_kernel", "milp_tree_kernel", "dshard_kernel", "dshard_select_kernel", "dshard_sweep_kernel", "small_kernel", "batch_kernel", "assemble", "resident_kernel", "resident2_kernel", "stream_kernel", "stream2_kernel", "stream3_kernel", "sweep_kernel")
 
 
 # resident2_kernel<T, J, R>: scalar registers spilled to lanes of vector registers (sgpr_spill_count), at most what each
@@ -173,7 +178,7 @@ def check_register_budgets(lib=LIB, min_resident=15):
                 bad.append("%s: sgpr_spill_count %s, bound %d" % (name, md.get("sgpr_spill_count"), RESIDENT2_SGPR_SPILLS[shape]))
         if any(tag in name for tag in NO_SCRATCH) and int(md["private_segment_fixed_size"]) != 0:
             bad.append("%s: private_segment_fixed_size %s (scratch)" % (name, md["private_segment_fixed_size"]))
-        queue = "lp_dense_free_kernel" in name or "lp_dense_bounds_kernel" in name or "lp_batch_kernel" in name or "milp_node_kernel" in name or "lp_variants_kernel" in name or "lp_sens_kernel" in name or "lp_warm_kernel" in name or "milp_tree_kernel" in name or "lp_dense_kernel" in name or "milp_dense_root_kernel" in name or "milp_dense_bounds_root_kernel" in name
+        queue = "lp_dense_free_kernel" in name or "lp_dense_bounds_kernel" in name or "lp_batch_kernel" in name or "milp_node_kernel" in name or "lp_variants_kernel" in name or "lp_sens_kernel" in name or "lp_warm_kernel" in name or "milp_tree_kernel" in name or "lp_dense_kernel" in name or "milp_dense_root_kernel" in name or "milp_dense_bounds_root_kernel" in name or "milp_dense_free_root_kernel" in name
         if queue and int(md["agpr_count"]) != 0:
             bad.append("%s: agpr_count %s" % (name, md["agpr_count"]))
         # its dynamic LDS block (tableau and pivot row, swept 16 bytes at a time) starts where the static LDS ends
@@ -293,10 +298,12 @@ def build_lpdense(force=False, verbose=False):
 
 
 def build_milpdense(force=False, verbose=False):
-    """libyalps_milpdense_bounds.so first (build_milpdense_bounds); then libyalps_milpdense.so: milp_dense.hip alone, linking it."""
+    """libyalps_milpdense_bounds.so and libyalps_milpdense_free.so first (build_milpdense_bounds, build_milpdense_free); then
+    libyalps_milpdense.so: milp_dense.hip alone, linking both."""
     bounds = build_milpdense_bounds(force, verbose)
-    return build_single_unit(MILPDENSE_SRC, LIB_MILPDENSE, MILPDENSE_DEPS + [bounds], MILPDENSE_HEADER,
-                             ("milp_dense_root_kernel", "milp_dense_solution_kernel", "milp_tree_kernel"), force, verbose, link=(bounds,))
+    free = build_milpdense_free(force, verbose)
+    return build_single_unit(MILPDENSE_SRC, LIB_MILPDENSE, MILPDENSE_DEPS + [bounds, free], MILPDENSE_HEADER,
+                             ("milp_dense_root_kernel", "milp_dense_solution_kernel", "milp_tree_kernel"), force, verbose, link=(bounds, free))
 
 
 def build_milpdense_bounds(force=False, verbose=False):
@@ -304,6 +311,13 @@ def build_milpdense_bounds(force=False, verbose=False):
     milp_dense_bounds_solution_kernel, under the register budget of their boundless siblings."""
     return build_single_unit(MILPDENSE_BOUNDS_SRC, LIB_MILPDENSE_BOUNDS, MILPDENSE_BOUNDS_DEPS, MILPDENSE_HEADER,
                              ("milp_dense_bounds_root_kernel", "milp_dense_bounds_solution_kernel"), force, verbose)
+
+
+def build_milpdense_free(force=False, verbose=False):
+    """libyalps_milpdense_free.so: milp_dense_free.hip alone, the six milp_dense_free_root_kernel forms and
+    milp_dense_free_solution_kernel, under the register budget of their bounded siblings."""
+    return build_single_unit(MILPDENSE_FREE_SRC, LIB_MILPDENSE_FREE, MILPDENSE_FREE_DEPS, MILPDENSE_HEADER,
+                             ("milp_dense_free_root_kernel", "milp_dense_free_solution_kernel"), force, verbose)
 
 
 def build_napi(force=False, verbose=False):

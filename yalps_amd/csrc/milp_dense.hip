@@ -9,6 +9,9 @@
 // A call with bounds (lb / ub) runs milp_dense_bounds_root_kernel and milp_dense_bounds_solution_kernel
 // (milp_dense_bounds_kernel.cuh), whose forms are libyalps_milpdense_bounds.so's: this library links it and takes the kernels'
 // pointers from yalps_milpdense_bounds_forms, so its own code object holds the boundless kernels alone.
+// A call with free variables (n_free > 0) runs milp_dense_free_root_kernel and milp_dense_free_solution_kernel
+// (milp_dense_free_kernel.cuh) on a tableau n_free columns wider, the kernels of libyalps_milpdense_free.so, linked likewise;
+// milp_tree_kernel is given the twin columns of the free integer variables behind the integer variables' own.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -35,6 +38,7 @@ namespace {
 #include "milp_tree_kernel.cuh"
 #include "milp_dense_kernel.cuh"
 #include "milp_dense_bounds_kernel.cuh" // (the two structs of a bounded call; its kernels are not instantiated here)
+#include "milp_dense_free_kernel.cuh"   // (the two structs of a call with free variables, likewise)
 #include "wg_queue_host.inc"
 #include "milp_tree_host.inc"
 
@@ -45,6 +49,7 @@ constexpr int SOLUTION_LANES = 256;
 } // namespace
 
 extern "C" void yalps_milpdense_bounds_forms(void *out[7]); // milp_dense_bounds.hip
+extern "C" void yalps_milpdense_free_forms(void *out[7]);   // milp_dense_free.hip
 
 namespace {
 // libyalps_milpdense_bounds.so's kernels: the same table over its root forms, and its epilogue
@@ -64,6 +69,24 @@ const BoundsKernels &bounds_kernels() {
     }();
     return kernels;
 }
+
+// libyalps_milpdense_free.so's kernels, likewise
+struct FreeKernels {
+    KernelTable<MilpDenseLaunch> roots;
+    void (*solution)(MilpFreeSolutionArgs);
+};
+const FreeKernels &free_kernels() {
+    static const FreeKernels kernels = [] {
+        FreeKernels k{kRootKernels, nullptr};
+        k.roots.name = "milp_dense_free_root_kernel";
+        void *fn[7];
+        yalps_milpdense_free_forms(fn);
+        for (int f = 0; f < 6; f++) k.roots.forms[f].fn = reinterpret_cast<void (*)(MilpDenseLaunch)>(fn[f]);
+        k.solution = reinterpret_cast<void (*)(MilpFreeSolutionArgs)>(fn[6]);
+        return k;
+    }();
+    return kernels;
+}
 } // namespace
 
 struct yalps_milpdense : QueueDevice {
@@ -72,7 +95,7 @@ struct yalps_milpdense : QueueDevice {
     TreePass t;
     // the last solve
     std::vector<LpDesc> roots;
-    int32_t n = 0, w = 0, h0 = 0, nints = 0, count = 0;
+    int32_t n = 0, w = 0, h0 = 0, nints = 0, count = 0; // nints: the integer COLUMNS, the twins of free integer variables among them
     bool walked = false;          // there was a tree pass
     std::vector<int32_t> overflowed;
     std::string info;
@@ -102,7 +125,7 @@ int check_list(const char *name, int32_t len, const int32_t *list, int32_t n) {
 
 int validate(int32_t count, int32_t n, int32_t m_ub, int32_t m_eq, const yalps_milpdense_operand *c, const yalps_milpdense_operand *A_ub,
              const yalps_milpdense_operand *b_ub, const yalps_milpdense_operand *A_eq, const yalps_milpdense_operand *b_eq, int32_t nints,
-             const int32_t *ints, int32_t nbin, const int32_t *bin, int32_t n_upper = 0) {
+             const int32_t *ints, int32_t nbin, const int32_t *bin, int32_t n_upper = 0, int32_t n_free = 0, int32_t int_twins = 0) {
     if (count < 0) return fail(YALPS_E_ARG, "yalps_milpdense: count < 0");
     if (n < 0 || m_ub < 0 || m_eq < 0) return fail(YALPS_E_ARG, "yalps_milpdense: n, m_ub and m_eq must be at least 0");
     if (n_upper < 0) return fail(YALPS_E_ARG, "yalps_milpdense: n_upper < 0");
@@ -113,7 +136,14 @@ int validate(int32_t count, int32_t n, int32_t m_ub, int32_t m_eq, const yalps_m
         if (at >= nints || ints[at] != bin[k])
             return fail(YALPS_E_ARG, "yalps_milpdense: binary variable " + std::to_string(bin[k]) + " is not in integers (the union of both sets)");
     }
-    const int64_t w = (int64_t)n + 1, h = 1 + (int64_t)m_ub + 2 * (int64_t)m_eq + (int64_t)n_upper + nbin, hmax = h + 2 * (int64_t)nints;
+    const int64_t w = (int64_t)n + 1 + n_free, h = 1 + (int64_t)m_ub + 2 * (int64_t)m_eq + (int64_t)n_upper + nbin;
+    const int64_t hmax = h + 2 * ((int64_t)nints + int_twins);
+    if (n_free > 0 && (w > INT32_MAX || hmax > INT32_MAX || 8 * w * hmax > YALPS_MILPDENSE_MAX_BYTES))
+        return fail(YALPS_E_ARG, "yalps_milpdense: largest node of " + std::to_string(hmax) + " x " + std::to_string(w) + " doubles (" +
+                                     std::to_string(n_free) + " twin columns of free variables, " + std::to_string(h) +
+                                     " rows and two cuts for each of " + std::to_string(nints + int_twins) + " integer columns: " +
+                                     std::to_string(nints) + " integer variables and the twins of the " + std::to_string(int_twins) +
+                                     " free ones among them) is above the limit of " + std::to_string((long long)YALPS_MILPDENSE_MAX_BYTES) + " bytes");
     if (w > INT32_MAX || hmax > INT32_MAX || 8 * w * hmax > YALPS_MILPDENSE_MAX_BYTES)
         return fail(YALPS_E_ARG, "yalps_milpdense: largest node of " + std::to_string(hmax) + " x " + std::to_string(w) + " doubles (" +
                                      std::to_string(h) + " rows and two cuts for each of " + std::to_string(nints) +
@@ -131,8 +161,8 @@ int validate(int32_t count, int32_t n, int32_t m_ub, int32_t m_eq, const yalps_m
 int validate_bounds(int32_t count, int32_t n, int32_t m_ub, int32_t m_eq, const yalps_milpdense_operand *c, const yalps_milpdense_operand *A_ub,
                     const yalps_milpdense_operand *b_ub, const yalps_milpdense_operand *A_eq, const yalps_milpdense_operand *b_eq,
                     const yalps_milpdense_operand *lb, const yalps_milpdense_operand *ub, int32_t n_upper, const int32_t *upper_idx,
-                    int32_t nints, const int32_t *ints, int32_t nbin, const int32_t *bin) {
-    if (int rc = validate(count, n, m_ub, m_eq, c, A_ub, b_ub, A_eq, b_eq, nints, ints, nbin, bin, n_upper)) return rc;
+                    int32_t nints, const int32_t *ints, int32_t nbin, const int32_t *bin, int32_t n_free = 0, int32_t int_twins = 0) {
+    if (int rc = validate(count, n, m_ub, m_eq, c, A_ub, b_ub, A_eq, b_eq, nints, ints, nbin, bin, n_upper, n_free, int_twins)) return rc;
     if (lb)
         if (int rc = check_operand("lb", lb, count, n, 1)) return rc;
     if (ub)
@@ -150,6 +180,33 @@ int validate_bounds(int32_t count, int32_t n, int32_t m_ub, int32_t m_eq, const 
                                          " is binary (a binary variable has no bound row)");
     }
     return 0;
+}
+
+// the free variables of a call: free_idx is host memory, strictly ascending, inside 0 .. n-1, and names no binary variable; the
+// width counts the n_free twins, the largest node the two cuts of every twin of a free INTEGER variable too.  *int_twins_out:
+// their number.  n_free = 0: validate_bounds.
+int validate_free(int32_t count, int32_t n, int32_t m_ub, int32_t m_eq, const yalps_milpdense_operand *c, const yalps_milpdense_operand *A_ub,
+                  const yalps_milpdense_operand *b_ub, const yalps_milpdense_operand *A_eq, const yalps_milpdense_operand *b_eq,
+                  const yalps_milpdense_operand *lb, const yalps_milpdense_operand *ub, int32_t n_upper, const int32_t *upper_idx,
+                  int32_t n_free, const int32_t *free_idx, int32_t nints, const int32_t *ints, int32_t nbin, const int32_t *bin,
+                  int32_t *int_twins_out = nullptr) {
+    int32_t int_twins = 0;
+    if (n_free != 0) {
+        if (n < 0) return fail(YALPS_E_ARG, "yalps_milpdense: n, m_ub and m_eq must be at least 0");
+        if (int rc = check_list("integers", nints, ints, n)) return rc;
+        if (int rc = check_list("binaries", nbin, bin, n)) return rc;
+        if (int rc = check_list("free_idx", n_free, free_idx, n)) return rc;
+        for (int32_t t = 0, at = 0, ai = 0; t < n_free; t++) { // (all three ascending: one walk)
+            while (at < nbin && bin[at] < free_idx[t]) at++;
+            if (at < nbin && bin[at] == free_idx[t])
+                return fail(YALPS_E_ARG, "yalps_milpdense: free_idx[" + std::to_string(t) + "]: variable " + std::to_string(free_idx[t]) +
+                                             " is binary (a binary variable cannot be free)");
+            while (ai < nints && ints[ai] < free_idx[t]) ai++;
+            if (ai < nints && ints[ai] == free_idx[t]) int_twins++;
+        }
+    }
+    if (int_twins_out) *int_twins_out = int_twins;
+    return validate_bounds(count, n, m_ub, m_eq, c, A_ub, b_ub, A_eq, b_eq, lb, ub, n_upper, upper_idx, nints, ints, nbin, bin, n_free, int_twins);
 }
 
 // A pointer a kernel is to dereference: device (or managed) memory of the handle's device, known to THIS runtime
@@ -187,6 +244,7 @@ int create_impl(int32_t device, void *hip_stream, yalps_milpdense **out) {
     b->info = "launches=0 reruns=0 overflows=0 gpu_us=0 root_us=0 tree_us=0 epilogue_us=0 rerun_lps=[] rerun_trees=[]\n";
     if (int rc = raise_lds_limit(kRootKernels)) return rc;
     if (int rc = raise_lds_limit(bounds_kernels().roots)) return rc;
+    if (int rc = raise_lds_limit(free_kernels().roots)) return rc;
     return raise_lds_limit(kTreeKernels);
 }
 
@@ -203,9 +261,12 @@ int solve_impl(yalps_milpdense *b, const char *entry, int32_t count, int32_t n, 
                int32_t maximize, double precision, double maxPivots, int32_t checkCycles, double tolerance, double maxIter,
                int32_t trace_cap, double *x_out, double *objective_out, int32_t *status_out, int64_t *nodes_out,
                int64_t *node_pivots_out, int64_t *root_pivots_out, Times &tm, const yalps_milpdense_operand *lb = nullptr,
-               const yalps_milpdense_operand *ub = nullptr, int32_t n_upper = 0, const int32_t *upper_idx = nullptr) {
+               const yalps_milpdense_operand *ub = nullptr, int32_t n_upper = 0, const int32_t *upper_idx = nullptr, int32_t n_free = 0,
+               const int32_t *free_idx = nullptr) {
     TreePass &t = b->t;
-    const bool bounds = lb || ub; // (either descriptor: the bounded kernels; neither: the kernels and the bits of before)
+    const bool split = n_free > 0; // (any free variable: the free kernels, with or without bounds)
+    const bool bounds = lb || ub;  // (else either descriptor: the bounded kernels; neither: the kernels and the bits of before)
+    const bool lists = split || bounds; // the bound rows' index list and the kind bytes are uploaded
     b->count = 0;
     b->walked = false;
     b->overflowed.clear();
@@ -215,7 +276,10 @@ int solve_impl(yalps_milpdense *b, const char *entry, int32_t count, int32_t n, 
     t.launches = t.overflows = 0;
     t.gpu_ms = 0.0;
     if (trace_cap < 0) return fail(YALPS_E_ARG, std::string(entry) + ": trace_cap < 0");
-    if (int rc = validate_bounds(count, n, m_ub, m_eq, c, A_ub, b_ub, A_eq, b_eq, lb, ub, n_upper, upper_idx, nints, ints, nbin, bin)) return rc;
+    int32_t int_twins = 0;
+    if (int rc = validate_free(count, n, m_ub, m_eq, c, A_ub, b_ub, A_eq, b_eq, lb, ub, n_upper, upper_idx, n_free, free_idx, nints, ints, nbin, bin,
+                               &int_twins))
+        return rc;
     if (count == 0) return 0;
     HIP_TRY(hipSetDevice(b->device));
     const struct {
@@ -238,18 +302,22 @@ int solve_impl(yalps_milpdense *b, const char *entry, int32_t count, int32_t n, 
         if (int rc = check_pointer(b, entry, a.name, a.p)) return rc;
 
     hipStream_t s = b->stream;
-    const int32_t w = n + 1, h = 1 + m_ub + 2 * m_eq + n_upper + nbin, hmax = h + 2 * nints;
+    const int32_t cols_n = nints + int_twins; // n_int_eff: the integer columns the trees branch on
+    const int32_t w = n + 1 + n_free, h = 1 + m_ub + 2 * m_eq + n_upper + nbin, hmax = h + 2 * cols_n;
     const size_t cnt = (size_t)count, heven = ((size_t)h + 1) & ~(size_t)1, perm = (size_t)w + (size_t)h;
     const bool aux = lp_class(w, h) == HBM_CLASS && lp_aux_hbm(w, h);
 
     // ---- the root pass: the description and the binary list behind it, one launch per pass, tableaux kept for the trees
-    // (a bounded call: the longer description, and behind the binary list the bound rows' index list and the kind bytes)
-    const size_t desc_bytes = bounds ? sizeof(MilpDenseBoundsCall) : sizeof(MilpDenseCall), call_bytes = (desc_bytes + 15) & ~(size_t)15;
+    // (a bounded call: the longer description, and behind the binary list the bound rows' index list and the kind bytes; a call
+    // with free variables: the longest, and behind the kind bytes, from the next multiple of 4, free_idx and twin)
+    const size_t desc_bytes = split ? sizeof(MilpDenseFreeCall) : bounds ? sizeof(MilpDenseBoundsCall) : sizeof(MilpDenseCall);
+    const size_t call_bytes = (desc_bytes + 15) & ~(size_t)15;
     const size_t bin_bytes = sizeof(int32_t) * (size_t)nbin, idx_bytes = sizeof(int32_t) * (size_t)n_upper;
-    if (int rc = ensure(b->call, call_bytes + bin_bytes + (bounds ? idx_bytes + (size_t)n : 0))) return rc;
+    const size_t kind_bytes = ((size_t)n + 3) & ~(size_t)3, free_bytes = sizeof(int32_t) * (size_t)n_free, twin_bytes = sizeof(int32_t) * (size_t)n;
+    if (int rc = ensure(b->call, call_bytes + bin_bytes + (lists ? idx_bytes + (split ? kind_bytes + free_bytes + twin_bytes : (size_t)n) : 0))) return rc;
     b->q.keep = true;
     if (int rc = ensure_outputs(b->q, cnt, heven * cnt, perm * cnt, (size_t)w * (size_t)h * cnt)) return rc;
-    MilpDenseBoundsCall D{};
+    MilpDenseFreeCall D{};
     D.n = n, D.m_ub = m_ub, D.m_eq = m_eq, D.n_bin = nbin;
     D.aux_hbm = aux ? 1 : 0;
     D.sign = maximize ? 1.0 : -1.0;
@@ -262,7 +330,8 @@ int solve_impl(yalps_milpdense *b, const char *entry, int32_t count, int32_t n, 
     D.b_eq = operand(b_eq, true);
     D.bin = reinterpret_cast<const int32_t *>(b->call.as<char>() + call_bytes);
     std::vector<uint8_t> kinds; // 0 continuous, 1 integer, 2 binary
-    if (bounds) {
+    std::vector<int32_t> twins; // the twin's column of a free variable, -1 of any other
+    if (lists) {
         if (lb && n) D.lb = operand(lb, true);
         if (ub && n_upper) D.ub = operand(ub, true);
         D.n_upper = n_upper;
@@ -274,16 +343,26 @@ int solve_impl(yalps_milpdense *b, const char *entry, int32_t count, int32_t n, 
         for (int32_t k = 0; k < nbin; k++) kinds[(size_t)bin[k]] = 2;
         if (n_upper) HIP_TRY(hipMemcpyAsync(behind, upper_idx, idx_bytes, hipMemcpyHostToDevice, s));
         if (n) HIP_TRY(hipMemcpyAsync(behind + idx_bytes, kinds.data(), (size_t)n, hipMemcpyHostToDevice, s));
+        if (split) {
+            char *lists_at = behind + idx_bytes + kind_bytes;
+            D.n_free = n_free;
+            D.free_idx = reinterpret_cast<const int32_t *>(lists_at);
+            D.twin = reinterpret_cast<const int32_t *>(lists_at + free_bytes);
+            twins.assign((size_t)n, -1);
+            for (int32_t k = 0; k < n_free; k++) twins[(size_t)free_idx[k]] = 1 + n + k;
+            HIP_TRY(hipMemcpyAsync(lists_at, free_idx, free_bytes, hipMemcpyHostToDevice, s));
+            HIP_TRY(hipMemcpyAsync(lists_at + free_bytes, twins.data(), twin_bytes, hipMemcpyHostToDevice, s));
+        }
     }
     HIP_TRY(hipMemcpyAsync(b->call.p, &D, desc_bytes, hipMemcpyHostToDevice, s));
     if (nbin) HIP_TRY(hipMemcpyAsync(b->call.as<char>() + call_bytes, bin, bin_bytes, hipMemcpyHostToDevice, s));
     if (int rc = reset_status(b->q, s, cnt)) return rc;
-    HIP_TRY(hipStreamSynchronize(s)); // (D and kinds are on this frame, `bin` and `upper_idx` are the caller's)
-    b->n = n, b->w = w, b->h0 = h, b->nints = nints;
+    HIP_TRY(hipStreamSynchronize(s)); // (D, kinds and twins are on this frame, `bin`, `upper_idx` and `free_idx` are the caller's)
+    b->n = n, b->w = w, b->h0 = h, b->nints = cols_n;
 
     QueueRun run;
     const int rc = run_queue(
-        *b, b->q, bounds ? bounds_kernels().roots : kRootKernels, QueueText{"yalps_milpdense", true, entry, "MILP"}, cnt,
+        *b, b->q, split ? free_kernels().roots : bounds ? bounds_kernels().roots : kRootKernels, QueueText{"yalps_milpdense", true, entry, "MILP"}, cnt,
         [&](int32_t, int *iw, int *ih) { return *iw = w, *ih = h, checkCycles != 0; },
         [&](MilpDenseLaunch &a) { a.call = b->call.as<const MilpDenseCall>(); }, [] { return 0; },
         [&](const Launch &L, const std::string &kernel, int pass, int launch, long long hist_cap) {
@@ -305,7 +384,7 @@ int solve_impl(yalps_milpdense *b, const char *entry, int32_t count, int32_t n, 
         std::vector<LpDesc> &R = b->roots;
         std::vector<TreeDesc> T(cnt);
         R.resize(cnt);
-        const int32_t maxcuts = std::max(1, 2 * nints), cls = lp_class(w, hmax);
+        const int32_t maxcuts = std::max(1, 2 * cols_n), cls = lp_class(w, hmax);
         const size_t tree_col0 = ((size_t)hmax + 1) & ~(size_t)1, tree_perm = (size_t)w + (size_t)hmax;
         const size_t tree_trace = (size_t)trace_cap * (4 + 2 * (size_t)maxcuts);
         for (size_t i = 0; i < cnt; i++) {
@@ -317,7 +396,7 @@ int solve_impl(yalps_milpdense *b, const char *entry, int32_t count, int32_t n, 
             r.aux_hbm = aux ? 1 : 0;
             TreeDesc &d = T[i];
             d = TreeDesc{};
-            d.nints = nints, d.maxcuts = maxcuts;
+            d.nints = cols_n, d.maxcuts = maxcuts;
             d.ints_off = 0; // (one list for the whole call)
             d.sign = D.sign, d.tolerance = tolerance, d.max_iter = maxIter;
             d.timedout = 0;
@@ -325,20 +404,25 @@ int solve_impl(yalps_milpdense *b, const char *entry, int32_t count, int32_t n, 
             d.col0_off = (long long)(i * tree_col0), d.perm_off = (long long)(i * tree_perm), d.trace_off = (long long)(i * tree_trace);
             d.aux_hbm = lp_aux_hbm(w, hmax) ? 1 : 0;
         }
-        std::vector<int32_t> cols((size_t)nints); // the tableau's columns: variable j is column j + 1
+        // the tableau's integer columns: variable j is column j + 1; behind them the twins of the free integer variables in
+        // ascending j (every twin's column is above n), so the whole list ascends
+        std::vector<int32_t> cols((size_t)nints);
         for (int32_t k = 0; k < nints; k++) cols[(size_t)k] = ints[k] + 1;
+        if (split)
+            for (int32_t k = 0; k < nints; k++)
+                if (twins[(size_t)ints[k]] >= 0) cols.push_back(twins[(size_t)ints[k]]);
         t.q.keep = false;
         t.trace_cap = trace_cap;
         if (int rc2 = ensure(b->rdesc, sizeof(LpDesc) * cnt)) return rc2;
         if (int rc2 = ensure(t.tdesc, sizeof(TreeDesc) * cnt)) return rc2;
-        if (int rc2 = ensure(t.ints, sizeof(int32_t) * (size_t)nints)) return rc2;
+        if (int rc2 = ensure(t.ints, sizeof(int32_t) * cols.size())) return rc2;
         if (int rc2 = ensure(t.d_used, sizeof(long long) * cnt)) return rc2;
         if (int rc2 = ensure(t.d_best_h, sizeof(int32_t) * cnt)) return rc2;
         if (int rc2 = ensure(t.d_trace, sizeof(double) * tree_trace * cnt)) return rc2;
         if (int rc2 = ensure_outputs(t.q, cnt, tree_col0 * cnt, tree_perm * cnt, 0)) return rc2;
         HIP_TRY(hipMemcpyAsync(b->rdesc.p, R.data(), sizeof(LpDesc) * cnt, hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemcpyAsync(t.tdesc.p, T.data(), sizeof(TreeDesc) * cnt, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(t.ints.p, cols.data(), sizeof(int32_t) * (size_t)nints, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(t.ints.p, cols.data(), sizeof(int32_t) * cols.size(), hipMemcpyHostToDevice, s));
         if (int rc2 = reset_status(t.q, s, cnt)) return rc2;
         HIP_TRY(hipStreamSynchronize(s)); // (T and cols are on this frame)
         t.trees = std::move(T);
@@ -359,7 +443,7 @@ int solve_impl(yalps_milpdense *b, const char *entry, int32_t count, int32_t n, 
         if (nodes_out) HIP_TRY(hipMemsetAsync(nodes_out, 0, sizeof(int64_t) * cnt, s));
         if (node_pivots_out) HIP_TRY(hipMemsetAsync(node_pivots_out, 0, sizeof(int64_t) * cnt, s));
     }
-    MilpBoundsSolutionArgs a{};
+    MilpFreeSolutionArgs a{};
     a.n = n, a.h0 = h, a.hmax = hmax, a.overflow = YALPS_MILPDENSE_OVERFLOW;
     a.sign = D.sign, a.precision = precision;
     a.status = last.status.as<const int32_t>();
@@ -372,10 +456,15 @@ int solve_impl(yalps_milpdense *b, const char *entry, int32_t count, int32_t n, 
     a.status_out = status_out, a.nodes_out = reinterpret_cast<long long *>(nodes_out);
     a.node_pivots_out = reinterpret_cast<long long *>(node_pivots_out);
     HIP_TRY(hipEventRecord(b->ev0, s));
-    if (bounds) {
+    if (split) {
+        a.c = D.c, a.lb = D.lb, a.kind = D.kind;
+        a.n_free = n_free, a.twin = D.twin;
+        void (*const solution)(MilpFreeSolutionArgs) = free_kernels().solution;
+        solution<<<dim3((unsigned)count), dim3(SOLUTION_LANES), 0, s>>>(a);
+    } else if (bounds) {
         a.c = D.c, a.lb = D.lb, a.kind = D.kind;
         void (*const solution)(MilpBoundsSolutionArgs) = bounds_kernels().solution;
-        solution<<<dim3((unsigned)count), dim3(SOLUTION_LANES), 0, s>>>(a);
+        solution<<<dim3((unsigned)count), dim3(SOLUTION_LANES), 0, s>>>(static_cast<const MilpBoundsSolutionArgs &>(a));
     } else {
         milp_dense_solution_kernel<SOLUTION_LANES><<<dim3((unsigned)count), dim3(SOLUTION_LANES), 0, s>>>(static_cast<const MilpSolutionArgs &>(a));
     }
@@ -385,7 +474,7 @@ int solve_impl(yalps_milpdense *b, const char *entry, int32_t count, int32_t n, 
     HIP_TRY(hipEventElapsedTime(&tm.epilogue, b->ev0, b->ev1));
     char line[192];
     std::snprintf(line, sizeof line, "launch=%lld pass=0 kernel=milp_dense_%ssolution_kernel<%d> class=-1 trees=%d grid=%d lds=0 hist_cap=0\n",
-                  (long long)t.launches++, bounds ? "bounds_" : "", SOLUTION_LANES, count, count);
+                  (long long)t.launches++, split ? "free_" : bounds ? "bounds_" : "", SOLUTION_LANES, count, count);
     tm.epilogue_line = line;
     b->walked = walk;
     b->count = count;
@@ -445,6 +534,16 @@ int32_t yalps_milpdense_validate_bounds(int32_t count, int32_t n, int32_t m_ub, 
                            binaries);
 }
 
+int32_t yalps_milpdense_validate_free(int32_t count, int32_t n, int32_t m_ub, int32_t m_eq, const yalps_milpdense_operand *c,
+                                      const yalps_milpdense_operand *A_ub, const yalps_milpdense_operand *b_ub,
+                                      const yalps_milpdense_operand *A_eq, const yalps_milpdense_operand *b_eq,
+                                      const yalps_milpdense_operand *lb, const yalps_milpdense_operand *ub, int32_t n_upper,
+                                      const int32_t *upper_idx, int32_t n_free, const int32_t *free_idx, int32_t n_integers,
+                                      const int32_t *integers, int32_t n_binaries, const int32_t *binaries) {
+    return validate_free(count, n, m_ub, m_eq, c, A_ub, b_ub, A_eq, b_eq, lb, ub, n_upper, upper_idx, n_free, free_idx, n_integers, integers,
+                         n_binaries, binaries);
+}
+
 int32_t yalps_milpdense_create(int32_t device, void *hip_stream, yalps_milpdense **out) {
     if (!out) return fail(YALPS_E_ARG, "yalps_milpdense_create: out is NULL");
     *out = nullptr;
@@ -496,6 +595,28 @@ int32_t yalps_milpdense_solve_bounds(yalps_milpdense *d, int32_t count, int32_t 
                                   n_binaries, binaries, maximize, precision, maxPivots, checkCycles, tolerance, maxIterations, trace_cap,
                                   x_out, objective_out, status_out, nodes_out, node_pivots_out, root_pivots_out, tm, lb, ub, n_upper,
                                   upper_idx);
+    if (rc) d->count = 0; // (no last solve to read from)
+    info_close(d, tm);
+    call_stats(d, tm, call_stats_out);
+    return rc;
+}
+
+int32_t yalps_milpdense_solve_free(yalps_milpdense *d, int32_t count, int32_t n, int32_t m_ub, int32_t m_eq,
+                                   const yalps_milpdense_operand *c, const yalps_milpdense_operand *A_ub,
+                                   const yalps_milpdense_operand *b_ub, const yalps_milpdense_operand *A_eq,
+                                   const yalps_milpdense_operand *b_eq, const yalps_milpdense_operand *lb,
+                                   const yalps_milpdense_operand *ub, int32_t n_upper, const int32_t *upper_idx, int32_t n_free,
+                                   const int32_t *free_idx, int32_t n_integers, const int32_t *integers, int32_t n_binaries,
+                                   const int32_t *binaries, int32_t maximize, double precision, double maxPivots, int32_t checkCycles,
+                                   double tolerance, double maxIterations, int32_t trace_cap, double *x_out, double *objective_out,
+                                   int32_t *status_out, int64_t *nodes_out, int64_t *node_pivots_out, int64_t *root_pivots_out,
+                                   int64_t *call_stats_out) {
+    if (!d) return fail(YALPS_E_ARG, "yalps_milpdense_solve_free: handle is NULL");
+    Times tm;
+    const int32_t rc = solve_impl(d, "yalps_milpdense_solve_free", count, n, m_ub, m_eq, c, A_ub, b_ub, A_eq, b_eq, n_integers, integers,
+                                  n_binaries, binaries, maximize, precision, maxPivots, checkCycles, tolerance, maxIterations, trace_cap,
+                                  x_out, objective_out, status_out, nodes_out, node_pivots_out, root_pivots_out, tm, lb, ub, n_upper,
+                                  upper_idx, n_free, free_idx);
     if (rc) d->count = 0; // (no last solve to read from)
     info_close(d, tm);
     call_stats(d, tm, call_stats_out);

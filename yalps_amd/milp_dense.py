@@ -3,7 +3,9 @@ call, and the fallback for trees that overflowed on the device -- tableauModel's
 src/tableau.ts:47-137), its cells as the lockstep driver (_native.MilpBatch) takes them, and solution() (src/YALPS.ts:8-50)
 of a best tableau as a dense row.  With variable bounds (milp_batch's lb, ub, upper) the tableau is the bounded one -- the
 right-hand sides moved by shift_sum with the effective lower bounds, the bound rows between the equality rows and the binary
-rows -- and the dense row is moved back."""
+rows -- and the dense row is moved back.  With free variables (milp_batch_free's free) it is the split one: one twin column per free
+variable behind the n originals, the twins of the free integer variables among the integer columns, and the dense row is
+x[j] = v(p) - v(q) there."""
 import math
 
 import numpy as np
@@ -43,9 +45,10 @@ def integer_sets(n, integers=(), binaries=(), who="milp_batch"):
     return sorted(set(ints) | set(bins)), bins
 
 
-def largest_node_bytes(n, m_ub, m_eq, n_int, n_bin, k=0):
-    """8 * w * (h + 2 * n_int): the root's k bound rows and n_bin binary rows, and two cuts per integer variable."""
-    return 8 * (n + 1) * (1 + m_ub + 2 * m_eq + k + n_bin + 2 * n_int)
+def largest_node_bytes(n, m_ub, m_eq, n_int, n_bin, k=0, f=0, int_twins=0):
+    """8 * w * (h + 2 * n_int_eff): the root's k bound rows and n_bin binary rows, two cuts per integer COLUMN -- the n_int
+    integer variables and the int_twins twins of the free ones among them -- and f twin columns in the width."""
+    return 8 * (n + 1 + f) * (1 + m_ub + 2 * m_eq + k + n_bin + 2 * (n_int + int_twins))
 
 
 SHIFT_LANES = 64
@@ -83,9 +86,30 @@ def bound_rows(idx, binaries, everything, who="milp_batch"):
     return list(idx)
 
 
-def effective_lower(lb, integers=(), binaries=()):
+def free_set(idx, binaries, everything, who="milp_batch"):
+    """The free variables: `idx` is the ascending list `free` stands for (tensors._free_set).  everything (free was True): every
+    variable that is not binary; else the list as it is, and one that names a binary variable is a ValueError, as bound_rows
+    refuses it -- a binary variable is 0 or 1 and cannot be free."""
+    bins = set(int(j) for j in binaries)
+    if everything:
+        return [j for j in idx if j not in bins]
+    named = [j for j in idx if j in bins]
+    if named:
+        raise ValueError("%s: free names variable %d, which is binary: a binary variable cannot be free" % (who, named[0]))
+    return list(idx)
+
+
+def integer_columns(n, integers, free=()):
+    """The tableau's integer columns as the trees take them: 1 + j of the integer variables in ascending j, then the twin
+    columns 1 + n + t of the free integer variables in ascending j -- the whole list ascends."""
+    ints, fidx = [int(j) for j in integers], sorted(int(j) for j in free)
+    return [j + 1 for j in ints] + [1 + n + t for t, j in enumerate(fidx) if j in set(ints)]
+
+
+def effective_lower(lb, integers=(), binaries=(), free=()):
     """l_eff of ONE MILP: lb[j] at a continuous variable, ceil(lb[j]) at an integer one (IEEE: ceil(-0.5) is -0.0; NaN and the
-    infinities pass through), +0.0 at a binary one, whatever lb holds there.  None without lb."""
+    infinities pass through), +0.0 at a binary one and at a free one, integer or not, whatever lb holds there.  None without
+    lb."""
     if lb is None:
         return None
     l = np.array(lb, np.float64).reshape(-1)
@@ -93,68 +117,87 @@ def effective_lower(lb, integers=(), binaries=()):
     with np.errstate(all="ignore"):
         l[ints] = np.ceil(l[ints])
     l[bins] = 0.0
+    l[[int(j) for j in free]] = 0.0
     return l
 
 
-def dense_tableau(c, A_ub=None, b_ub=None, A_eq=None, b_eq=None, binaries=(), maximize=False, integers=(), lb=None, ub=None, upper=()):
+def dense_tableau(c, A_ub=None, b_ub=None, A_eq=None, b_eq=None, binaries=(), maximize=False, integers=(), lb=None, ub=None, upper=(),
+                  free=()):
     """The flat row-major (1 + m_ub + 2 m_eq + k + n_bin) x (n + 1) matrix of ONE MILP: row 0 = +0.0, sign * c (a product); rows
     1 + i = b_ub[i], A_ub[i]; rows 1 + m_ub + 2k and the next = b_eq[k], A_eq[k] and their negations; then one row per binary
     variable j in ascending order: column 0 and column j + 1 are 1.0.
     Bounds: with lb, column 0 of every operand row is moved by shift_sum(row, l_eff), one subtraction (negated in the second
     row of an equality), l_eff = effective_lower(lb, integers, binaries); and between the equality rows and the binary rows
-    come k = len(upper) rows, ascending: ub[j] - l_eff[j] (or ub[j]) in column 0, 1.0 in column j + 1."""
+    come k = len(upper) rows, ascending: ub[j] - l_eff[j] (or ub[j]) in column 0, 1.0 in column j + 1.
+    Free variables: the matrix is f = len(free) columns wider; twin t, column 1 + n + t, of the t-th free variable j in ascending
+    order holds the IEEE negation of column 1 + j in every operand row, -1.0 in j's bound row, +0.0 in every other generated
+    row; l_eff is +0.0 at j."""
     c = np.asarray(c, np.float64)
     n = c.shape[0]
     m_ub = 0 if b_ub is None else len(b_ub)
     m_eq = 0 if b_eq is None else len(b_eq)
     bins = sorted(int(j) for j in binaries)
     idx = sorted(int(j) for j in upper)
-    low = effective_lower(lb, integers, bins)
+    fidx = sorted(int(j) for j in free)
+    low = effective_lower(lb, integers, bins, fidx)
     h0 = 1 + m_ub + 2 * m_eq
     hb = h0 + len(idx)
-    m = np.zeros((hb + len(bins), n + 1), np.float64)
-    m[0, 1:] = np.float64(1.0 if maximize else -1.0) * c
+    m = np.zeros((hb + len(bins), n + 1 + len(fidx)), np.float64)
+    m[0, 1:n + 1] = np.float64(1.0 if maximize else -1.0) * c
     if m_ub:
         m[1:1 + m_ub, 0] = b_ub
-        m[1:1 + m_ub, 1:] = np.asarray(A_ub, np.float64).reshape(m_ub, n)
+        m[1:1 + m_ub, 1:n + 1] = np.asarray(A_ub, np.float64).reshape(m_ub, n)
     if m_eq:
         A, b = np.asarray(A_eq, np.float64).reshape(m_eq, n), np.asarray(b_eq, np.float64)
-        m[1 + m_ub:h0:2, 0], m[1 + m_ub:h0:2, 1:] = b, A
-        m[2 + m_ub:h0:2, 0], m[2 + m_ub:h0:2, 1:] = -b, -A
+        m[1 + m_ub:h0:2, 0], m[1 + m_ub:h0:2, 1:n + 1] = b, A
+        m[2 + m_ub:h0:2, 0], m[2 + m_ub:h0:2, 1:n + 1] = -b, -A
     with np.errstate(all="ignore"):
         if low is not None:
             for i in range(m_ub):
-                m[1 + i, 0] = m[1 + i, 0] - shift_sum(m[1 + i, 1:], low)
+                m[1 + i, 0] = m[1 + i, 0] - shift_sum(m[1 + i, 1:n + 1], low)
             for k in range(m_eq):
-                v = m[1 + m_ub + 2 * k, 0] - shift_sum(m[1 + m_ub + 2 * k, 1:], low)
+                v = m[1 + m_ub + 2 * k, 0] - shift_sum(m[1 + m_ub + 2 * k, 1:n + 1], low)
                 m[1 + m_ub + 2 * k, 0], m[2 + m_ub + 2 * k, 0] = v, -v
         for t, j in enumerate(idx):
             u = np.float64(np.asarray(ub, np.float64).reshape(-1)[j])
             m[h0 + t, 0] = u - low[j] if low is not None else u
             m[h0 + t, j + 1] = 1.0
+            if j in fidx:
+                m[h0 + t, 1 + n + fidx.index(j)] = -1.0
+    for t, j in enumerate(fidx):
+        m[:h0, 1 + n + t] = -m[:h0, 1 + j]
     for q, j in enumerate(bins):
         m[hb + q, 0] = m[hb + q, j + 1] = 1.0
     return m.ravel()
 
 
-def packed_milp(lp, integers, binaries, maximize, options, lb=None, ub=None, upper=()):
+def packed_milp(lp, integers, binaries, maximize, options, lb=None, ub=None, upper=(), free=()):
     """One dense MILP as _native.PackedMilps takes it: (width, height, row, col, val, integer columns, sign, options).
     lp = (c, A_ub, b_ub, A_eq, b_eq); integers / binaries as integer_sets returns them; lb / ub / upper: its bounds
-    (dense_tableau)."""
-    m = dense_tableau(*lp, binaries=binaries, maximize=maximize, integers=integers, lb=lb, ub=ub, upper=upper)
-    w = len(lp[0]) + 1
+    and free variables (dense_tableau; the integer columns by integer_columns)."""
+    m = dense_tableau(*lp, binaries=binaries, maximize=maximize, integers=integers, lb=lb, ub=ub, upper=upper, free=free)
+    n = len(lp[0])
+    w = n + 1 + len(free)
     h = m.size // w
-    return (w, h, *_native.dense_cells(m, w, h), [j + 1 for j in integers], 1.0 if maximize else -1.0, options)
+    return (w, h, *_native.dense_cells(m, w, h), integer_columns(n, integers, free), 1.0 if maximize else -1.0, options)
 
 
-def dense_solution(col0, pos, var, status, result, sign, precision, n, c=None, low=None):
+def dense_solution(col0, pos, var, status, result, sign, precision, n, c=None, low=None, free=()):
     """(x[n], objective) of one best tableau of width n + 1, as solution() reads it.  low (effective_lower's l_eff) and c: the
     answer in x' moved back, x = x' + low and objective = objective' + shift_sum(c, low), one addition each whatever the
-    status."""
+    status.  free: the tableau is len(free) columns wider and x[j] of a free variable is v(p) - v(q), one subtraction of the two
+    columns' own values -- so an unbounded twin gives -inf -- in front of the addition of low."""
     if low is not None:
-        x, objective = dense_solution(col0, pos, var, status, result, sign, precision, n)
+        x, objective = dense_solution(col0, pos, var, status, result, sign, precision, n, free=free)
         with np.errstate(all="ignore"):
             return x + np.asarray(low, np.float64), float(np.float64(objective) + shift_sum(c, low))
+    if len(free):
+        fidx = sorted(int(j) for j in free)
+        wide, objective = dense_solution(col0, pos, var, status, result, sign, precision, n + len(fidx))
+        x = wide[:n].copy()
+        with np.errstate(all="ignore"):
+            x[fidx] = wide[fidx] - wide[n:]
+        return x, objective
     w = n + 1
     if status == "optimal" or (status == "timedout" and not math.isnan(result)):
         x = np.zeros(n, np.float64)

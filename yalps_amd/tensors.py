@@ -243,7 +243,7 @@ def linprog_batch(c, A_ub=None, b_ub=None, A_eq=None, b_eq=None, *, lb=None, ub=
     the twin's -- about 0 at an optimum, as scipy reports -- so the two identities above hold at every j, with the effective
     lower bound in place of lb.  A call with free variables runs lp_dense_free_kernel, with or without lb / ub.
     Out of scope: per-LP `upper` and `free` sets, and inferring freeness from the data (an lb entry of -inf at a variable `free`
-    does not list is taken as it lies in memory, like every other value).  milp_batch takes lb, ub and upper, not free.
+    does not list is taken as it lies in memory, like every other value).  milp_batch takes lb, ub and upper; milp_batch_free takes free too.
 
     See the module's docstring for the loading rule: torch first."""
     sets = {}
@@ -440,12 +440,14 @@ def linprog_objective_bounds(c, A_ub=None, b_ub=None, A_eq=None, b_eq=None, *, l
 
 
 def _solve_on_host(device, rows, given, batched, B, ints, bins, maximize, options, out, bounds=(None, None), bounds_batched=(False, False),
-                   upper=()):
+                   upper=(), free=()):
     """The trees `rows` of a milp_batch call through the lockstep driver (_native.MilpBatch.solve), as solve.milptree_solve
     sends its overflows: their operands are gathered on the device and copied to the host, their tableaux built there
     (milp_dense.packed_milp), and x / objective / status / nodes written into the output tensors `out`.  node_pivots of such
     a row is -1: the lockstep driver does not count the pivots of the nodes it consumes.  bounds = (lb, ub) tensors or None:
-    gathered likewise, the tableaux are the bounded ones and x / objective are moved back (milp_dense.dense_solution)."""
+    gathered likewise, the tableaux are the bounded ones and x / objective are moved back (milp_dense.dense_solution).  free:
+    the tableaux are the split ones, the driver branches on the twins of the free integer variables too, and the halves are
+    subtracted on the way back."""
     from . import milp_dense
     idx = torch.tensor(rows, dtype=torch.int64, device=device)
     host = []
@@ -456,9 +458,9 @@ def _solve_on_host(device, rows, given, batched, B, ints, bins, maximize, option
             host.append((t.index_select(0, idx) if has_batch else t).cpu().numpy())
     lbs, ubs = (None if t is None else (t.index_select(0, idx) if has_batch else t).cpu().numpy() for t, has_batch in zip(bounds, bounds_batched))
     pick = lambda k, a, has_batch: None if a is None else (a[k] if has_batch else a)
-    low_of = lambda k: milp_dense.effective_lower(pick(k, lbs, bounds_batched[0]), ints, bins)
+    low_of = lambda k: milp_dense.effective_lower(pick(k, lbs, bounds_batched[0]), ints, bins, free)
     milps = [milp_dense.packed_milp(tuple(pick(k, a, hb) for a, hb in zip(host, batched)), ints, bins, maximize, options,
-                                    lb=pick(k, lbs, bounds_batched[0]), ub=pick(k, ubs, bounds_batched[1]), upper=upper)
+                                    lb=pick(k, lbs, bounds_batched[0]), ub=pick(k, ubs, bounds_batched[1]), upper=upper, free=free)
              for k in range(len(rows))]
     batch = _fallbacks.get(device.index)
     if batch is None:
@@ -470,7 +472,7 @@ def _solve_on_host(device, rows, given, batched, B, ints, bins, maximize, option
     for k, (st, res) in enumerate(zip(statuses, results)):
         _, col0, pos, var = batch.solution(k)
         x, obj = milp_dense.dense_solution(col0, pos, var, st, float(res), sign, options["precision"], n,
-                                           c=pick(k, host[0], batched[0]), low=low_of(k))
+                                           c=pick(k, host[0], batched[0]), low=low_of(k), free=free)
         xs.append(x)
         objs.append(obj)
     dev = lambda a, dtype: torch.as_tensor(a, dtype=dtype).to(device)
@@ -543,16 +545,78 @@ def milp_batch(c, A_ub=None, b_ub=None, A_eq=None, b_eq=None, *, lb=None, ub=Non
     {"max": ub[j] - l_eff[j]}, "integers" / "binaries" as given), moved back.  With no integer and no binary variable x, objective,
     status and root_pivots are linprog_batch(..., lb=, ub=, upper=)'s bit for bit.  Without lb and ub the call launches the
     kernels it always launched and returns the same bits.  Nothing of size B x n is materialised.  Out of scope: free
-    variables, per-MILP sets, and duals (a node's duals are not the model's).
+    variables in this function -- milp_batch_free is this call with linprog_batch's `free` -- per-MILP sets, and duals (a node's duals are
+    not the model's).
 
     See the module's docstring for the loading rule: torch first."""
+    return _milp_call(c, A_ub, b_ub, A_eq, b_eq, (), **dict(lb=lb, ub=ub, upper=upper, integers=integers, binaries=binaries, maximize=maximize, precision=precision, max_pivots=max_pivots,
+                           check_cycles=check_cycles, tolerance=tolerance, max_iterations=max_iterations, stats=stats))
+
+
+def milp_batch_free(c, A_ub=None, b_ub=None, A_eq=None, b_eq=None, *, lb=None, ub=None, upper=True, free=(), integers=(), binaries=(),
+                    maximize=False, precision=1e-8, max_pivots=8192, check_cycles=False, tolerance=0.0, max_iterations=32768, stats=None):
+    """milp_batch with free variables (a function of its own: milp_batch keeps the argument list it has, as linprog_objective
+    does beside linprog_objective_bounds).  Every argument but `free`, the result and the contract are milp_batch's; the
+    messages of what is refused say "milp_batch".
+
+    Free variables.  `free` is linprog_batch's: a HOST sequence of 0-based indices of the variables without a lower bound, or
+    True, shared by the batch and checked like `integers` (TypeError / ValueError before the library is touched).  (), False
+    and None mean none, and such a call is the call it was: the same kernels by name, the same bits.  The rules, all decided
+    on the host:
+      1. the split is linprog_batch's: x[j] = p[j] - q[j]; p keeps column 1 + j, the f = len(free) twins q are generated columns
+         behind the n originals in ascending j, each cell the IEEE negation of the cell written at column 1 + j of that row (one
+         strided read of the operand, not a second product), -1.0 in the bound row of a free variable `upper` lists, +0.0 in
+         every other generated row, the binary rows included.  Width 1 + n + f.
+      2. lb is not read at a free variable: l_eff[j] is +0.0 there, with no ceil, integer or not; the product with +0.0 is
+         still formed and added in shift_sum, which runs over the n original columns only.  Everywhere else l_eff is rule 1 of
+         the bounds.
+      3. a binary variable cannot be free: free=True means every variable that is not binary, and an explicit `free` that names
+         a binary variable raises ValueError, as `upper` does.
+      4. a free integer variable has two integer columns: the trees are handed the n_int columns 1 + j in ascending j, then the
+         twin columns of the free integer variables in ascending j (the whole list ascends), so that q is integral where p is.
+         n_int_eff = n_int + |free & integers|, and the largest possible node is 8 (1 + n + f) (height + 2 n_int_eff) bytes:
+         the 4 MiB refusal counts exactly that, and says so.
+      5. the rows are unchanged: linprog_batch's, then the k bound rows, then the binary rows.
+      6. x[j] of a free variable is read off the best tableau by linprog_batch's rule: "optimal" and "timedout" with a solution
+         give v(p) - v(q), each v the rule above on its own column (basic and above precision: rounded; else +0.0), one
+         subtraction, then + l_eff[j] where lb is given; "unbounded" gives +inf at the unbounded column, so -inf where that
+         column is a twin; any other status NaN.  objective = objective' + shift_sum(c, l_eff), one addition.
+    For finite data row i is solve() of the equivalent model in x', moved back: linprog_batch(free=)'s model -- one variable
+    q<j> per free variable behind all x<j>, listing the negated coefficient of every constraint x<j> lists, and -c[j] -- with
+    "integers" / "binaries" naming the variables, and "integers" naming the twins q<j> of the free integer variables too.  With
+    no integer and no binary variable x, objective, status and root_pivots are linprog_batch(..., lb=, ub=, upper=, free=)'s
+    bit for bit, and nodes = node_pivots = 0.  A call with free variables runs milp_dense_free_root_kernel and
+    milp_dense_free_solution_kernel, with or without lb / ub; an overflowed tree of such a call is answered by the lockstep
+    driver on the split tableau and moved back.  Nothing of size B x n or B x f is materialised.
+    Hold a free integer variable by whole numbers: every row sees p and q as p - q, so where an LP leaves such a variable at a
+    fraction v that the objective pushes against, the cut q >= ceil(-v) is answered by p rising with it, x stays at v, the next
+    cut is on p, and the chain ends only at max_iterations ("timedout") -- in the reference's search as in this one.
+    Out of scope: per-MILP sets, duals (a node's duals are not the model's), and inferring freeness from the data (an lb entry
+    of -inf at a variable `free` does not list is taken as it lies in memory).
+
+    See the module's docstring for the loading rule: torch first."""
+    return _milp_call(c, A_ub, b_ub, A_eq, b_eq, free, **dict(lb=lb, ub=ub, upper=upper, integers=integers, binaries=binaries, maximize=maximize, precision=precision, max_pivots=max_pivots,
+                           check_cycles=check_cycles, tolerance=tolerance, max_iterations=max_iterations, stats=stats))
+
+
+def _milp_call(c, A_ub, b_ub, A_eq, b_eq, free, *, lb, ub, upper, integers, binaries, maximize, precision, max_pivots, check_cycles, tolerance,
+               max_iterations, stats):
+    """milp_batch and milp_batch_free behind their argument lists."""
     from . import milp_dense
     sets = {}
 
     def size(n, m_ub, m_eq):
         ints, bins = sets["ints"], sets["bins"] = milp_dense.integer_sets(n, integers, binaries)
         idx = sets["upper"] = milp_dense.bound_rows(_upper_set(n, upper, ub is not None, "milp_batch"), bins, upper is True)
-        nbytes = milp_dense.largest_node_bytes(n, m_ub, m_eq, len(ints), len(bins), len(idx))
+        fidx = sets["free"] = milp_dense.free_set(_free_set(n, free, "milp_batch"), bins, free is True)
+        twins = len(set(fidx) & set(ints))
+        nbytes = milp_dense.largest_node_bytes(n, m_ub, m_eq, len(ints), len(bins), len(idx), len(fidx), twins)
+        if fidx and nbytes > _native.MILPDENSE_MAX_BYTES:
+            w, rows = n + 1 + len(fidx), 1 + m_ub + 2 * m_eq + len(idx) + len(bins)
+            raise ValueError("milp_batch: the largest possible node, %d x %d doubles (%d bytes: %d twin columns of free variables, %d "
+                             "rows and two cuts for each of %d integer columns -- %d integer variables and the twins of the %d free "
+                             "ones among them), is above the batch limit of %d bytes; solve() is the route for such models"
+                             % (nbytes // (8 * w), w, nbytes, len(fidx), rows, len(ints) + twins, len(ints), twins, _native.MILPDENSE_MAX_BYTES))
         if nbytes > _native.MILPDENSE_MAX_BYTES:
             raise ValueError("milp_batch: the largest possible node, %d x %d doubles (%d bytes: %d rows and two cuts for each of %d "
                              "integer variables), is above the batch limit of %d bytes; solve() is the route for such models"
@@ -560,11 +624,13 @@ def milp_batch(c, A_ub=None, b_ub=None, A_eq=None, b_eq=None, *, lb=None, ub=Non
 
     B, n, m_ub, m_eq, device, operands, given, batched, bounds = _call_operands("milp_batch", c, A_ub, b_ub, A_eq, b_eq, size,
                                                                                 vectors={"lb": lb, "ub": ub})
-    ints, bins, idx = sets["ints"], sets["bins"], sets["upper"]
+    ints, bins, idx, fidx = sets["ints"], sets["bins"], sets["upper"], sets["free"]
     more = {}
+    if fidx:
+        more["free"] = fidx
     if lb is not None or ub is not None:
         # (a bound tensor without an element -- n = 0 -- stays a descriptor, so that the call still is the bounded one)
-        more = dict(lb=None if lb is None else bounds["lb"] or (None, 0, 0, 0), ub=None if ub is None else bounds["ub"] or (None, 0, 0, 0),
+        more.update(lb=None if lb is None else bounds["lb"] or (None, 0, 0, 0), ub=None if ub is None else bounds["ub"] or (None, 0, 0, 0),
                     upper=idx)
     out = MilpBatchResult(torch.empty((B, n), dtype=torch.float64, device=device), torch.empty((B,), dtype=torch.float64, device=device),
                           torch.empty((B,), dtype=torch.int32, device=device), *(torch.empty((B,), dtype=torch.int64, device=device) for _ in range(3)))
@@ -588,5 +654,5 @@ def milp_batch(c, A_ub=None, b_ub=None, A_eq=None, b_eq=None, *, lb=None, ub=Non
             options = {"precision": float(precision), "maxPivots": float(max_pivots), "checkCycles": bool(check_cycles),
                        "tolerance": float(tolerance), "timeout": float("inf"), "maxIterations": float(max_iterations)}
             _solve_on_host(device, over, given, batched, B, ints, bins, bool(maximize), options, out, (lb, ub),
-                           tuple(t is not None and t.dim() == 2 for t in (lb, ub)), idx)
+                           tuple(t is not None and t.dim() == 2 for t in (lb, ub)), idx, fidx)
     return out
