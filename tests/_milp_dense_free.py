@@ -6,6 +6,8 @@ tests/_np_milp_dense_free.py: the oracle-driven search on the split tableau, mov
   table()         [FCall]: every call of the child "table", through _native.MilpDense with a trace
   child "table"   the table, then the plumbing through milp_batch_free and the equalities with the other calls
   child "mix"     mix_call() through milp_batch_free under the environment the test sets (YALPS_MILPDENSE_GRID / _ARENA / _ARENA_MAX)
+  child "hist"    hist_call() through milp_batch_free under YALPS_MILPDENSE_HIST=4: the rerun of a free root refills the split tableau
+                  from the operands, and the free epilogue reads what the last pass left
 """
 import math
 import sys
@@ -149,7 +151,7 @@ def names():
     out = ["n=%d" % n for n in LANES] + list(EDGES)
     for name in SHAPES:
         out += [name] + ([name + " check"] if name in CHECKED else [])
-    out += ["binary rows and twins", "free with a bound row, lb elsewhere", "lb only", "ub only", "no bounds", "equalities", "minimize",
+    out += ["check at 256 lanes", "binary rows and twins", "free with a bound row, lb elsewhere", "lb only", "ub only", "no bounds", "equalities", "minimize",
             "NaN in lb at free", "negative optimum by the twin", "tie between a p and a q", "unbounded through a twin", "infeasible row",
             "timedout with a solution"]
     return out
@@ -176,7 +178,8 @@ def table():
             assert (LB.size_class(c.w, c.h), LB.size_class(c.w, c.h_no_twins), LB.size_class(c.w, c.hmax)) == classes, (name, c.w, c.h, c.hmax)
             assert BS.aux_hbm(c.w, c.h) == (name == "aux form")
             T.append(c)
-    T += [call("binary rows and twins", 3, 6, 3, 1, ints=[0, 3], bins=[1, 4], free=[0, 2, 3], seed=4),
+    T += [call("check at 256 lanes", 3, 6, 3, 1, ints=[0, 3], bins=[1, 4], free=[0, 2, 3], seed=10, check=True),
+          call("binary rows and twins", 3, 6, 3, 1, ints=[0, 3], bins=[1, 4], free=[0, 2, 3], seed=4),
           call("free with a bound row, lb elsewhere", 3, 5, 3, 0, ints=[0, 3], free=[0, 1], upper=(0, 2), seed=2),
           call("lb only", 3, 5, 3, 1, ints=[0, 3], bins=[2], free=[0, 4], mode="lb", seed=1),
           call("ub only", 3, 5, 3, 1, ints=[0, 3], bins=[2], free=[3], mode="ub", seed=2),
@@ -213,6 +216,25 @@ def mix_call():
         guards[np.arange(len(free)), free] = -1.0
         lps.append((c, np.concatenate([A, guards]), np.concatenate([b, np.full(len(free), 1.0 if i == 6 else 2.0)]), None, None, lb, ub))
     return NF.FCall("mix", lps, free=free, integers=mix.integers, maximize=True, max_iterations=200.0)
+
+
+HIST = MDB.HIST
+
+
+def hist_call():
+    """MDB.hist_call's boxed MILPs (root LPs and nodes of more pivots than a history of HIST holds, checkCycles on) with every second
+    integer variable free, as in mix_call: its objective coefficient negated and a guard row -x[j] <= 2 under A_ub (whole: free_milp
+    says why), and a budget of 200 nodes."""
+    hist = MDB.hist_call()
+    free = hist.ints[::2]
+    lps = []
+    for lp, lb, ub in zip(hist.lps, hist.lbs, hist.ubs):
+        c, A, b = lp[0].copy(), lp[1], lp[2]
+        c[free] *= -1.0
+        guards = np.zeros((len(free), hist.n))
+        guards[np.arange(len(free)), free] = -1.0
+        lps.append((c, np.concatenate([A, guards]), np.concatenate([b, np.full(len(free), 2.0)]), None, None, lb, ub))
+    return NF.FCall("hist", lps, free=free, integers=hist.integers, maximize=True, check=True, max_iterations=200.0)
 
 
 def lp_call():
@@ -416,11 +438,11 @@ def child_table(path):
     np.savez(path, **out)
 
 
-def child_mix(path):
+def child_mix(path, call=None):
     torch = MD._torch_first()
     from yalps_amd import tensors
     stats = {}
-    out = MD.answer(public(torch, mix_call(), stats))
+    out = MD.answer(public(torch, call or mix_call(), stats))
     out.update(reruns=np.int64(stats["reruns"]), launches=np.int64(stats["launches"]), overflows=np.int64(stats["overflows"]),
                passes=np.int64(1 + max(k["pass"] for k in stats["kernels"])), grids=np.array([k["grid"] for k in stats["kernels"]], np.int64),
                kernels=np.array(" ".join(k["kernel"] for k in stats["kernels"])),
@@ -428,5 +450,11 @@ def child_mix(path):
     np.savez(path, **out)
 
 
+def child_hist(path):
+    import os
+    assert os.environ.get("YALPS_MILPDENSE_HIST") == str(HIST)
+    child_mix(path, hist_call())
+
+
 if __name__ == "__main__":
-    {"table": child_table, "mix": child_mix}[sys.argv[1]](sys.argv[2])
+    {"table": child_table, "mix": child_mix, "hist": child_hist}[sys.argv[1]](sys.argv[2])

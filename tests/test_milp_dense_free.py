@@ -85,9 +85,10 @@ def test_call_against_the_oracle_search(ran, refs, name):
 
 
 def test_the_table_names_every_form(ran):
-    """LDS 256, LDS 1024, HBM and the aux form, `check` on two of them."""
+    """All six compiled forms of the root kernel: LDS 256, LDS 1024 and HBM, each with and without `check`; and the aux form."""
     roots = {str(of(ran, name)["kernels"]).split()[0] for name in MF.names()}
-    assert {"milp_dense_free_root_kernel<%s>" % t for t in ("256,lds", "1024,lds", "1024,check,lds", "1024", "1024,check")} <= roots, roots
+    forms = ("256,lds", "256,check,lds", "1024,lds", "1024,check,lds", "1024", "1024,check")
+    assert {"milp_dense_free_root_kernel<%s>" % t for t in forms} == roots, roots
     assert int(of(ran, "aux form")["aux"][0]) == 1 and int(of(ran, "HBM")["aux"][0]) == 0
 
 
@@ -181,6 +182,23 @@ def test_refusals_name_the_entry_and_launch_nothing(ran, refs):
 
 
 # ---------------------------------------------------------------------------------------------- the test hooks
+
+def test_history_rerun_refills_the_split_tableau(tmp_path_factory, nat, oracle):
+    """Under YALPS_MILPDENSE_HIST=4 every root outgrows its checkCycles history and runs again on the split tableau, refilled from the
+    operands; so does every tree with a node of more pivots than that; the free epilogue runs after the last pass.  Bit for bit
+    against the oracle-driven search."""
+    got = run_child(tmp_path_factory, "hist", {"YALPS_MILPDENSE_HIST": str(MF.HIST)})
+    call = MF.hist_call()
+    rows = NF.expected(nat, oracle, call)
+    check_tensors(got, call, rows, "hist")
+    assert all(r["root_pivots"] > MF.HIST for r in rows) and any(r["nodes"] > 0 for r in rows)
+    assert any((r["x_split"][call.n:] > 0.0).any() and (r["x"] < 0.0).any() for r in rows)  # (a twin is basic: x of a free variable is negative)
+    long_trees = sum(any(node[4] > MF.HIST for node in r["trace"]) for r in rows)
+    assert int(got["reruns"]) >= len(call.lps) + long_trees > len(call.lps) and int(got["passes"]) >= 2 and int(got["overflows"]) == 0
+    kernels = str(got["kernels"]).split()
+    assert all("check" in k for k in kernels if k != EPILOGUE) and kernels[-1] == EPILOGUE and kernels.count(EPILOGUE) == 1
+    assert kernels[0] == root_kernel(call) == "milp_dense_free_root_kernel<256,check,lds>" and kernels.count(kernels[0]) >= 2
+
 
 @pytest.fixture(scope="module")
 def mix_rows(nat, oracle):

@@ -185,7 +185,8 @@ def linprog_batch(c, A_ub=None, b_ub=None, A_eq=None, b_eq=None, *, lb=None, ub=
     The contract.  For finite data, row i is what solve() returns for the equivalent model -- constraints u0.. {"max":
     b_ub[i, r]}, then e0.. {"equal": b_eq[i, k]}, every variable listing every coefficient, zeros included -- with
     includeZeroVariables read off the dense x: "optimal" gives the variables' values (those not above precision are +0.0)
-    and objective = solve()'s result; "unbounded" gives +0.0 but +inf at the unbounded variable and objective = +-inf;
+    and objective = solve()'s result; "unbounded" gives +0.0 but +inf at the unbounded variable and objective = +-inf
+    (the variable whose own column the simplex found unbounded: where that column is a row's slack, no entry of x is infinite);
     "infeasible" and "cycled" give NaN everywhere.  For any data, NaN and infinities included, it is what the reference's
     `simplex` and `solution` give on the tableau as built: values are taken as they lie in memory.
 
