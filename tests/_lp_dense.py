@@ -33,6 +33,7 @@ NONFINITE_SHAPE = (60, 64)    # (M, N) of the non-finite families
 AUX_SHAPE = (8162, 30)        # (m_ub, n): pcols + h = 30 + 8163 = 8193, colbuf / prow behind the tableau in HBM
 QUEUE_LPS = 2100              # more than class 0's grid of 8 x 256 workgroups
 HIST = 4                      # YALPS_LPDENSE_HIST of the child "hist"
+GRID_HOOKS = ("YALPS_LPDENSE_CUS", "YALPS_LPDENSE_PER_CU")  # (test hooks that shrink the grid: kept out of the children's environments)
 
 
 class Call:

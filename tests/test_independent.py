@@ -19,7 +19,8 @@ from tests import _lp_batch as LB
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOOKS = ("YALPS_MILPDENSE_ARENA", "YALPS_MILPDENSE_ARENA_MAX", "YALPS_MILPDENSE_HIST", "YALPS_MILPDENSE_GRID", "YALPS_LPDENSE_HIST")
+HOOKS = ("YALPS_MILPDENSE_ARENA", "YALPS_MILPDENSE_ARENA_MAX", "YALPS_MILPDENSE_HIST", "YALPS_MILPDENSE_GRID", "YALPS_LPDENSE_HIST",
+         "YALPS_MILPDENSE_CUS", "YALPS_MILPDENSE_PER_CU", "YALPS_LPDENSE_CUS", "YALPS_LPDENSE_PER_CU")
 LP_GROUPS = [g["name"] for g in I.lp_groups()] + [g["name"] for g in I.ending_groups("lp")]
 MILP_GROUPS = [g["name"] for g in I.milp_groups()] + [g["name"] for g in I.ending_groups("milp")]
 LP_KERNEL = {"plain": "lp_dense_kernel", "bounded": "lp_dense_bounds_kernel", "free": "lp_dense_free_kernel"}

@@ -16,7 +16,8 @@ from tests import _np_milp_dense as NM
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOOKS = ("YALPS_MILPDENSE_ARENA", "YALPS_MILPDENSE_ARENA_MAX", "YALPS_MILPDENSE_HIST", "YALPS_MILPDENSE_GRID")
+HOOKS = ("YALPS_MILPDENSE_ARENA", "YALPS_MILPDENSE_ARENA_MAX", "YALPS_MILPDENSE_HIST", "YALPS_MILPDENSE_GRID", "YALPS_MILPDENSE_CUS",
+         "YALPS_MILPDENSE_PER_CU", "YALPS_LPDENSE_CUS", "YALPS_LPDENSE_PER_CU")
 
 
 def run_child(tmp_path_factory, which, env=None, tag=None):

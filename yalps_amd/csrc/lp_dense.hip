@@ -159,9 +159,17 @@ DenseOperand operand(const yalps_lpdense_operand *o, bool vector) {
 int create_impl(int32_t device, void *hip_stream, yalps_lpdense **out) {
     yalps_lpdense *b = new yalps_lpdense();
     *out = b;
+    // (test hooks: a grid smaller than the card, one per_cu for every class, so that a workgroup takes several LPs of any class;
+    // read and refused in front of the device, 0 or unset: the card's own table)
+    const int per_cu = env_int("YALPS_LPDENSE_PER_CU", 0), cus = env_int("YALPS_LPDENSE_CUS", 0);
+    if (per_cu < 0 || per_cu > 8) return fail(YALPS_E_ARG, "YALPS_LPDENSE_PER_CU: " + std::to_string(per_cu) + " is outside 0..8 (0: unset)");
+    if (cus < 0) return fail(YALPS_E_ARG, "YALPS_LPDENSE_CUS: " + std::to_string(cus) + " is negative");
     if (int rc = open_device(*b, device, hip_stream)) return rc;
     if (hip_stream == static_cast<void *>(hipStreamLegacy)) b->stream = nullptr; // the device's default stream, by its own name
     b->q.hist_first = std::max(1, env_int("YALPS_LPDENSE_HIST", (int)HIST_FIRST)); // (test hook: forces the rerun)
+    if (cus) b->num_cus = std::min(cus, b->num_cus);
+    if (per_cu)
+        for (int k = 0; k < NCLASS; k++) b->per_cu[k] = std::min(per_cu, kClasses[k].per_cu);
     if (int rc = raise_lds_limit(kDenseKernels)) return rc;
     if (int rc = raise_lds_limit(bounds_kernels())) return rc;
     return raise_lds_limit(free_kernels());

@@ -91,6 +91,7 @@ const FreeKernels &free_kernels() {
 
 struct yalps_milpdense : QueueDevice {
     QueueBufs q;                  // the root pass
+    QueueDevice root;             // the root pass's class table: the handle's own, but for the test hooks _CUS / _PER_CU
     DevBuf call, rdesc;           // the call's description with the binary list behind it; one LpDesc per root
     TreePass t;
     // the last solve
@@ -235,8 +236,17 @@ MilpDenseOperand operand(const yalps_milpdense_operand *o, bool vector) {
 int create_impl(int32_t device, void *hip_stream, yalps_milpdense **out) {
     yalps_milpdense *b = new yalps_milpdense();
     *out = b;
+    // (test hooks: the ROOT pass on a grid smaller than the card, one per_cu for every class, so that a workgroup takes several
+    // roots of any class; read and refused in front of the device, 0 or unset: the card's own table.  The trees keep _GRID.)
+    const int per_cu = env_int("YALPS_MILPDENSE_PER_CU", 0), cus = env_int("YALPS_MILPDENSE_CUS", 0);
+    if (per_cu < 0 || per_cu > 8) return fail(YALPS_E_ARG, "YALPS_MILPDENSE_PER_CU: " + std::to_string(per_cu) + " is outside 0..8 (0: unset)");
+    if (cus < 0) return fail(YALPS_E_ARG, "YALPS_MILPDENSE_CUS: " + std::to_string(cus) + " is negative");
     if (int rc = open_device(*b, device, hip_stream)) return rc;
     if (hip_stream == static_cast<void *>(hipStreamLegacy)) b->stream = nullptr; // the device's default stream, by its own name
+    b->root = *b; // (the same stream and events: one pass runs at a time)
+    if (cus) b->root.num_cus = std::min(cus, b->num_cus);
+    if (per_cu)
+        for (int k = 0; k < NCLASS; k++) b->root.per_cu[k] = std::min(per_cu, kClasses[k].per_cu);
     b->q.hist_first = b->t.q.hist_first = std::max(1, env_int("YALPS_MILPDENSE_HIST", (int)HIST_FIRST)); // (test hooks: they force the reruns)
     b->t.arena_first = std::max(2, env_int("YALPS_MILPDENSE_ARENA", ARENA_FIRST));
     b->t.arena_max = std::max(2, env_int("YALPS_MILPDENSE_ARENA_MAX", ARENA_MAX));
@@ -362,7 +372,7 @@ int solve_impl(yalps_milpdense *b, const char *entry, int32_t count, int32_t n, 
 
     QueueRun run;
     const int rc = run_queue(
-        *b, b->q, split ? free_kernels().roots : bounds ? bounds_kernels().roots : kRootKernels, QueueText{"yalps_milpdense", true, entry, "MILP"}, cnt,
+        b->root, b->q, split ? free_kernels().roots : bounds ? bounds_kernels().roots : kRootKernels, QueueText{"yalps_milpdense", true, entry, "MILP"}, cnt,
         [&](int32_t, int *iw, int *ih) { return *iw = w, *ih = h, checkCycles != 0; },
         [&](MilpDenseLaunch &a) { a.call = b->call.as<const MilpDenseCall>(); }, [] { return 0; },
         [&](const Launch &L, const std::string &kernel, int pass, int launch, long long hist_cap) {

@@ -2564,7 +2564,9 @@ static int32_t batch_create_impl(yalps_ctx *ctx, int32_t width, int32_t root_hei
     if (b->shmem > 150 * 1024) return fail(YALPS_E_ARG, "yalps_batch_create: node tableau too large for the batched path");
     const size_t nm = (size_t)max_nodes;
     HIP_TRY(hipMalloc(&b->root_mat, sizeof(double) * (size_t)d.h0 * d.pitch));
-    HIP_TRY(hipMemset(b->root_mat, 0, sizeof(double) * (size_t)d.h0 * d.pitch));
+    // (the padding columns.  On the context's stream, in front of set_root's copies: the stream is non-blocking, so a hipMemset --
+    // null stream, not waited for on device memory -- was ordered with nothing and now and then landed on the root just uploaded)
+    HIP_TRY(hipMemsetAsync(b->root_mat, 0, sizeof(double) * (size_t)d.h0 * d.pitch, ctx->stream));
     HIP_TRY(hipMalloc(&b->root_rhs, sizeof(double) * (size_t)d.h0));
     HIP_TRY(hipMalloc(&b->root_pos, sizeof(int32_t) * (size_t)(width + d.h0)));
     HIP_TRY(hipMalloc(&b->root_var, sizeof(int32_t) * (size_t)(width + d.h0)));
