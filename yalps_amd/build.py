@@ -32,7 +32,7 @@ HIP_SRC = os.path.join(CSRC, "yalps_hip.hip")  # host side + C ABI + the launch-
 # the persistent kernels' instantiations, one translation unit per group: compiled side by side (the device compile of
 # ~40 register-heavy kernels in one unit took 2.5 minutes)
 HIP_UNITS = [HIP_SRC] + [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.startswith("persistent_") and f.endswith(".hip")]
-HIP_DEPS = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith((".cuh", ".inc", ".h")) and not f.startswith(("lp_batch", "lp_dense", "lp_variants", "lp_sens", "lp_warm", "milp_node", "milp_tree", "milp_dense", "wg_queue"))]
+HIP_DEPS = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith((".cuh", ".inc", ".h")) and not f.startswith(("lp_batch", "lp_dense", "lp_variants", "lp_sens", "lp_warm", "milp_node", "milp_tree", "milp_dense", "wg_queue", "dense_"))]
 # the batch library: one translation unit of its own around the shared workgroup loop, never linked into libyalps_hip.so
 LIB_LPBATCH = os.path.join(HERE, "libyalps_lpbatch.so")
 LPBATCH_SRC = os.path.join(CSRC, "lp_batch.hip")
@@ -67,7 +67,8 @@ MILPTREE_HEADER = os.path.join(ROOT, "include", "yalps_milptree.h")
 # the dense library: operands and answers in device memory, one translation unit around the same workgroup loop
 LIB_LPDENSE = os.path.join(HERE, "libyalps_lpdense.so")
 LPDENSE_SRC = os.path.join(CSRC, "lp_dense.hip")
-LPDENSE_DEPS = [os.path.join(CSRC, "lp_dense_kernel.cuh")] + QUEUE_DEPS
+DENSE_DEPS = [os.path.join(CSRC, f) for f in ("dense_tableau.cuh", "dense_host.inc")] + QUEUE_DEPS  # the tableau's rules and the host checks of both dense libraries
+LPDENSE_DEPS = [os.path.join(CSRC, "lp_dense_kernel.cuh")] + DENSE_DEPS
 # its kernels with bounds, a code object of their own that libyalps_lpdense.so links: the boundless library's holds the six forms it always held
 LIB_LPDENSE_BOUNDS = os.path.join(HERE, "libyalps_lpdense_bounds.so")
 LPDENSE_BOUNDS_SRC = os.path.join(CSRC, "lp_dense_bounds.hip")
@@ -79,12 +80,12 @@ LPDENSE_FREE_SRC = os.path.join(CSRC, "lp_dense_free.hip")
 LIB_MILPDENSE = os.path.join(HERE, "libyalps_milpdense.so")
 MILPDENSE_SRC = os.path.join(CSRC, "milp_dense.hip")
 MILPDENSE_DEPS = [os.path.join(CSRC, f) for f in ("milp_dense_kernel.cuh", "milp_tree_kernel.cuh", "milp_tree_rules.cuh", "milp_tree_host.inc",
-                                                  "lp_batch_kernel.cuh", "milp_dense_bounds_kernel.cuh", "milp_dense_free_kernel.cuh")] + QUEUE_DEPS  # (the last two: the structs of a call with bounds, with free variables)
+                                                  "lp_batch_kernel.cuh", "milp_dense_bounds_kernel.cuh", "milp_dense_free_kernel.cuh")] + DENSE_DEPS  # (the last two: the sibling kernels' types)
 MILPDENSE_HEADER = os.path.join(ROOT, "include", "yalps_milpdense.h")
 # its root and solution kernels with bounds, a code object of their own that libyalps_milpdense.so links: the boundless library's holds the kernels it always held
 LIB_MILPDENSE_BOUNDS = os.path.join(HERE, "libyalps_milpdense_bounds.so")
 MILPDENSE_BOUNDS_SRC = os.path.join(CSRC, "milp_dense_bounds.hip")
-MILPDENSE_BOUNDS_DEPS = [os.path.join(CSRC, f) for f in ("milp_dense_bounds_kernel.cuh", "milp_dense_kernel.cuh", "milp_tree_rules.cuh")] + QUEUE_DEPS
+MILPDENSE_BOUNDS_DEPS = [os.path.join(CSRC, f) for f in ("milp_dense_bounds_kernel.cuh", "milp_dense_kernel.cuh", "milp_tree_rules.cuh")] + DENSE_DEPS
 # and with free variables, likewise a code object of their own that libyalps_milpdense.so links
 LIB_MILPDENSE_FREE = os.path.join(HERE, "libyalps_milpdense_free.so")
 MILPDENSE_FREE_SRC = os.path.join(CSRC, "milp_dense_free.hip")

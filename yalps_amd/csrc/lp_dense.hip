@@ -30,9 +30,14 @@ namespace {
 #include "wg_simplex.cuh"
 #include "lp_dense_kernel.cuh"
 #include "wg_queue_host.inc"
+#include "dense_host.inc"
 
 static_assert(YALPS_LPDENSE_MAX_BYTES == QUEUE_MAX_BYTES, "include/yalps_lpdense.h");
 const KernelTable<DenseLaunch> kDenseKernels = QUEUE_KERNEL_TABLE(lp_dense_kernel);
+struct X { // (dense_host.inc)
+    static constexpr const char *name = "yalps_lpdense";
+    using Operand = yalps_lpdense_operand;
+};
 } // namespace
 
 extern "C" void yalps_lpdense_bounds_forms(void *out[6]); // lp_dense_bounds.hip
@@ -41,27 +46,12 @@ extern "C" void yalps_lpdense_free_forms(void *out[6]);   // lp_dense_free.hip
 namespace {
 // the same table over libyalps_lpdense_bounds.so's kernels
 const KernelTable<DenseLaunch> &bounds_kernels() {
-    static const KernelTable<DenseLaunch> table = [] {
-        KernelTable<DenseLaunch> t = kDenseKernels;
-        t.name = "lp_dense_bounds_kernel";
-        void *fn[6];
-        yalps_lpdense_bounds_forms(fn);
-        for (int k = 0; k < 6; k++) t.forms[k].fn = reinterpret_cast<void (*)(DenseLaunch)>(fn[k]);
-        return t;
-    }();
+    static const KernelTable<DenseLaunch> table = adopt_forms(kDenseKernels, "lp_dense_bounds_kernel", yalps_lpdense_bounds_forms);
     return table;
 }
-
 // and over libyalps_lpdense_free.so's
 const KernelTable<DenseLaunch> &free_kernels() {
-    static const KernelTable<DenseLaunch> table = [] {
-        KernelTable<DenseLaunch> t = kDenseKernels;
-        t.name = "lp_dense_free_kernel";
-        void *fn[6];
-        yalps_lpdense_free_forms(fn);
-        for (int k = 0; k < 6; k++) t.forms[k].fn = reinterpret_cast<void (*)(DenseLaunch)>(fn[k]);
-        return t;
-    }();
+    static const KernelTable<DenseLaunch> table = adopt_forms(kDenseKernels, "lp_dense_free_kernel", yalps_lpdense_free_forms);
     return table;
 }
 } // namespace
@@ -77,15 +67,6 @@ struct yalps_lpdense : QueueDevice {
 };
 
 namespace {
-// an operand of `rows` x `cols` elements per LP (a vector: cols = 1, the col stride ignored)
-int check_operand(const char *name, const yalps_lpdense_operand *o, int32_t count, int64_t rows, int64_t cols) {
-    const std::string who = std::string("yalps_lpdense: ") + name;
-    if (!o) return fail(YALPS_E_ARG, who + ": the operand descriptor is NULL");
-    if (o->batch < 0 || o->row < 0 || o->col < 0) return fail(YALPS_E_ARG, who + ": negative stride");
-    if (count > 0 && rows > 0 && cols > 0 && !o->ptr) return fail(YALPS_E_ARG, who + " is NULL");
-    return 0;
-}
-
 int validate(int32_t count, int32_t n, int32_t m_ub, int32_t m_eq, const yalps_lpdense_operand *c, const yalps_lpdense_operand *A_ub,
              const yalps_lpdense_operand *b_ub, const yalps_lpdense_operand *A_eq, const yalps_lpdense_operand *b_eq, int32_t n_upper = 0,
              int32_t n_free = 0) {
@@ -97,12 +78,7 @@ int validate(int32_t count, int32_t n, int32_t m_ub, int32_t m_eq, const yalps_l
     if (w > INT32_MAX || h > INT32_MAX || 8 * w * h > YALPS_LPDENSE_MAX_BYTES)
         return fail(YALPS_E_ARG, "yalps_lpdense: tableau of " + std::to_string(h) + " x " + std::to_string(w) + " doubles is above the limit of " +
                                      std::to_string((long long)YALPS_LPDENSE_MAX_BYTES) + " bytes");
-    if (int rc = check_operand("c", c, count, n, 1)) return rc;
-    if (int rc = check_operand("A_ub", A_ub, count, m_ub, n)) return rc;
-    if (int rc = check_operand("b_ub", b_ub, count, m_ub, 1)) return rc;
-    if (int rc = check_operand("A_eq", A_eq, count, m_eq, n)) return rc;
-    if (int rc = check_operand("b_eq", b_eq, count, m_eq, 1)) return rc;
-    return 0;
+    return check_operands<X>(count, n, m_ub, m_eq, c, A_ub, b_ub, A_eq, b_eq);
 }
 
 // the bounds of a call: lb / ub may be NULL descriptors (absent); upper_idx is host memory, ascending, inside 0 .. n-1
@@ -111,49 +87,10 @@ int validate_bounds(int32_t count, int32_t n, int32_t m_ub, int32_t m_eq, const 
                     const yalps_lpdense_operand *lb, const yalps_lpdense_operand *ub, int32_t n_upper, const int32_t *upper_idx,
                     int32_t n_free = 0, const int32_t *free_idx = nullptr) {
     if (int rc = validate(count, n, m_ub, m_eq, c, A_ub, b_ub, A_eq, b_eq, n_upper, n_free)) return rc;
-    if (lb)
-        if (int rc = check_operand("lb", lb, count, n, 1)) return rc;
-    if (ub)
-        if (int rc = check_operand("ub", ub, count, n_upper, 1)) return rc;
-    if (n_upper > 0 && !ub) return fail(YALPS_E_ARG, "yalps_lpdense: n_upper > 0 without ub");
-    if (n_upper > 0 && !upper_idx) return fail(YALPS_E_ARG, "yalps_lpdense: upper_idx is NULL");
-    for (int32_t t = 0; t < n_upper; t++) {
-        if (upper_idx[t] < 0 || upper_idx[t] >= n)
-            return fail(YALPS_E_ARG, "yalps_lpdense: upper_idx[" + std::to_string(t) + "] = " + std::to_string(upper_idx[t]) + " is outside 0 .. n-1");
-        if (t && upper_idx[t] <= upper_idx[t - 1])
-            return fail(YALPS_E_ARG, "yalps_lpdense: upper_idx is not ascending at " + std::to_string(t));
-    }
+    const auto nothing = [](int32_t) { return 0; };
+    if (int rc = check_bounds<X>(count, n, lb, ub, n_upper, upper_idx, nothing)) return rc;
     // the free variables: host memory, ascending, inside 0 .. n-1 (the width that counts their twins is checked above)
-    if (n_free > 0 && !free_idx) return fail(YALPS_E_ARG, "yalps_lpdense: free_idx is NULL");
-    for (int32_t t = 0; t < n_free; t++) {
-        if (free_idx[t] < 0 || free_idx[t] >= n)
-            return fail(YALPS_E_ARG, "yalps_lpdense: free_idx[" + std::to_string(t) + "] = " + std::to_string(free_idx[t]) + " is outside 0 .. n-1");
-        if (t && free_idx[t] <= free_idx[t - 1])
-            return fail(YALPS_E_ARG, "yalps_lpdense: free_idx is not ascending at " + std::to_string(t));
-    }
-    return 0;
-}
-
-// A pointer the kernel is to dereference: device (or managed) memory of the handle's device, known to THIS runtime.
-int check_pointer(const yalps_lpdense *b, const char *entry, const char *name, const void *p) {
-    if (!p) return 0;
-    const std::string who = std::string(entry) + ": " + name;
-    hipPointerAttribute_t attr;
-    std::memset(&attr, 0, sizeof attr);
-    if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
-        (void)hipGetLastError(); // (the lookup's failure is this answer, not the next call's)
-        return fail(YALPS_E_ARG, who + " is a pointer this HIP runtime does not know (host memory, or memory of another HIP runtime "
-                                       "in this process: load the framework that owns it before this library)");
-    }
-    if (attr.type != hipMemoryTypeDevice && attr.type != hipMemoryTypeManaged)
-        return fail(YALPS_E_ARG, who + " is host memory: operands and outputs are device pointers");
-    if (attr.type == hipMemoryTypeDevice && attr.device != b->device)
-        return fail(YALPS_E_ARG, who + " is memory of device " + std::to_string(attr.device) + ", the handle is on device " + std::to_string(b->device));
-    return 0;
-}
-
-DenseOperand operand(const yalps_lpdense_operand *o, bool vector) {
-    return DenseOperand{o->ptr, (long long)o->batch, (long long)o->row, vector ? 0ll : (long long)o->col};
+    return check_index_list<X>("free_idx", n_free, free_idx, n, nothing);
 }
 
 int create_impl(int32_t device, void *hip_stream, yalps_lpdense **out) {
@@ -210,7 +147,7 @@ int solve_impl(yalps_lpdense *b, const char *entry, int32_t count, int32_t n, in
                     {"ub", ub && n_upper ? ub->ptr : nullptr},
                     {"upper_out", n_upper ? upper_out : nullptr}};
     for (const auto &a : pointers)
-        if (int rc = check_pointer(b, entry, a.name, a.p)) return rc;
+        if (int rc = check_pointer(b->device, entry, a.name, a.p)) return rc;
 
     hipStream_t s = b->stream;
     const int32_t w = n + 1 + n_free, h = 1 + m_ub + 2 * m_eq + n_upper;

@@ -1,4 +1,4 @@
-// lp_dense_bounds.hip -- libyalps_lpdense_bounds.so: the six lp_dense_bounds_kernel instantiations (lp_dense_kernel.cuh, DenseJob<true>)
+// lp_dense_bounds.hip -- libyalps_lpdense_bounds.so: the six lp_dense_bounds_kernel instantiations (lp_dense_kernel.cuh, the bounded traits)
 // A code object of its own beside libyalps_lpdense.so, which links it: the boundless kernels' code object holds the six forms it
 // held before bounds existed, and nothing else.  No host code but the table below; the C ABI, the pass and the handle are
 // lp_dense.hip's, which launches these kernels through the pointers it gets here.

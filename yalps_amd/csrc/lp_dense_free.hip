@@ -1,4 +1,4 @@
-// lp_dense_free.hip -- libyalps_lpdense_free.so: the six lp_dense_free_kernel instantiations (lp_dense_kernel.cuh, DenseFreeJob)
+// lp_dense_free.hip -- libyalps_lpdense_free.so: the six lp_dense_free_kernel instantiations (lp_dense_kernel.cuh, the free traits)
 // A code object of its own beside libyalps_lpdense.so and libyalps_lpdense_bounds.so: theirs hold the forms they held before free
 // variables existed, and nothing else.  No host code but the table below; the C ABI, the pass and the handle are lp_dense.hip's,
 // which launches these kernels through the pointers it gets here.

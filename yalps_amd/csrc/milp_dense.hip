@@ -37,54 +37,43 @@ namespace {
 #include "lp_batch_kernel.cuh" // (LpDesc: what milp_tree_kernel reads of a root; lp_batch_kernel itself is not instantiated here)
 #include "milp_tree_kernel.cuh"
 #include "milp_dense_kernel.cuh"
-#include "milp_dense_bounds_kernel.cuh" // (the two structs of a bounded call; its kernels are not instantiated here)
-#include "milp_dense_free_kernel.cuh"   // (the two structs of a call with free variables, likewise)
+#include "milp_dense_bounds_kernel.cuh" // (the siblings' kernels, for their types; they are not instantiated here)
+#include "milp_dense_free_kernel.cuh"
 #include "wg_queue_host.inc"
 #include "milp_tree_host.inc"
+#include "dense_host.inc"
 
 static_assert(YALPS_MILPDENSE_MAX_BYTES == QUEUE_MAX_BYTES, "include/yalps_milpdense.h");
 static_assert(TREE_TIMEDOUT == YALPS_MILPDENSE_TIMEDOUT && TREE_OVERFLOW == YALPS_MILPDENSE_OVERFLOW, "include/yalps_milpdense.h");
 const KernelTable<MilpDenseLaunch> kRootKernels = QUEUE_KERNEL_TABLE(milp_dense_root_kernel);
 constexpr int SOLUTION_LANES = 256;
+struct X { // (dense_host.inc)
+    static constexpr const char *name = "yalps_milpdense";
+    using Operand = yalps_milpdense_operand;
+};
 } // namespace
 
 extern "C" void yalps_milpdense_bounds_forms(void *out[7]); // milp_dense_bounds.hip
 extern "C" void yalps_milpdense_free_forms(void *out[7]);   // milp_dense_free.hip
 
 namespace {
-// libyalps_milpdense_bounds.so's kernels: the same table over its root forms, and its epilogue
-struct BoundsKernels {
+// a sibling library's kernels: the same table over its root forms, and its epilogue
+struct SiblingKernels {
     KernelTable<MilpDenseLaunch> roots;
-    void (*solution)(MilpBoundsSolutionArgs);
+    void (*solution)(MilpSolutionArgs);
 };
-const BoundsKernels &bounds_kernels() {
-    static const BoundsKernels kernels = [] {
-        BoundsKernels k{kRootKernels, nullptr};
-        k.roots.name = "milp_dense_bounds_root_kernel";
-        void *fn[7];
-        yalps_milpdense_bounds_forms(fn);
-        for (int f = 0; f < 6; f++) k.roots.forms[f].fn = reinterpret_cast<void (*)(MilpDenseLaunch)>(fn[f]);
-        k.solution = reinterpret_cast<void (*)(MilpBoundsSolutionArgs)>(fn[6]);
-        return k;
-    }();
+SiblingKernels sibling(const char *name, void (*forms)(void **)) {
+    void *solution = nullptr;
+    SiblingKernels k{adopt_forms(kRootKernels, name, forms, &solution), nullptr};
+    k.solution = reinterpret_cast<void (*)(MilpSolutionArgs)>(solution);
+    return k;
+}
+const SiblingKernels &bounds_kernels() { // libyalps_milpdense_bounds.so's
+    static const SiblingKernels kernels = sibling("milp_dense_bounds_root_kernel", yalps_milpdense_bounds_forms);
     return kernels;
 }
-
-// libyalps_milpdense_free.so's kernels, likewise
-struct FreeKernels {
-    KernelTable<MilpDenseLaunch> roots;
-    void (*solution)(MilpFreeSolutionArgs);
-};
-const FreeKernels &free_kernels() {
-    static const FreeKernels kernels = [] {
-        FreeKernels k{kRootKernels, nullptr};
-        k.roots.name = "milp_dense_free_root_kernel";
-        void *fn[7];
-        yalps_milpdense_free_forms(fn);
-        for (int f = 0; f < 6; f++) k.roots.forms[f].fn = reinterpret_cast<void (*)(MilpDenseLaunch)>(fn[f]);
-        k.solution = reinterpret_cast<void (*)(MilpFreeSolutionArgs)>(fn[6]);
-        return k;
-    }();
+const SiblingKernels &free_kernels() { // libyalps_milpdense_free.so's
+    static const SiblingKernels kernels = sibling("milp_dense_free_root_kernel", yalps_milpdense_free_forms);
     return kernels;
 }
 } // namespace
@@ -103,15 +92,6 @@ struct yalps_milpdense : QueueDevice {
 };
 
 namespace {
-// an operand of `rows` x `cols` elements per MILP (a vector: cols = 1, the col stride ignored)
-int check_operand(const char *name, const yalps_milpdense_operand *o, int32_t count, int64_t rows, int64_t cols) {
-    const std::string who = std::string("yalps_milpdense: ") + name;
-    if (!o) return fail(YALPS_E_ARG, who + ": the operand descriptor is NULL");
-    if (o->batch < 0 || o->row < 0 || o->col < 0) return fail(YALPS_E_ARG, who + ": negative stride");
-    if (count > 0 && rows > 0 && cols > 0 && !o->ptr) return fail(YALPS_E_ARG, who + " is NULL");
-    return 0;
-}
-
 // a HOST list of 0-based variable indices: strictly ascending, within 0 .. n - 1
 int check_list(const char *name, int32_t len, const int32_t *list, int32_t n) {
     const std::string who = std::string("yalps_milpdense: ") + name;
@@ -149,12 +129,7 @@ int validate(int32_t count, int32_t n, int32_t m_ub, int32_t m_eq, const yalps_m
         return fail(YALPS_E_ARG, "yalps_milpdense: largest node of " + std::to_string(hmax) + " x " + std::to_string(w) + " doubles (" +
                                      std::to_string(h) + " rows and two cuts for each of " + std::to_string(nints) +
                                      " integer variables) is above the limit of " + std::to_string((long long)YALPS_MILPDENSE_MAX_BYTES) + " bytes");
-    if (int rc = check_operand("c", c, count, n, 1)) return rc;
-    if (int rc = check_operand("A_ub", A_ub, count, m_ub, n)) return rc;
-    if (int rc = check_operand("b_ub", b_ub, count, m_ub, 1)) return rc;
-    if (int rc = check_operand("A_eq", A_eq, count, m_eq, n)) return rc;
-    if (int rc = check_operand("b_eq", b_eq, count, m_eq, 1)) return rc;
-    return 0;
+    return check_operands<X>(count, n, m_ub, m_eq, c, A_ub, b_ub, A_eq, b_eq);
 }
 
 // the bounds of a call: lb / ub may be NULL descriptors (absent); upper_idx is host memory, ascending, inside 0 .. n-1, and names
@@ -164,23 +139,14 @@ int validate_bounds(int32_t count, int32_t n, int32_t m_ub, int32_t m_eq, const 
                     const yalps_milpdense_operand *lb, const yalps_milpdense_operand *ub, int32_t n_upper, const int32_t *upper_idx,
                     int32_t nints, const int32_t *ints, int32_t nbin, const int32_t *bin, int32_t n_free = 0, int32_t int_twins = 0) {
     if (int rc = validate(count, n, m_ub, m_eq, c, A_ub, b_ub, A_eq, b_eq, nints, ints, nbin, bin, n_upper, n_free, int_twins)) return rc;
-    if (lb)
-        if (int rc = check_operand("lb", lb, count, n, 1)) return rc;
-    if (ub)
-        if (int rc = check_operand("ub", ub, count, n_upper, 1)) return rc;
-    if (n_upper > 0 && !ub) return fail(YALPS_E_ARG, "yalps_milpdense: n_upper > 0 without ub");
-    if (n_upper > 0 && !upper_idx) return fail(YALPS_E_ARG, "yalps_milpdense: upper_idx is NULL");
-    for (int32_t t = 0, at = 0; t < n_upper; t++) {
-        if (upper_idx[t] < 0 || upper_idx[t] >= n)
-            return fail(YALPS_E_ARG, "yalps_milpdense: upper_idx[" + std::to_string(t) + "] = " + std::to_string(upper_idx[t]) + " is outside 0 .. n-1");
-        if (t && upper_idx[t] <= upper_idx[t - 1])
-            return fail(YALPS_E_ARG, "yalps_milpdense: upper_idx is not ascending at " + std::to_string(t));
-        while (at < nbin && bin[at] < upper_idx[t]) at++; // (both ascending: one walk)
+    int32_t at = 0; // (both ascending: one walk)
+    return check_bounds<X>(count, n, lb, ub, n_upper, upper_idx, [&](int32_t t) {
+        while (at < nbin && bin[at] < upper_idx[t]) at++;
         if (at < nbin && bin[at] == upper_idx[t])
             return fail(YALPS_E_ARG, "yalps_milpdense: upper_idx[" + std::to_string(t) + "]: variable " + std::to_string(upper_idx[t]) +
                                          " is binary (a binary variable has no bound row)");
-    }
-    return 0;
+        return 0;
+    });
 }
 
 // the free variables of a call: free_idx is host memory, strictly ascending, inside 0 .. n-1, and names no binary variable; the
@@ -208,29 +174,6 @@ int validate_free(int32_t count, int32_t n, int32_t m_ub, int32_t m_eq, const ya
     }
     if (int_twins_out) *int_twins_out = int_twins;
     return validate_bounds(count, n, m_ub, m_eq, c, A_ub, b_ub, A_eq, b_eq, lb, ub, n_upper, upper_idx, nints, ints, nbin, bin, n_free, int_twins);
-}
-
-// A pointer a kernel is to dereference: device (or managed) memory of the handle's device, known to THIS runtime
-// (as lp_dense.hip::check_pointer).
-int check_pointer(const yalps_milpdense *b, const char *entry, const char *name, const void *p) {
-    if (!p) return 0;
-    const std::string who = std::string(entry) + ": " + name;
-    hipPointerAttribute_t attr;
-    std::memset(&attr, 0, sizeof attr);
-    if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
-        (void)hipGetLastError(); // (the lookup's failure is this answer, not the next call's)
-        return fail(YALPS_E_ARG, who + " is a pointer this HIP runtime does not know (host memory, or memory of another HIP runtime "
-                                       "in this process: load the framework that owns it before this library)");
-    }
-    if (attr.type != hipMemoryTypeDevice && attr.type != hipMemoryTypeManaged)
-        return fail(YALPS_E_ARG, who + " is host memory: operands and outputs are device pointers");
-    if (attr.type == hipMemoryTypeDevice && attr.device != b->device)
-        return fail(YALPS_E_ARG, who + " is memory of device " + std::to_string(attr.device) + ", the handle is on device " + std::to_string(b->device));
-    return 0;
-}
-
-MilpDenseOperand operand(const yalps_milpdense_operand *o, bool vector) {
-    return MilpDenseOperand{o->ptr, (long long)o->batch, (long long)o->row, vector ? 0ll : (long long)o->col};
 }
 
 int create_impl(int32_t device, void *hip_stream, yalps_milpdense **out) {
@@ -309,7 +252,7 @@ int solve_impl(yalps_milpdense *b, const char *entry, int32_t count, int32_t n, 
                     {"node_pivots_out", node_pivots_out},
                     {"root_pivots_out", root_pivots_out}};
     for (const auto &a : pointers)
-        if (int rc = check_pointer(b, entry, a.name, a.p)) return rc;
+        if (int rc = check_pointer(b->device, entry, a.name, a.p)) return rc;
 
     hipStream_t s = b->stream;
     const int32_t cols_n = nints + int_twins; // n_int_eff: the integer columns the trees branch on
@@ -318,16 +261,16 @@ int solve_impl(yalps_milpdense *b, const char *entry, int32_t count, int32_t n, 
     const bool aux = lp_class(w, h) == HBM_CLASS && lp_aux_hbm(w, h);
 
     // ---- the root pass: the description and the binary list behind it, one launch per pass, tableaux kept for the trees
-    // (a bounded call: the longer description, and behind the binary list the bound rows' index list and the kind bytes; a call
-    // with free variables: the longest, and behind the kind bytes, from the next multiple of 4, free_idx and twin)
-    const size_t desc_bytes = split ? sizeof(MilpDenseFreeCall) : bounds ? sizeof(MilpDenseBoundsCall) : sizeof(MilpDenseCall);
+    // (a bounded call: more of the description, and behind the binary list the bound rows' index list and the kind bytes; a call
+    // with free variables: all of it, and behind the kind bytes, from the next multiple of 4, free_idx and twin)
+    const size_t desc_bytes = dense_desc_bytes(bounds, split);
     const size_t call_bytes = (desc_bytes + 15) & ~(size_t)15;
     const size_t bin_bytes = sizeof(int32_t) * (size_t)nbin, idx_bytes = sizeof(int32_t) * (size_t)n_upper;
     const size_t kind_bytes = ((size_t)n + 3) & ~(size_t)3, free_bytes = sizeof(int32_t) * (size_t)n_free, twin_bytes = sizeof(int32_t) * (size_t)n;
     if (int rc = ensure(b->call, call_bytes + bin_bytes + (lists ? idx_bytes + (split ? kind_bytes + free_bytes + twin_bytes : (size_t)n) : 0))) return rc;
     b->q.keep = true;
     if (int rc = ensure_outputs(b->q, cnt, heven * cnt, perm * cnt, (size_t)w * (size_t)h * cnt)) return rc;
-    MilpDenseFreeCall D{};
+    DenseDesc D{};
     D.n = n, D.m_ub = m_ub, D.m_eq = m_eq, D.n_bin = nbin;
     D.aux_hbm = aux ? 1 : 0;
     D.sign = maximize ? 1.0 : -1.0;
@@ -374,7 +317,7 @@ int solve_impl(yalps_milpdense *b, const char *entry, int32_t count, int32_t n, 
     const int rc = run_queue(
         b->root, b->q, split ? free_kernels().roots : bounds ? bounds_kernels().roots : kRootKernels, QueueText{"yalps_milpdense", true, entry, "MILP"}, cnt,
         [&](int32_t, int *iw, int *ih) { return *iw = w, *ih = h, checkCycles != 0; },
-        [&](MilpDenseLaunch &a) { a.call = b->call.as<const MilpDenseCall>(); }, [] { return 0; },
+        [&](MilpDenseLaunch &a) { a.call = b->call.as<const DenseDesc>(); }, [] { return 0; },
         [&](const Launch &L, const std::string &kernel, int pass, int launch, long long hist_cap) {
             char line[256];
             std::snprintf(line, sizeof line, "launch=%d pass=%d kernel=%s class=%d aux=%d lps=%zu grid=%d lds=%zu hist_cap=%lld\n", launch,
@@ -453,7 +396,7 @@ int solve_impl(yalps_milpdense *b, const char *entry, int32_t count, int32_t n, 
         if (nodes_out) HIP_TRY(hipMemsetAsync(nodes_out, 0, sizeof(int64_t) * cnt, s));
         if (node_pivots_out) HIP_TRY(hipMemsetAsync(node_pivots_out, 0, sizeof(int64_t) * cnt, s));
     }
-    MilpFreeSolutionArgs a{};
+    MilpSolutionArgs a{};
     a.n = n, a.h0 = h, a.hmax = hmax, a.overflow = YALPS_MILPDENSE_OVERFLOW;
     a.sign = D.sign, a.precision = precision;
     a.status = last.status.as<const int32_t>();
@@ -466,18 +409,10 @@ int solve_impl(yalps_milpdense *b, const char *entry, int32_t count, int32_t n, 
     a.status_out = status_out, a.nodes_out = reinterpret_cast<long long *>(nodes_out);
     a.node_pivots_out = reinterpret_cast<long long *>(node_pivots_out);
     HIP_TRY(hipEventRecord(b->ev0, s));
-    if (split) {
-        a.c = D.c, a.lb = D.lb, a.kind = D.kind;
-        a.n_free = n_free, a.twin = D.twin;
-        void (*const solution)(MilpFreeSolutionArgs) = free_kernels().solution;
-        solution<<<dim3((unsigned)count), dim3(SOLUTION_LANES), 0, s>>>(a);
-    } else if (bounds) {
-        a.c = D.c, a.lb = D.lb, a.kind = D.kind;
-        void (*const solution)(MilpBoundsSolutionArgs) = bounds_kernels().solution;
-        solution<<<dim3((unsigned)count), dim3(SOLUTION_LANES), 0, s>>>(static_cast<const MilpBoundsSolutionArgs &>(a));
-    } else {
-        milp_dense_solution_kernel<SOLUTION_LANES><<<dim3((unsigned)count), dim3(SOLUTION_LANES), 0, s>>>(static_cast<const MilpSolutionArgs &>(a));
-    }
+    if (lists) a.c = D.c, a.lb = D.lb, a.kind = D.kind;
+    if (split) a.n_free = n_free, a.twin = D.twin;
+    void (*const solution)(MilpSolutionArgs) = split ? free_kernels().solution : bounds ? bounds_kernels().solution : milp_dense_solution_kernel<SOLUTION_LANES>;
+    solution<<<dim3((unsigned)count), dim3(SOLUTION_LANES), 0, s>>>(a);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(b->ev1, s));
     HIP_TRY(hipStreamSynchronize(s));

@@ -31,7 +31,7 @@ namespace {
 
 // The root forms in QUEUE_KERNEL_TABLE's order: <256, false, true>, <256, true, true>, <1024, false, true>,
 // <1024, true, true>, <1024, false, false>, <1024, true, false>, each a void (*)(MilpDenseLaunch); then the epilogue <256>,
-// a void (*)(MilpBoundsSolutionArgs).
+// a void (*)(MilpSolutionArgs).
 extern "C" void yalps_milpdense_bounds_forms(void *out[7]) {
     out[0] = reinterpret_cast<void *>(milp_dense_bounds_root_kernel<256, false, true>);
     out[1] = reinterpret_cast<void *>(milp_dense_bounds_root_kernel<256, true, true>);
